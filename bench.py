@@ -18,13 +18,18 @@ the N rank processes itself when it was not started by torch.distributed.run) th
 dealt to ranks (strong scaling: the operator is fixed); each step then ends with ONE RCCL collective on y
 over xGMI, issued by libbfhip.so on the apply stream.
 
-Prints ONE JSON line on rank 0 (contract in the round prompt): metric, value, roofline{...} for the stage
-kernel from hipEvents inside the library, and cpu_baseline{...} = the CPU oracle (oracle/bfref.c, a port of
-the reference's bfMatMul / bfMatMulVec) timed on a bounded sample of the same operand on this box.
-The default line (N = 262144, one GPU) also carries two extra keys measured after the headline loop, so that the
-driver's own run times them: `nrhs64` (BASELINE configs[2], FP64-MFMA kernel) and `configs4_streamer` (the
---workload streamer measurement at N = 1M, in a child process: the operand is laid out in ~6 s by the C layout,
-compiled + synthesized in ~10 s, its CPU baseline sample takes ~20 s); --no-extra / --no-streamer skip them.
+Prints ONE JSON line on rank 0: metric, value, unit, higher_is_better, dtype, ms_per_step (the wall time of one
+timed step), and roofline{...} for the stage kernel from hipEvents inside the library.  A plain run does only
+that: it sets up, warms up, times --steps applies, writes y of the last one with --dump-outputs DIR, and prints.
+
+--full adds what the headline figure does not need: cpu_baseline{...} = the CPU oracle (oracle/bfref.c, a port
+of the reference's bfMatMul / bfMatMulVec) timed on a bounded sample of the same operand on this host, and on
+the default line (N = 262144, one GPU) the adjoint apply (packed copy and shared leaves), the host-vector path
+(`pcie_inclusive`) and three keys measured after the headline loop: `nrhs64` (BASELINE configs[2], FP64-MFMA
+kernel), `n65536` (configs[1], in a child process) and `configs4_streamer` (the --workload streamer
+measurement at N = 1M, in a child process: the operand is laid out in ~6 s by the C layout, compiled +
+synthesized in ~10 s, its CPU baseline sample takes ~20 s); --no-cpu-baseline / --no-extra / --no-streamer
+skip parts of it.
 """
 from __future__ import annotations
 
@@ -73,9 +78,16 @@ def parse_args(argv):
                     help="leaf bytes of the cpu_baseline sample (default: a quarter of the operand's leaf bytes, at least 4 GB and at most 24 GB)")
     ap.add_argument("--adjoint-both", action="store_true",
                     help="with --adjoint: after the packed-copy measurement compile the operator again with the shared-leaf adjoint plan and time that too (`adjoint_shared` key)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the 64-RHS and configs[4] measurements appended to the default line")
-    ap.add_argument("--no-streamer", action="store_true", help="skip only the configs[4] (streamed butterfly) measurement appended to the default line")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baseline, and on the default line the adjoint, "
+                         "host-vector, 64-RHS, configs[1] and configs[4] measurements (without it a run sets up, warms up, times "
+                         "--steps applies and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (y = A x) to DIR/<name>.npy, float32 / float64, "
+                         "at most 64 MB (a fixed sample of the rows of a larger y)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the measurements appended to the default line")
+    ap.add_argument("--no-streamer", action="store_true", help="with --full: skip only the configs[4] (streamed butterfly) measurement appended to the default line")
     ap.add_argument("--dtype", choices=["c128", "f64", "f32"], default=None,
                     help="helm2: c128 (headline); f64 / f32 = the same block layout with real values (a kernel proxy).  "
                          "streamer: f32 (default; the build's extension, configs[4]) or f64 (the reference's type)")
@@ -95,6 +107,10 @@ def parse_args(argv):
                          "rowblocks = whole top-level block rows by LPT + all-gather; blocks = top-level (row, col) blocks by LPT + ONE all-reduce; "
                          "rowsum = whole block rows + column shares of the rest, ONE all-gather, shared rows' partials added in rank order (no replication)")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:              # a plain run times the headline only: what else the line can carry needs --full
+        args.no_cpu_baseline = args.no_extra = True
     if args.gpus is None:          # started by torch.distributed.run without --gpus: the launcher's world size is the job's
         args.gpus = int(os.environ.get("WORLD_SIZE", "1"))
     return args
@@ -167,16 +183,54 @@ def pad_to_common_length(dist, vec, use_pg):
     return torch.cat([vec, torch.zeros(int(m.item()) - vec.numel(), dtype=vec.dtype, device=vec.device)])
 
 
+DUMP_LIMIT_BYTES = 64_000_000
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array of `arrays` (name -> torch tensor) as <out_dir>/<name>.npy in float64 / float32, a complex
+    one with a trailing [re, im] axis.  Past DUMP_LIMIT_BYTES in all, the same seeded sample of rows is kept of every array,
+    and its row indices go to <out_dir>/<name>_rows.npy (float64, exact)."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.is_complex():
+            t = torch.view_as_real(t.resolve_conj())
+        if t.dtype not in (torch.float32, torch.float64):
+            t = t.to(torch.float64)
+        host[name] = t.cpu().numpy()
+    total = sum(a.nbytes for a in host.values())
+    for name, a in host.items():
+        rows = None
+        if total > DUMP_LIMIT_BYTES and a.ndim and a.shape[0] > 1:
+            row_bytes = a.nbytes // a.shape[0] + 8              # (+ the index of the row)
+            keep = max(1, min(a.shape[0], int(DUMP_LIMIT_BYTES / len(host) - 4096) // row_bytes))
+            rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(a.shape[0], size=keep, replace=False))
+            a = a[rows]
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a))
+        if rows is not None:
+            np.save(os.path.join(out_dir, f"{name}_rows.npy"), rows.astype(np.float64))
+
+
 # ---------------------------------------------------------------------------------------------------
 # CPU baselines (the oracle as the checker and as the stated baseline; never the thing shipped)
 # ---------------------------------------------------------------------------------------------------
+_BLAS_POOL = []      # threads OpenBLAS started with (OPENBLAS_NUM_THREADS / OMP_NUM_THREADS, at most the host's cores)
+
+
 def _blas_one_thread():
     from oracle import bfref
     blas = bfref.try_use_openblas()
     if blas:
         try:                                   # "cores": 1 must be true: the reference is serial (SURVEY 8(d))
             import ctypes
-            ctypes.CDLL(blas).scipy_openblas_set_num_threads(1)
+            ob = ctypes.CDLL(blas)
+            if not _BLAS_POOL:
+                _BLAS_POOL.append(int(ob.scipy_openblas_get_num_threads()))
+            ob.scipy_openblas_set_num_threads(1)
         except Exception:
             pass
     return blas
@@ -217,13 +271,14 @@ def cpu_baseline_helm2(desc, seed, total_leaf_elems, weights, budget_bytes, nrhs
         reps += 1
     cnt = bfref.counters()
     # The reference is single-threaded and its leaf GEMMs are small; for blocks of RHS also time
-    # the same port with OpenBLAS on every host core this process may use
+    # the same port with OpenBLAS on every host core this process may use.  The thread count stays within the
+    # pool OpenBLAS started with: raising it above that pool makes the bundled OpenBLAS crash in its next GEMM.
     multi = None
     if blas and nrhs >= 3:
         try:
             import ctypes
             ob = ctypes.CDLL(blas)
-            ncores = len(os.sched_getaffinity(0))
+            ncores = max(1, min(len(os.sched_getaffinity(0)), _BLAS_POOL[0] if _BLAS_POOL else 1))
             ob.scipy_openblas_set_num_threads(ncores)
             bm = None
             for _ in range(2):
@@ -245,7 +300,7 @@ def cpu_baseline_helm2(desc, seed, total_leaf_elems, weights, budget_bytes, nrhs
     extra = {}
     if multi:
         extra["all_cores"] = {"value": nrhs / (multi[1] / frac), "unit": "matvec/s", "cores": multi[0],
-                              "note": "same port, OpenBLAS threads = host cores available to this process"}
+                              "note": "same port, OpenBLAS threads = host cores available to this process, within OpenBLAS's thread pool"}
     return dict(value=full_equiv, unit="matvec/s", cores=1, kind="port", **extra,
                 sample=(f"EXTRAPOLATED from a {frac * 100:.1f}% sample: top-level block rows {chosen} of {len(weights)} "
                         f"({sample_elems * 16 / 1e9:.2f} GB of {total_leaf_elems * 16 / 1e9:.2f} GB leaf data), best of {reps} in "
@@ -678,6 +733,9 @@ def main():
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller: y = A x (in an emulated run, the rows of the emulated rank's shard)
+        dump_outputs(args.dump_outputs, {"y": y_full})
     ms, launches, sbytes = op.stage_profile()
     op.set_profile_sampling(1)
 
@@ -1125,7 +1183,7 @@ def main():
         # BASELINE configs[1] (N = 65536, k = 4096, one right-hand side: launches of ~1 GB) in a child process: its own line
         try:
             torch.cuda.empty_cache()
-            cmd = [sys.executable, os.path.abspath(__file__), "--npoints", "65536", "--steps", "50", "--warmup", "5", "--no-extra", "--pcie",
+            cmd = [sys.executable, os.path.abspath(__file__), "--npoints", "65536", "--steps", "50", "--warmup", "5", "--full", "--no-extra", "--pcie",
                    "--seed", str(args.seed)]
             env = dict(os.environ)
             for k_ in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
@@ -1147,7 +1205,7 @@ def main():
             try:
                 torch.cuda.empty_cache()
                 cmd = [sys.executable, os.path.abspath(__file__), "--workload", "streamer", "--steps", "10", "--warmup", "2", "--adjoint", "--adjoint-both",
-                       "--no-extra", "--seed", str(args.seed)]
+                       "--full", "--no-extra", "--seed", str(args.seed)]
                 env = dict(os.environ)
                 for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
                     env.pop(k, None)

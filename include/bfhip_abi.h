@@ -24,8 +24,8 @@
  * a debug build appends two pointers to BfMat, mat.h:192-195, and is refused
  * by bfhipCompile's sanity walk).  The vtable is declared as an array of 66
  * untyped slots plus the indices the engine needs; sizes and offsets are
- * pinned by _Static_asserts below and re-validated against the reference's
- * real headers by tests/test_abi_layout.py when /root/reference is present.
+ * pinned by _Static_asserts below and re-validated by tests/test_abi_layout.py
+ * against the layout recorded from the reference's real headers.
  */
 #ifndef BFHIP_ABI_H
 #define BFHIP_ABI_H

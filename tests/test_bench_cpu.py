@@ -93,3 +93,39 @@ def test_a_launcher_without_the_gpus_flag_sets_the_world_size():
                         "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--npoints", "16384"], capture_output=True, text=True, timeout=600, env=env)
     assert p.returncode == 0, p.stderr[-2000:]
     assert _line(p)["n_gpus"] == 2
+
+
+def test_plain_run_and_full_options():
+    """A plain run measures the headline only (no CPU baselines, nothing appended to the line); --full brings them back,
+    and --steps is the number of timed steps (at least one)."""
+    import pytest
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and a.no_cpu_baseline and a.no_extra and a.dump_outputs is None
+    f = bench.parse_args(["--gpus", "1", "--full", "--dump-outputs", "out"])
+    assert not f.no_cpu_baseline and not f.no_extra and f.dump_outputs == "out"
+    assert bench.parse_args(["--full", "--no-cpu-baseline"]).no_cpu_baseline
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+
+
+def test_dump_outputs_formats_and_bound(tmp_path):
+    """Complex arrays are written as float64 [re, im]; real ones keep float32 / float64; past 64 MB in all the same seeded
+    sample of rows is written, with its row indices."""
+    import numpy as np
+    import torch
+    import bench
+    small = torch.arange(6, dtype=torch.float64).to(torch.complex128) * (1 - 2j)
+    bench.dump_outputs(str(tmp_path / "s"), {"y": small, "z": torch.ones(3, 2, dtype=torch.float32)})
+    y, z = np.load(tmp_path / "s" / "y.npy"), np.load(tmp_path / "s" / "z.npy")
+    assert y.dtype == np.float64 and y.shape == (6, 2) and np.array_equal(y[:, 0] + 1j * y[:, 1], small.numpy())
+    assert z.dtype == np.float32 and z.shape == (3, 2) and not (tmp_path / "s" / "y_rows.npy").exists()
+    big = torch.randn(300_000, 16, dtype=torch.complex128, generator=torch.Generator().manual_seed(3))      # 76.8 MB
+    for d in ("b1", "b2"):
+        bench.dump_outputs(str(tmp_path / d), {"y": big})
+    files = list((tmp_path / "b1").iterdir())
+    assert sum(p.stat().st_size for p in files) <= 64_000_000 and {p.name for p in files} == {"y.npy", "y_rows.npy"}
+    y, rows = np.load(tmp_path / "b1" / "y.npy"), np.load(tmp_path / "b1" / "y_rows.npy")
+    assert rows.dtype == np.float64 and len(rows) == len(y) > 200_000 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(y[..., 0] + 1j * y[..., 1], big.numpy()[rows.astype(np.int64)])
+    assert np.array_equal(y, np.load(tmp_path / "b2" / "y.npy"))

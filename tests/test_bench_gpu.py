@@ -23,7 +23,7 @@ def run_bench(*extra):
 
 
 def test_default_contract_keys():
-    d = run_bench("--cpu-budget-gb", "0.05")
+    d = run_bench("--full", "--cpu-budget-gb", "0.05")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k
@@ -35,6 +35,35 @@ def test_default_contract_keys():
     c = d["cpu_baseline"]
     assert c["kind"] == "port" and c["cores"] == 1 and c["value"] > 0 and c["parity_rel_l2"] < 1e-12
     assert abs(d["value"] - 3 / (d["ms_per_step"] * 3e-3)) / d["value"] < 1e-6
+
+
+def test_plain_run_times_the_headline_only():
+    """Without --full a run sets up, warms up, times --steps applies and prints the line: no CPU baseline, nothing else timed."""
+    d = run_bench()
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["dtype"] == "c128" and d["unit"] == "matvec/s" and d["higher_is_better"] is True
+    assert abs(d["value"] - 3 / (d["ms_per_step"] * 3e-3)) / d["value"] < 1e-6
+    for k in ("cpu_baseline", "adjoint", "adjoint_shared", "pcie_inclusive", "nrhs64", "n65536", "configs4_streamer"):
+        assert k not in d, k
+
+
+def test_dump_outputs_hold_the_last_step(tmp_path):
+    """--dump-outputs DIR: y of the last timed step as float64 [re, im], the same from run to run, equal to the oracle's
+    apply of the same seeded operand to the same seeded x."""
+    import numpy as np
+    from butterfly_amd import helm2_structure as hs
+    from oracle import bfref
+    a, b = tmp_path / "a", tmp_path / "b"
+    run_bench("--dump-outputs", str(a))
+    run_bench("--dump-outputs", str(b), "--steps", "5")
+    ya, yb = np.load(a / "y.npy"), np.load(b / "y.npy")
+    assert sorted(p.name for p in a.iterdir()) == ["y.npy"] and ya.dtype == np.float64 and ya.shape == (8192, 2)
+    assert np.array_equal(ya, yb)
+    desc, _ = hs.native_multilevel_structure(hs.circle_points(8192), 8192 / 16.0)
+    rng = np.random.default_rng(1234)
+    x = (rng.standard_normal(8192) + 1j * rng.standard_normal(8192)) / np.sqrt(2)
+    y_ref = bfref.mat_mul(bfref.from_desc(desc, None, seed=1234), x[:, None])[:, 0]
+    y = ya[:, 0] + 1j * ya[:, 1]
+    assert np.linalg.norm(y - y_ref) / np.linalg.norm(y_ref) < 1e-12
 
 
 def test_rhs_block_reports_mfma_roofline():
@@ -61,7 +90,7 @@ def test_multi_rank_reporting_with_one_rank(monkeypatch):
     the bit-identical row shard timed next to a default that is not `rows`, the parity sample on a shared block row -- through
     the same code with ONE rank (--force-collective starts a 1-rank process group)."""
     monkeypatch.setenv("BENCH_ALSO_TIME_ROWS", "1")
-    d = run_bench("--force-collective", "--shard", "rowsum", "--cpu-budget-gb", "0.05")
+    d = run_bench("--force-collective", "--shard", "rowsum", "--full", "--cpu-budget-gb", "0.05")
     m = d["multi_gpu"]
     assert m["mode"] == "rowsum" and m["ranks_agree"] and m["ranks_max_abs_diff"] == 0.0 and m["collective_impl"].startswith("libbfhip")
     assert m["also_timed"]["mode"] == "rows" and m["also_timed"]["bit_identical_to_one_gpu"] and m["also_timed"]["ranks_agree"] and m["also_timed"]["ms_per_step"] > 0
@@ -132,7 +161,7 @@ def test_streamer_workload_contract():
 
 def run_streamer():
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "streamer", "--npoints", "16384", "--lmax", "31", "--steps", "3",
-           "--warmup", "1", "--adjoint", "--cpu-budget-gb", "0.05"]
+           "--warmup", "1", "--adjoint", "--full", "--cpu-budget-gb", "0.05"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]

@@ -9,7 +9,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/records_$TAG
 mkdir -p $O
 cd $R
-B="timeout -k 10 400 python bench.py"
+B="timeout -k 10 400 python bench.py --full"
 run() { local name=$1; shift; "$@" > $O/$name.json 2> $O/$name.err; echo "$name exit=$?"; }      # (an env assignment in front of `run` reaches the command)
 if [ "$PART" = all ] || [ "$PART" = single ]; then
 run ${TAG}_bench_n262144                 $B --pcie
@@ -37,7 +37,7 @@ BFHIP_LIB_PATH=$EXPLIB BFHIP_FLOW=1 run ${TAG}_bench_n262144_flow $B --no-cpu-ba
 BFHIP_LIB_PATH=$EXPLIB BFHIP_PERSISTENT=1 run ${TAG}_bench_n65536_persistent $B --npoints 65536 --no-cpu-baseline --no-extra
 BFHIP_LIB_PATH=$EXPLIB BFHIP_PERSISTENT=1 run ${TAG}_bench_n262144_persistent $B --no-cpu-baseline --no-extra
 # BASELINE configs[4]: the streamed real butterfly (fac_streamer structure, rank model), fp32 and fp64
-S="timeout -k 10 900 python bench.py --workload streamer"
+S="timeout -k 10 900 python bench.py --full --workload streamer"
 run ${TAG}_bench_streamer_n1048576_f32   $S --adjoint --steps 10
 run ${TAG}_bench_streamer_n1048576_f32_adjoint_shared $S --adjoint --adjoint-shared --steps 10 --no-cpu-baseline
 run ${TAG}_bench_streamer_n1048576_f64   $S --dtype f64 --adjoint --steps 10 --no-cpu-baseline

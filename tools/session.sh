@@ -15,7 +15,7 @@ step() { # name limit cmd...
   echo "$name exit=$rc"
   if [ $rc -eq 124 ] || [ $rc -eq 137 ]; then echo "step $name hit its limit: stopping"; tail -5 $O/$name.err; exit 1; fi
 }
-B="python bench.py"
+B="python bench.py --full"
 gputests()   { step pytest 900 python -m pytest tests -m gpu -x -q; tail -5 $O/pytest.out; }
 n65536()     { step bench_n65536 300 $B --npoints 65536 --steps 50 --warmup 5 --no-cpu-baseline --no-extra; grep "stage " $O/bench_n65536.err; cat $O/bench_n65536.out | cut -c1-400; }
 shards8()    { step shards8_rows 600 $B --emulate-world 8 --emulate-rank -1 --steps 20 --no-extra --no-cpu-baseline --shard rows;
