@@ -10,7 +10,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BFHIP_LIB_PATH") or os.path.join(_HERE, "csrc", "libbfhip.so")      # (the override is for A/B builds of the kernels)
 
-BFHIP_C128, BFHIP_F64, BFHIP_F32 = 0, 1, 2
+BFHIP_C128, BFHIP_F64, BFHIP_F32, BFHIP_C64 = 0, 1, 2, 3
 FLAG_PROFILE = 1
 FLAG_PLAN_ONLY = 2
 FLAG_ADJOINT = 4

@@ -151,8 +151,21 @@ static int uploadArray(void **d, void const *h, size_t bytes, uint64_t *meta) {
 
 /* write one piece (mr x ncols sub-block of a leaf, column-major, rows padded
  * to mrPad) at dst */
-static void packPiece(BfPlan const *pl, BfIr const *ir, BfDevPiece const *pc, BfPieceSrc const *src,
+static int packPiece(BfPlan const *pl, BfIr const *ir, BfDevPiece const *pc, BfPieceSrc const *src,
                       uint32_t mr, uint32_t mrPad, unsigned char *dst, uint64_t seed) {
+  if (pl->dtype == BFHIP_C64) {
+    /* complex64: the piece is packed in complex128 (decorations added in double), then each component is rounded once; the
+     * device synthesizer (bfSynthKernel<BFHIP_C64>) rounds the same double values */
+    size_t const elems = (pc->flags & BF_PIECE_ROWMAJOR) ? (size_t)mr * pc->ld : (size_t)mrPad * pc->ncols;
+    double *wide = malloc(elems * 16 + 16);
+    if (!wide) return bfhipFail(BFABI_ERROR_MEMORY_ERROR, "host OOM (complex64 packing)");
+    BfPlan wp = *pl;
+    wp.dtype = BFHIP_C128;
+    int const rc = packPiece(&wp, ir, pc, src, mr, mrPad, (unsigned char *)wide, seed);
+    if (!rc) for (size_t k = 0; k < 2 * elems; ++k) ((float *)dst)[k] = (float)wide[k];
+    free(wide);
+    return rc;
+  }
   uint64_t node = src->node;
   void const *data = ir->leafData[node];
   int const cplx = pl->dtype == BFHIP_C128;
@@ -189,7 +202,8 @@ static void packPiece(BfPlan const *pl, BfIr const *ir, BfDevPiece const *pc, Bf
     for (uint32_t r = 0; r < mr; ++r)
       for (uint32_t c = pc->ncols; c < pc->ld; ++c) {
         uint64_t e = (uint64_t)r * pc->ld + c;
-        if (pl->dtype == BFHIP_F64) ((double *)dst)[e] = 0; else ((float *)dst)[e] = 0;
+        if (cplx) ((double *)dst)[2 * e] = ((double *)dst)[2 * e + 1] = 0;
+        else if (pl->dtype == BFHIP_F64) ((double *)dst)[e] = 0; else ((float *)dst)[e] = 0;
       }
   /* sparse decorations folded into this leaf (bfhip_ir.c: tryFold): patches are sorted by (leaf, row, col) */
   if (ir->numPatches && data) {
@@ -204,6 +218,7 @@ static void packPiece(BfPlan const *pl, BfIr const *ir, BfDevPiece const *pc, Bf
       else ((float *)dst)[e] = (float)((double)((float *)dst)[e] + pt->re);
     }
   }
+  return 0;
 }
 
 /* pack leaves into the arena, stage by stage, in arena order.  hostDst != NULL:
@@ -212,7 +227,7 @@ static void packPiece(BfPlan const *pl, BfIr const *ir, BfDevPiece const *pc, Bf
  * device. */
 static int packLeavesPlan(BfPlan const *pl, void *dArena, BfIr const *ir, uint64_t seed, void *hostDst) {
   size_t const es = pl->elemSize;
-  int const cplx = pl->dtype == BFHIP_C128;
+  int const cplx = bfDtypeComplex(pl->dtype);
   size_t const chunkBytes = (size_t)64 << 20;
   unsigned char *stage = NULL;
   BfSynthPiece *synth = NULL;
@@ -233,7 +248,7 @@ static int packLeavesPlan(BfPlan const *pl, void *dArena, BfIr const *ir, uint64
         uint64_t node = src->node;
         size_t bytes = ((pc->flags & BF_PIECE_ROWMAJOR) ? (size_t)mr * pc->ld : (size_t)mrPad * pc->ncols) * es;
         if (hostDst) {
-          packPiece(pl, ir, pc, src, mr, mrPad, (unsigned char *)hostDst + pc->dataOff * es, seed);
+          if ((rc = packPiece(pl, ir, pc, src, mr, mrPad, (unsigned char *)hostDst + pc->dataOff * es, seed))) break;
           continue;
         }
         if (!ir->leafData[node]) {
@@ -268,7 +283,7 @@ static int packLeavesPlan(BfPlan const *pl, void *dArena, BfIr const *ir, uint64
         }
         if (!fill) chunkBase = pc->dataOff;
         if (bytes > chunkBytes) { rc = bfhipFail(BFABI_ERROR_RUNTIME_ERROR, "piece larger than staging chunk"); break; }
-        packPiece(pl, ir, pc, src, mr, mrPad, stage + fill, seed);
+        if ((rc = packPiece(pl, ir, pc, src, mr, mrPad, stage + fill, seed))) break;
         fill += bytes;
       }
     }
@@ -460,10 +475,7 @@ int bfhipCompileIrFill(BfIr *ir, BfhipOptions const *opts, BfFillFn fill, void *
   BfPlanOptions po;
   memset(&po, 0, sizeof po);
   po.storeDtype = ir->dtype;
-  if (o.demoteToF32) {
-    if (ir->dtype != BFHIP_F64) { rc = bfhipFail(BFABI_ERROR_TYPE_ERROR, "demoteToF32 applies to real operands only"); goto done; }
-    po.storeDtype = BFHIP_F32;
-  }
+  if (o.demoteToF32) po.storeDtype = ir->dtype == BFHIP_C128 ? BFHIP_C64 : BFHIP_F32;
   po.groupByInput = o.maxRhs >= 3;
 #ifndef BF_MIN_CHUNK_ROWS
 #define BF_MIN_CHUNK_ROWS 16     /* lower bound of the adaptive item height, in 16-byte row units (A/B builds: 8) */
@@ -490,7 +502,7 @@ int bfhipCompileIrFill(BfIr *ir, BfhipOptions const *opts, BfFillFn fill, void *
      * per stage (N = 1M fp32: 8.66 -> 8.08 ms; 16384: 8.25, 65536: 8.15) costs nothing but a few more partial sums.  Complex
      * (fac_helm2) plans keep 4096: their stages are 10 GB, the cap binds either way and more items measured 1-2 % slower, as did
      * more items in the FORWARD plan of either operand (DESIGN_EXPERIMENTS.md section 10). */
-    if (op->plan.dtype != BFHIP_C128) pt.itemsWanted = 32768;
+    if (!bfDtypeC128Layout(op->plan.dtype)) pt.itemsWanted = 32768;
     if ((rc = bfPlanBuild(&irT, &pt, &op->tplan))) goto done;
     op->hasTplan = 1;
     op->packedT = 1;
@@ -868,7 +880,7 @@ static int covScratch(BfhipOperator *op) {
 
 int bfhipCovSampleDevice(BfhipOperator *op, void const *dGammaLam, uint64_t const *dRowPerm, void const *dW, void *dZ, void *stream) {
   if (!op || !dW || !dZ) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL argument");
-  if (op->plan.dtype == BFHIP_C128) return bfhipFail(BFABI_ERROR_TYPE_ERROR, "covariance products are defined for real operators");
+  if (bfDtypeComplex(op->plan.dtype)) return bfhipFail(BFABI_ERROR_TYPE_ERROR, "covariance products are defined for real operators (not complex128 / complex64)");
   if (op->flags & BFHIP_FLAG_PLAN_ONLY) return bfhipFail(BFABI_ERROR_RUNTIME_ERROR, "operator was compiled with BFHIP_FLAG_PLAN_ONLY: no device operator exists");
   int rc, prev = -1;
   bfdevGetDevice(&prev);
@@ -888,7 +900,7 @@ out:
 
 int bfhipCovMatvecDevice(BfhipOperator *op, void const *dGammaLam, uint64_t const *dRowPerm, uint64_t const *dRevRowPerm, void const *dV, void *dZ, void *stream) {
   if (!op || !dV || !dZ) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL argument");
-  if (op->plan.dtype == BFHIP_C128) return bfhipFail(BFABI_ERROR_TYPE_ERROR, "covariance products are defined for real operators");
+  if (bfDtypeComplex(op->plan.dtype)) return bfhipFail(BFABI_ERROR_TYPE_ERROR, "covariance products are defined for real operators (not complex128 / complex64)");
   if (!op->hasTplan) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "operator was not compiled with BFHIP_FLAG_ADJOINT");
   if (op->flags & BFHIP_FLAG_PLAN_ONLY) return bfhipFail(BFABI_ERROR_RUNTIME_ERROR, "operator was compiled with BFHIP_FLAG_PLAN_ONLY: no device operator exists");
   int rc, prev = -1;
@@ -929,6 +941,7 @@ static int applyHost(BfhipOperator *op, int transpose, void const *X, size_t ldx
   if ((rc = bfdevSetDevice(op->device))) return rc;
   size_t es = op->plan.elemSize;
   size_t hostEs = op->srcDtype == BFHIP_C128 ? 16 : 8;      /* host side is always double precision */
+  size_t const nc = bfDtypeComplex(op->plan.dtype) ? 2 : 1;  /* scalars per element (the fp32 / complex64 conversions below) */
   uint64_t n = transpose ? op->plan.numRows : op->plan.numCols, m = transpose ? op->plan.numCols : op->plan.numRows;
   uint64_t big = n > m ? n : m;
   int const same = es == hostEs;
@@ -959,7 +972,7 @@ static int applyHost(BfhipOperator *op, int transpose, void const *X, size_t ldx
         if (ldx == nrhs) memcpy((char *)hx + r0 * nrhs * es, (char const *)X + r0 * nrhs * es, (r1 - r0) * nrhs * es);
         else for (uint64_t i = r0; i < r1; ++i) memcpy((char *)hx + i * nrhs * es, (char const *)X + i * ldx * es, nrhs * es);
       } else {
-        for (uint64_t i = r0; i < r1; ++i) for (size_t q = 0; q < nrhs; ++q) ((float *)hx)[i * nrhs + q] = (float)((double const *)X)[i * ldx + q];
+        for (uint64_t i = r0; i < r1; ++i) for (size_t q = 0; q < nrhs * nc; ++q) ((float *)hx)[i * nrhs * nc + q] = (float)((double const *)X)[i * ldx * nc + q];
       }
       if ((rc = bfdevMemcpyH2DAsync((char *)op->dX + r0 * nrhs * es, (char *)hx + r0 * nrhs * es, (r1 - r0) * nrhs * es, NULL))) goto out;
     }
@@ -985,7 +998,7 @@ static int applyHost(BfhipOperator *op, int transpose, void const *X, size_t ldx
         if (ldy == nrhs) memcpy((char *)Y + r0 * nrhs * es, (char *)hy + r0 * nrhs * es, (r1 - r0) * nrhs * es);
         else for (uint64_t i = r0; i < r1; ++i) memcpy((char *)Y + i * ldy * es, (char *)hy + i * nrhs * es, nrhs * es);
       } else {
-        for (uint64_t i = r0; i < r1; ++i) for (size_t q = 0; q < nrhs; ++q) ((double *)Y)[i * ldy + q] = ((float *)hy)[i * nrhs + q];
+        for (uint64_t i = r0; i < r1; ++i) for (size_t q = 0; q < nrhs * nc; ++q) ((double *)Y)[i * ldy * nc + q] = ((float *)hy)[i * nrhs * nc + q];
       }
     }
     if (m == 0 && (rc = bfdevSync(NULL))) goto out;
@@ -1212,7 +1225,7 @@ static int validateStage(BfPlan const *pl, uint64_t arenaElems, BfStage const *s
     if (!mr || mr > pl->maxItemRows || mr > st->maxRows || (it->mrFlags & ~(0xffffu | BF_ITEM_OUT_Y | BF_ITEM_ROWMAJOR | BF_ITEM_MERGED | BF_ITEM_SMALL | BF_ITEM_TNARROW)) ||
         ((it->mrFlags & BF_ITEM_TNARROW) != 0) != (i < st->numNarrow) || ((it->mrFlags & BF_ITEM_TNARROW) && (!pl->transposed || mr > 16)) ||
         ((it->mrFlags & BF_ITEM_SMALL) != 0) != (i >= st->firstSmall) ||
-        ((it->mrFlags & BF_ITEM_ROWMAJOR) && (pl->transposed || pl->dtype == BFHIP_C128 || mr > 2 * pl->epl)) ||
+        ((it->mrFlags & BF_ITEM_ROWMAJOR) && (pl->transposed || bfDtypeC128Layout(pl->dtype) || mr > 2 * pl->epl)) ||
         (pl->transposed && mr > 64) ||       /* bfStageKernelT: at most 64 columns of A per item */
         !fitsIn(it->outOff, mr, outLen) || !fitsIn(it->pieceBegin, it->numPieces, st->numPieces))
       return bfhipFail(BFABI_ERROR_FILE_ERROR, "corrupt operator file: item %llu out of bounds", (unsigned long long)i);
@@ -1221,7 +1234,7 @@ static int validateStage(BfPlan const *pl, uint64_t arenaElems, BfStage const *s
       int const sm = (it->mrFlags & BF_ITEM_SMALL) != 0;
       uint64_t next = 0, dense = 0;
       int const smRm = sm && (it->mrFlags & BF_ITEM_ROWMAJOR);      /* small items: row-major pieces, no contiguity promise */
-      int badm = pl->transposed || pl->dtype == BFHIP_C128 || (!sm && (it->mrFlags & BF_ITEM_ROWMAJOR)) || it->numPieces > (sm ? BF_SMALL_PIECES : 64u) ||
+      int badm = pl->transposed || bfDtypeC128Layout(pl->dtype) || (!sm && (it->mrFlags & BF_ITEM_ROWMAJOR)) || it->numPieces > (sm ? BF_SMALL_PIECES : 64u) ||
                  (sm && (mr > 2 * pl->epl || !(it->mrFlags & BF_ITEM_ROWMAJOR)));
       for (uint32_t k = 0; k < it->numPieces && !badm; ++k) {
         BfDevPiece const *pc = &pieces[it->pieceBegin + k];
@@ -1240,7 +1253,7 @@ static int validateStage(BfPlan const *pl, uint64_t arenaElems, BfStage const *s
       if (!(pc->flags & BF_PIECE_IDENTITY) && !pl->transposed && rm != ((it->mrFlags & BF_ITEM_ROWMAJOR) != 0)) bad = 1;
       if (pc->flags & BF_PIECE_IDENTITY) bad |= !fitsIn(pc->inOff, mr, inLen);
       else if (pl->transposed && rm)      /* rows of a row-major forward piece: ncols rows, mr columns from dataOff */
-        bad |= !pc->ld || pc->ld % pl->epl || pc->dataOff % pl->epl || pl->dtype == BFHIP_C128 || !pc->ncols ||
+        bad |= !pc->ld || pc->ld % pl->epl || pc->dataOff % pl->epl || bfDtypeC128Layout(pl->dtype) || !pc->ncols ||
                !fitsIn(pc->dataOff, mulAddSat(pc->ncols - 1, pc->ld, (mr + pl->epl - 1) / pl->epl * pl->epl), arenaElems) ||
                !fitsIn(pc->inOff, pc->ncols, inLen);
       else if (rm)
@@ -1397,8 +1410,8 @@ int bfhipLoad(char const *path, BfhipOptions const *opts, BfhipOperator **out) {
   if (!fp) return bfhipFail(BFABI_ERROR_FILE_ERROR, "cannot open %s", path);
   FileHeader fh;
   int rc = readAll(fp, &fh, sizeof fh);
-  if (!rc && (memcmp(fh.magic, BFHIP_FILE_MAGIC, 8) != 0 || fh.version != 1 || fh.dtype > BFHIP_F32 ||
-              fh.elemSize != (fh.dtype == BFHIP_C128 ? 16u : fh.dtype == BFHIP_F64 ? 8u : 4u)))
+  if (!rc && (memcmp(fh.magic, BFHIP_FILE_MAGIC, 8) != 0 || fh.version != 1 || fh.dtype > BFHIP_C64 ||
+              fh.elemSize != bfDtypeElemSize(fh.dtype) || (fh.dtype == BFHIP_C64 && fh.srcDtype != BFHIP_C128)))
     rc = bfhipFail(BFABI_ERROR_FILE_ERROR, "%s is not a bfhip operator file (bad magic / version / dtype)", path);
   if (rc) { fclose(fp); return rc; }
   BfhipOperator *op = calloc(1, sizeof *op);

@@ -496,6 +496,8 @@ int bfhipBuildHelm2(BfhipDesc const *desc, BfhipHelm2Problem const *prob, BfhipO
   int rc = checkProblem(prob);
   if (rc) return rc;
   if (desc->dtype != BFHIP_C128) return bfhipFail(BFABI_ERROR_TYPE_ERROR, "the Helmholtz builder fills complex128 operands");
+  /* compile would accept the demotion, and fillArena writes complex128 values: refused before any device work */
+  if (opts && opts->demoteToF32) return bfhipFail(BFABI_ERROR_NOT_IMPLEMENTED, "the Helmholtz builder has no complex64 output (demoteToF32)");
   if (opts && (opts->flags & BFHIP_FLAG_PLAN_ONLY)) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "BFHIP_FLAG_PLAN_ONLY has no device to build on");
   BfhipBuildStats local;
   memset(&local, 0, sizeof local);

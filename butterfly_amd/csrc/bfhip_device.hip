@@ -29,6 +29,7 @@
 // judged on leaf bytes / time against 8 TB/s (MI355X_MICROARCH.md).
 
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #include <vector>
 #include <stdint.h>
 #include <stdio.h>
@@ -51,10 +52,49 @@ static int hipFail(hipError_t e, char const *what) {
 // ---------------------------------------------------------------------------
 // element traits
 // ---------------------------------------------------------------------------
+// S: scalar of the stored values; A: scalar the kernels accumulate in; E / EA: one element and its accumulator in the real
+// family's kernels (the complex64 operand runs on them: 8-byte elements like F64, complex MACs in double).
+struct __attribute__((aligned(8))) bfC64 { float re, im; };
+struct bfC64Acc { double re, im; };
+__device__ __forceinline__ bfC64Acc &operator+=(bfC64Acc &a, bfC64Acc b) { a.re += b.re; a.im += b.im; return a; }
+
 template <int DT> struct Traits;
-template <> struct Traits<BFHIP_C128> { using S = double; static constexpr int EPL = 1; static constexpr bool CPLX = true; };
-template <> struct Traits<BFHIP_F64> { using S = double; static constexpr int EPL = 2; static constexpr bool CPLX = false; };
-template <> struct Traits<BFHIP_F32> { using S = float; static constexpr int EPL = 4; static constexpr bool CPLX = false; };
+template <> struct Traits<BFHIP_C128> { using S = double; using A = double; static constexpr int EPL = 1; static constexpr bool CPLX = true; };
+template <> struct Traits<BFHIP_F64> { using S = double; using A = double; using E = double; using EA = double; static constexpr int EPL = 2; static constexpr bool CPLX = false; };
+template <> struct Traits<BFHIP_F32> { using S = float; using A = float; using E = float; using EA = float; static constexpr int EPL = 4; static constexpr bool CPLX = false; };
+template <> struct Traits<BFHIP_C64> { using S = float; using A = double; using E = bfC64; using EA = bfC64Acc; static constexpr int EPL = 2; static constexpr bool CPLX = true; };
+
+// acc + a * x on one element.  Real: one fma in the element type.  Complex64: both factors widened to double (exact), the
+// four fmas in the order of the complex128 transposed kernel.
+__device__ __forceinline__ double bfMac(double acc, double a, double x) { return fma(a, x, acc); }
+__device__ __forceinline__ float bfMac(float acc, float a, float x) { return fma(a, x, acc); }
+__device__ __forceinline__ bfC64Acc bfMac(bfC64Acc acc, bfC64 a, bfC64 x) {
+  double const ar = a.re, ai = a.im, xr = x.re, xi = x.im;
+  acc.re = fma(ar, xr, acc.re); acc.re = fma(-ai, xi, acc.re);
+  acc.im = fma(ar, xi, acc.im); acc.im = fma(ai, xr, acc.im);
+  return acc;
+}
+__device__ __forceinline__ double bfToAcc(double v) { return v; }
+__device__ __forceinline__ float bfToAcc(float v) { return v; }
+__device__ __forceinline__ bfC64Acc bfToAcc(bfC64 v) { return bfC64Acc{v.re, v.im}; }
+__device__ __forceinline__ double bfFromAcc(double v) { return v; }
+__device__ __forceinline__ float bfFromAcc(float v) { return v; }
+__device__ __forceinline__ bfC64 bfFromAcc(bfC64Acc v) { return bfC64{(float)v.re, (float)v.im}; }
+__device__ __forceinline__ double bfShflXor(double v, int m, int w) { return __shfl_xor(v, m, w); }
+__device__ __forceinline__ float bfShflXor(float v, int m, int w) { return __shfl_xor(v, m, w); }
+__device__ __forceinline__ bfC64Acc bfShflXor(bfC64Acc v, int m, int w) { return bfC64Acc{__shfl_xor(v.re, m, w), __shfl_xor(v.im, m, w)}; }
+
+// acc[0..NC) += a * x on NC-scalar elements in the accumulator type (the transposed kernel)
+template <int NC, typename A, typename S>
+__device__ __forceinline__ void bfMacN(A *acc, S const *a, S const *x) {
+  if constexpr (NC == 1) {
+    acc[0] = fma((A)a[0], (A)x[0], acc[0]);
+  } else {
+    A const ar = a[0], ai = a[1], xr = x[0], xi = x[1];
+    acc[0] = fma(ar, xr, acc[0]); acc[0] = fma(-ai, xi, acc[0]);
+    acc[1] = fma(ar, xi, acc[1]); acc[1] = fma(ai, xr, acc[1]);
+  }
+}
 
 template <typename V> __device__ __forceinline__ V bfLoadStreamV(V const *p) {
   static_assert(sizeof(V) == 16, "one 16-byte lane load");
@@ -97,12 +137,12 @@ __global__ __launch_bounds__(BF_C128_WG_WAVES * 64) BF_C128_ATTR void bfStageKer
 // lane + 64, ... of every row; UNR units are in flight at once, so (MR + 1) * UNR independent loads per lane.  All
 // addresses are a wave-uniform base plus a 32-bit lane offset (a piece is < 64 KiB per row set).
 template <int DT, int MR>
-__device__ __forceinline__ void bfRowMajorPiece(void const *rowpV, uint32_t upr, typename Traits<DT>::S const *xin, uint32_t n,
-                                                uint32_t nrhs, int lane, typename Traits<DT>::S *racc) {
-  using S = typename Traits<DT>::S;
+__device__ __forceinline__ void bfRowMajorPiece(void const *rowpV, uint32_t upr, typename Traits<DT>::E const *xin, uint32_t n,
+                                                uint32_t nrhs, int lane, typename Traits<DT>::EA *racc) {
+  using E = typename Traits<DT>::E;
   constexpr int EPL = Traits<DT>::EPL;
-  struct __attribute__((aligned(16))) V { S v[EPL]; };
-  struct __attribute__((packed, aligned(sizeof(S)))) VU { S v[EPL]; };     // x: element-aligned 16 bytes
+  struct __attribute__((aligned(16))) V { E v[EPL]; };
+  struct __attribute__((packed, aligned(sizeof(E)))) VU { E v[EPL]; };     // x: element-aligned 16 bytes
   char const *rowp = (char const *)rowpV;
   constexpr int UNR = MR <= 2 ? 4 : 2;
   uint32_t const rowBytes = upr * 16u;
@@ -125,7 +165,7 @@ __device__ __forceinline__ void bfRowMajorPiece(void const *rowpV, uint32_t upr,
 #pragma unroll
         for (int r = 0; r < MR; ++r) {
 #pragma unroll
-          for (int e = 0; e < EPL; ++e) racc[r] = fma(a[k][r].v[e], xv[k].v[e], racc[r]);
+          for (int e = 0; e < EPL; ++e) racc[r] = bfMac(racc[r], a[k][r].v[e], xv[k].v[e]);
         }
       }
     }
@@ -139,7 +179,7 @@ __device__ __forceinline__ void bfRowMajorPiece(void const *rowpV, uint32_t upr,
 #pragma unroll
     for (int r = 0; r < MR; ++r) {
 #pragma unroll
-      for (int e = 0; e < EPL; ++e) racc[r] = fma(a[r].v[e], xv.v[e], racc[r]);
+      for (int e = 0; e < EPL; ++e) racc[r] = bfMac(racc[r], a[r].v[e], xv.v[e]);
     }
   }
   // what is left: the ragged last unit (nrhs == 1), or everything with strided x (nrhs > 1); x past column n is
@@ -149,13 +189,13 @@ __device__ __forceinline__ void bfRowMajorPiece(void const *rowpV, uint32_t upr,
     V a[MR];
 #pragma unroll
     for (int r = 0; r < MR; ++r) a[r] = bfLoadStreamV((V const *)(rowp + ((uint32_t)r * rowBytes + u * 16u)));
-    S xv[EPL];
+    E xv[EPL];
 #pragma unroll
-    for (int e = 0; e < EPL; ++e) xv[e] = u * EPL + e < n ? xin[(uint64_t)(u * EPL + e) * nrhs] : (S)0;
+    for (int e = 0; e < EPL; ++e) xv[e] = u * EPL + e < n ? xin[(uint64_t)(u * EPL + e) * nrhs] : E{};
 #pragma unroll
     for (int r = 0; r < MR; ++r) {
 #pragma unroll
-      for (int e = 0; e < EPL; ++e) racc[r] = fma(a[r].v[e], xv[e], racc[r]);
+      for (int e = 0; e < EPL; ++e) racc[r] = bfMac(racc[r], a[r].v[e], xv[e]);
     }
   }
 }
@@ -171,10 +211,11 @@ __device__ __forceinline__ void bfRowMajorPiece(void const *rowpV, uint32_t upr,
 // one-item-per-wavefront body in one launch)
 template <int DT>
 __device__ __forceinline__ void bfStageBodySmall(StageParams const &p, uint32_t const bid) {
-  using S = typename Traits<DT>::S;
+  using E = typename Traits<DT>::E;
+  using EA = typename Traits<DT>::EA;
   constexpr int EPL = Traits<DT>::EPL;
   constexpr int RMAX = 2 * EPL;
-  struct __attribute__((aligned(16))) V { S v[EPL]; };
+  struct __attribute__((aligned(16))) V { E v[EPL]; };
   int const wave = threadIdx.x >> 6;
   int const lane = threadIdx.x & 63;
   uint32_t const item0 = __builtin_amdgcn_readfirstlane((bid * BF_WAVES_PER_WG + wave) * 4u);
@@ -197,12 +238,12 @@ __device__ __forceinline__ void bfStageBodySmall(StageParams const &p, uint32_t 
   }
   V const *arena = (V const *)p.arena;
   uint32_t const nrhs = p.nrhs;
-  S *out = (it.mrFlags & BF_ITEM_OUT_Y) ? (S *)p.y : (S *)p.temp;
+  E *out = (it.mrFlags & BF_ITEM_OUT_Y) ? (E *)p.y : (E *)p.temp;
   for (uint32_t q = 0; q < nrhs; ++q) {
-    S racc[RMAX];
+    EA racc[RMAX];
 #pragma unroll
-    for (int r = 0; r < RMAX; ++r) racc[r] = 0;
-    S ident = 0;                                       // group lane r: identity contributions to row r
+    for (int r = 0; r < RMAX; ++r) racc[r] = EA{};
+    EA ident{};                                        // group lane r: identity contributions to row r
     for (uint32_t k = 0; k < npMax; ++k) {
       int const from = (int)(gid * 16u + k);
       uint32_t const flags = (uint32_t)__shfl((int)my.flags, from, 64);
@@ -212,9 +253,9 @@ __device__ __forceinline__ void bfStageBodySmall(StageParams const &p, uint32_t 
       uint32_t const dLo = (uint32_t)__shfl((int)(uint32_t)my.dataOff, from, 64);
       uint32_t const dHi = (uint32_t)__shfl((int)(uint32_t)(my.dataOff >> 32), from, 64);
       if (k >= np) continue;
-      S const *xin = ((flags & BF_PIECE_IN_X) ? (S const *)p.x : (S const *)p.temp) + ((uint64_t)inOff * nrhs + q);
+      E const *xin = ((flags & BF_PIECE_IN_X) ? (E const *)p.x : (E const *)p.temp) + ((uint64_t)inOff * nrhs + q);
       if (flags & BF_PIECE_IDENTITY) {
-        if (gl < mr) ident += xin[(uint64_t)gl * nrhs];
+        if (gl < mr) ident += bfToAcc(xin[(uint64_t)gl * nrhs]);
         continue;
       }
       uint32_t const upr = ld / EPL;                   // 16-byte units per row: <= BF_SMALL_COLS / EPL
@@ -224,29 +265,29 @@ __device__ __forceinline__ void bfStageBodySmall(StageParams const &p, uint32_t 
         V a[RMAX];
 #pragma unroll
         for (int r = 0; r < RMAX; ++r) if ((uint32_t)r < mr) a[r] = bfLoadStreamV(base + (uint64_t)r * upr + u);
-        S xv[EPL];
+        E xv[EPL];
 #pragma unroll
-        for (int e = 0; e < EPL; ++e) xv[e] = u * EPL + e < ncols ? xin[(uint64_t)(u * EPL + e) * nrhs] : (S)0;   // the zero row padding never meets a NaN
+        for (int e = 0; e < EPL; ++e) xv[e] = u * EPL + e < ncols ? xin[(uint64_t)(u * EPL + e) * nrhs] : E{};   // the zero row padding never meets a NaN
 #pragma unroll
         for (int r = 0; r < RMAX; ++r)
           if ((uint32_t)r < mr) {
 #pragma unroll
-            for (int e = 0; e < EPL; ++e) racc[r] = fma(a[r].v[e], xv[e], racc[r]);
+            for (int e = 0; e < EPL; ++e) racc[r] = bfMac(racc[r], a[r].v[e], xv[e]);
           }
       }
     }
     // sum over the group's 16 lanes: fixed butterfly (deterministic); group lane r keeps row r
-    S mine = ident;
+    EA mine = ident;
 #pragma unroll
     for (int r = 0; r < RMAX; ++r) {
-      S t = racc[r];
-      t += __shfl_xor(t, 8, 64);
-      t += __shfl_xor(t, 4, 64);
-      t += __shfl_xor(t, 2, 64);
-      t += __shfl_xor(t, 1, 64);
+      EA t = racc[r];
+      t += bfShflXor(t, 8, 64);
+      t += bfShflXor(t, 4, 64);
+      t += bfShflXor(t, 2, 64);
+      t += bfShflXor(t, 1, 64);
       if (gl == (uint32_t)r) mine += t;
     }
-    if (gl < mr) out[((uint64_t)it.outOff + gl) * nrhs + q] = mine;
+    if (gl < mr) out[((uint64_t)it.outOff + gl) * nrhs + q] = bfFromAcc(mine);
   }
 }
 
@@ -256,21 +297,23 @@ __global__ __launch_bounds__(BF_WAVES_PER_WG * 64) __attribute__((amdgpu_waves_p
 }
 
 // ---------------------------------------------------------------------------
-// real stage kernel (f64: 2 rows per lane, f32: 4 rows per lane)
+// real-family stage kernel (f64 and complex64: 2 rows per lane, f32: 4 rows per lane)
 // ---------------------------------------------------------------------------
 #ifndef BF_REAL_UNROLL
 #define BF_REAL_UNROLL 8
 #endif
 template <int DT>
 __device__ __forceinline__ void bfStageBodyReal(StageParams const &p, uint32_t const bid, unsigned char (*ldsRaw)[BF_WAVE_LDS_BYTES]) {
-  using S = typename Traits<DT>::S;
+  using E = typename Traits<DT>::E;
+  using EA = typename Traits<DT>::EA;
   constexpr int EPL = Traits<DT>::EPL;
-  struct __attribute__((aligned(16))) V { S v[EPL]; };
+  struct __attribute__((aligned(16))) V { E v[EPL]; };
   int const wave = threadIdx.x >> 6;
   int const lane = threadIdx.x & 63;
   uint32_t item = __builtin_amdgcn_readfirstlane(bid * BF_WAVES_PER_WG + wave);
   if (item >= p.numItems) return;
-  S *xs = (S *)ldsRaw[wave];
+  E *xs = (E *)ldsRaw[wave];
+  EA *xa = (EA *)ldsRaw[wave];                       // the same bytes: the groups' accumulators at the end of an item
   V const *arena = (V const *)p.arena;
   uint32_t const nrhs = p.nrhs;
   BfDevItem const it = p.items[item];
@@ -283,7 +326,7 @@ __device__ __forceinline__ void bfStageBodyReal(StageParams const &p, uint32_t c
   uint32_t const lc = active ? (uint32_t)lane : G - 1;
   uint32_t const c = lc / ms;
   uint32_t const rs = lc - c * ms;
-  S *out = (it.mrFlags & BF_ITEM_OUT_Y) ? (S *)p.y : (S *)p.temp;
+  E *out = (it.mrFlags & BF_ITEM_OUT_Y) ? (E *)p.y : (E *)p.temp;
 
   if (it.mrFlags & BF_ITEM_ROWMAJOR) {
     // Few-row wide leaves (mr <= 2 EPL rows, stored row-major, rows padded with zeros to the lane granule): a lane
@@ -293,19 +336,19 @@ __device__ __forceinline__ void bfStageBodyReal(StageParams const &p, uint32_t c
     // lane is busy whatever mr is.  Piece descriptors come 64 at a time, one per lane.
     constexpr int RMAX = 2 * EPL;
     for (uint32_t q = 0; q < nrhs; ++q) {
-      S racc[RMAX];
+      EA racc[RMAX];
 #pragma unroll
-      for (int r = 0; r < RMAX; ++r) racc[r] = 0;
-      S ident = 0;                                   // lane r < mr: identity contributions to row r
+      for (int r = 0; r < RMAX; ++r) racc[r] = EA{};
+      EA ident{};                                    // lane r < mr: identity contributions to row r
       for (uint32_t p0 = 0; p0 < it.numPieces; p0 += 64) {
         uint32_t const np = it.numPieces - p0 < 64u ? it.numPieces - p0 : 64u;
         BfPieceWin const win = bfPieceWinLoad(p.pieces + it.pieceBegin + p0, np, lane);
         for (uint32_t pi = 0; pi < np; ++pi) {
           BfDevPiece const pc = bfPieceWinGet(win, pi);
-          S const *xin = (pc.flags & BF_PIECE_IN_X) ? (S const *)p.x : (S const *)p.temp;
+          E const *xin = (pc.flags & BF_PIECE_IN_X) ? (E const *)p.x : (E const *)p.temp;
           xin += (uint64_t)pc.inOff * nrhs + q;
           if (pc.flags & BF_PIECE_IDENTITY) {
-            if ((uint32_t)lane < mr) ident += xin[(uint64_t)lane * nrhs];
+            if ((uint32_t)lane < mr) ident += bfToAcc(xin[(uint64_t)lane * nrhs]);
             continue;
           }
           V const *rowp = arena + pc.dataOff / EPL;
@@ -322,15 +365,15 @@ __device__ __forceinline__ void bfStageBodyReal(StageParams const &p, uint32_t c
           }
         }
       }
-      S mine = ident;
+      EA mine = ident;
 #pragma unroll
       for (int r = 0; r < RMAX; ++r) {
-        S t = racc[r];
+        EA t = racc[r];
 #pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) t += __shfl_xor(t, m, 64);      // fixed order: deterministic
+        for (int m = 32; m >= 1; m >>= 1) t += bfShflXor(t, m, 64);      // fixed order: deterministic
         if ((uint32_t)lane == (uint32_t)r) mine += t;
       }
-      if ((uint32_t)lane < mr) out[((uint64_t)it.outOff + lane) * nrhs + q] = mine;
+      if ((uint32_t)lane < mr) out[((uint64_t)it.outOff + lane) * nrhs + q] = bfFromAcc(mine);
     }
     return;
   }
@@ -343,9 +386,9 @@ __device__ __forceinline__ void bfStageBodyReal(StageParams const &p, uint32_t c
   // such runs instead of hundreds of two-step contractions.  Items the planner flags BF_ITEM_MERGED are a single run.
   // A piece wider than BF_MERGE_COLS is contracted on its own, its x handed over through LDS in one loop.
   for (uint32_t q = 0; q < nrhs; ++q) {
-    S acc[EPL];
+    EA acc[EPL];
 #pragma unroll
-    for (int e = 0; e < EPL; ++e) acc[e] = 0;
+    for (int e = 0; e < EPL; ++e) acc[e] = EA{};
     for (uint32_t p0 = 0; p0 < it.numPieces; p0 += 64) {
       uint32_t const np = it.numPieces - p0 < 64u ? it.numPieces - p0 : 64u;
       BfPieceWin const win = bfPieceWinLoad(p.pieces + it.pieceBegin + p0, np, lane);
@@ -361,13 +404,13 @@ __device__ __forceinline__ void bfStageBodyReal(StageParams const &p, uint32_t c
         for (; k < np; ++k) {
           BfDevPiece const pc = bfPieceWinGet(win, k);
           if (pc.flags & BF_PIECE_IDENTITY) {
-            S const *xin = (pc.flags & BF_PIECE_IN_X) ? (S const *)p.x : (S const *)p.temp;
+            E const *xin = (pc.flags & BF_PIECE_IN_X) ? (E const *)p.x : (E const *)p.temp;
             xin += (uint64_t)pc.inOff * nrhs + q;
             if (c == 0 && active) {
 #pragma unroll
               for (int e = 0; e < EPL; ++e) {
                 uint32_t row = rs * EPL + e;
-                if (row < mr) acc[e] += xin[(uint64_t)row * nrhs];
+                if (row < mr) acc[e] += bfToAcc(xin[(uint64_t)row * nrhs]);
               }
             }
             continue;
@@ -391,7 +434,7 @@ __device__ __forceinline__ void bfStageBodyReal(StageParams const &p, uint32_t c
         uint32_t n;
         V const *ap = arena + data0 / EPL + lc;               // dataOff is in elements; a lane load is EPL elements
         if (wideCols) {
-          S const *xin = (wideFlags & BF_PIECE_IN_X) ? (S const *)p.x : (S const *)p.temp;
+          E const *xin = (wideFlags & BF_PIECE_IN_X) ? (E const *)p.x : (E const *)p.temp;
           xin += (uint64_t)wideIn * nrhs + q;
           n = wideCols;
           waveSync();
@@ -406,14 +449,14 @@ __device__ __forceinline__ void bfStageBodyReal(StageParams const &p, uint32_t c
 #pragma unroll
             for (int kk = 0; kk < 2; ++kk) {
 #pragma unroll
-              for (int e = 0; e < EPL; ++e) a2[kk].v[e] = 0;
+              for (int e = 0; e < EPL; ++e) a2[kk].v[e] = E{};
               if (active && c + kk * g < n) a2[kk] = bfLoadStreamV(ap + (uint64_t)kk * G);
             }
           }
-          S xg[XS];
+          E xg[XS];
 #pragma unroll
           for (int t = 0; t < XS; ++t)
-            xg[t] = src[t] != ~0u ? (((srcX >> t) & 1u) ? (S const *)p.x : (S const *)p.temp)[(uint64_t)src[t] * nrhs + q] : (S)0;
+            xg[t] = src[t] != ~0u ? (((srcX >> t) & 1u) ? (E const *)p.x : (E const *)p.temp)[(uint64_t)src[t] * nrhs + q] : E{};
           waveSync();
 #pragma unroll
           for (int t = 0; t < XS; ++t) if ((uint32_t)lane + 64u * t < n) xs[lane + 64 * t] = xg[t];
@@ -421,9 +464,9 @@ __device__ __forceinline__ void bfStageBodyReal(StageParams const &p, uint32_t c
           if (tiny) {
 #pragma unroll
             for (int kk = 0; kk < 2; ++kk) {
-              S xv = (active && c + kk * g < n) ? xs[c + kk * g] : (S)0;
+              E xv = (active && c + kk * g < n) ? xs[c + kk * g] : E{};
 #pragma unroll
-              for (int e = 0; e < EPL; ++e) acc[e] = fma(a2[kk].v[e], xv, acc[e]);
+              for (int e = 0; e < EPL; ++e) acc[e] = bfMac(acc[e], a2[kk].v[e], xv);
             }
             continue;
           }
@@ -442,9 +485,9 @@ __device__ __forceinline__ void bfStageBodyReal(StageParams const &p, uint32_t c
           for (int k = 0; k < BF_REAL_UNROLL; ++k) a8[k] = bfLoadStreamV(ap + (uint64_t)(s + k) * G);
 #pragma unroll
           for (int k = 0; k < BF_REAL_UNROLL; ++k) {
-            S const xv = xs[j];
+            E const xv = xs[j];
 #pragma unroll
-            for (int e = 0; e < EPL; ++e) acc[e] = fma(a8[k].v[e], xv, acc[e]);
+            for (int e = 0; e < EPL; ++e) acc[e] = bfMac(acc[e], a8[k].v[e], xv);
             j += g;
           }
         }
@@ -456,29 +499,29 @@ __device__ __forceinline__ void bfStageBodyReal(StageParams const &p, uint32_t c
 #pragma unroll
           for (int k = 0; k < BF_REAL_UNROLL - 1; ++k)
             if ((uint32_t)k < left) {
-              S const xv = xs[j];
+              E const xv = xs[j];
 #pragma unroll
-              for (int e = 0; e < EPL; ++e) acc[e] = fma(a8[k].v[e], xv, acc[e]);
+              for (int e = 0; e < EPL; ++e) acc[e] = bfMac(acc[e], a8[k].v[e], xv);
               j += g;
             }
         }
         uint32_t const rem = n - nfull * g;
         if (active && c < rem) {
           V a = bfLoadStreamV(ap + (uint64_t)nfull * G);
-          S xv = xs[j];
+          E xv = xs[j];
 #pragma unroll
-          for (int e = 0; e < EPL; ++e) acc[e] = fma(a.v[e], xv, acc[e]);
+          for (int e = 0; e < EPL; ++e) acc[e] = bfMac(acc[e], a.v[e], xv);
         }
       }
     }
     waveSync();
 #pragma unroll
-    for (int e = 0; e < EPL; ++e) xs[lane * EPL + e] = acc[e];   // index = c*mrPad + row for active lanes
+    for (int e = 0; e < EPL; ++e) xa[lane * EPL + e] = acc[e];   // index = c*mrPad + row for active lanes
     waveSync();
     for (uint32_t row = lane; row < mr; row += 64) {
-      S sum = 0;
-      for (uint32_t cc = 0; cc < g; ++cc) sum += xs[cc * mrPad + row];
-      out[((uint64_t)it.outOff + row) * nrhs + q] = sum;
+      EA sum{};
+      for (uint32_t cc = 0; cc < g; ++cc) sum += xa[cc * mrPad + row];
+      out[((uint64_t)it.outOff + row) * nrhs + q] = bfFromAcc(sum);
     }
   }
 }
@@ -550,7 +593,8 @@ template <int DT, int R, int NQ, bool COOP, bool ONE, typename CoopBuf>
 __device__ __forceinline__ void bfStageBodyT(StageParams const &p, uint32_t const bid, CoopBuf &coopBuf) {
   constexpr int C = 64 / R;                          // columns per load instruction
   using S = typename Traits<DT>::S;
-  constexpr int EPL = Traits<DT>::EPL;              // rows per 16-byte unit (complex: 1)
+  using A = typename Traits<DT>::A;                 // accumulator scalar (complex64: double)
+  constexpr int EPL = Traits<DT>::EPL;              // rows per 16-byte unit (complex128: 1)
   constexpr int NC = Traits<DT>::CPLX ? 2 : 1;      // scalars per element
   constexpr int UNIT = EPL * NC;                    // scalars per 16-byte unit
   struct __attribute__((aligned(16))) U { S v[UNIT]; };
@@ -580,14 +624,16 @@ __device__ __forceinline__ void bfStageBodyT(StageParams const &p, uint32_t cons
   uint32_t const cgRm = lane % CG_RM, rlRm = lane / CG_RM;
 
   for (uint32_t q = 0; q < nrhs; ++q) {
-    S acc[NQ][NC];
+    A acc[NQ][NC];
 #pragma unroll
     for (int cq = 0; cq < NQ; ++cq)
 #pragma unroll
       for (int k = 0; k < NC; ++k) acc[cq][k] = 0;
-    S racc[EPL];
+    A racc[EPL][NC];
 #pragma unroll
-    for (int e = 0; e < EPL; ++e) racc[e] = 0;
+    for (int e = 0; e < EPL; ++e)
+#pragma unroll
+      for (int k = 0; k < NC; ++k) racc[e][k] = 0;
     bool anyRowMajor = false;
     for (uint32_t wbase = 0; wbase < it.numPieces; wbase += 64) {
       uint32_t const wn = it.numPieces - wbase < 64 ? it.numPieces - wbase : 64;
@@ -602,11 +648,11 @@ __device__ __forceinline__ void bfStageBodyT(StageParams const &p, uint32_t cons
 #pragma unroll
             for (int cq = 0; cq < NQ; ++cq)
 #pragma unroll
-              for (int k = 0; k < NC; ++k) acc[cq][k] += xin[(uint64_t)jcol[cq] * nrhs * NC + k];
+              for (int k = 0; k < NC; ++k) acc[cq][k] += (A)xin[(uint64_t)jcol[cq] * nrhs * NC + k];
           }
           continue;
         }
-        if constexpr (!Traits<DT>::CPLX) {
+        if constexpr (EPL > 1) {                     // the real family's layout (f64, f32, complex64): row-major pieces exist
           if (pc.flags & BF_PIECE_ROWMAJOR) {
             // rows of a row-major forward piece (few-row leaves): element (row s, column j) = arena[dataOff + s * ld + j].
             // Lane = (column group cg of EPL consecutive columns, row lane rl): one 16-byte load per row, no reduction
@@ -627,16 +673,19 @@ __device__ __forceinline__ void bfStageBodyT(StageParams const &p, uint32_t cons
               dual = (pc2.flags & (BF_PIECE_ROWMAJOR | BF_PIECE_IDENTITY)) == BF_PIECE_ROWMAJOR;
             }
             U a[ITERS], a2[ITERS];
-            S xv[ITERS], xv2[ITERS];
+            S xv[ITERS][NC], xv2[ITERS][NC];
 #pragma unroll
             for (int i = 0; i < ITERS; ++i) {
               uint32_t const srow = rlRm + (uint32_t)i * RL_RM, sc = srow < n ? srow : n - 1;
               a[i] = bfLoadStreamV(src + (uint64_t)sc * rowUnits);
-              S const xr = xin[(uint64_t)sc * nrhs];
-              xv[i] = srow < n ? xr : (S)0;
+#pragma unroll
+              for (int k = 0; k < NC; ++k) {
+                S const xr = xin[(uint64_t)sc * nrhs * NC + k];
+                xv[i][k] = srow < n ? xr : (S)0;
+              }
             }
             if (dual) {                                             // wave-uniform
-              S const *xin2 = ((pc2.flags & BF_PIECE_IN_X) ? (S const *)p.x : (S const *)p.temp) + ((uint64_t)pc2.inOff * nrhs + q);
+              S const *xin2 = ((pc2.flags & BF_PIECE_IN_X) ? (S const *)p.x : (S const *)p.temp) + ((uint64_t)pc2.inOff * nrhs + q) * NC;
               uint32_t const n2 = pc2.ncols;
               U const *src2 = arena + pc2.dataOff / EPL + cgc;
               uint32_t const rowUnits2 = pc2.ld / EPL;
@@ -644,19 +693,22 @@ __device__ __forceinline__ void bfStageBodyT(StageParams const &p, uint32_t cons
               for (int i = 0; i < ITERS; ++i) {
                 uint32_t const srow = rlRm + (uint32_t)i * RL_RM, sc = srow < n2 ? srow : n2 - 1;
                 a2[i] = bfLoadStreamV(src2 + (uint64_t)sc * rowUnits2);
-                S const xr = xin2[(uint64_t)sc * nrhs];
-                xv2[i] = srow < n2 ? xr : (S)0;
+#pragma unroll
+                for (int k = 0; k < NC; ++k) {
+                  S const xr = xin2[(uint64_t)sc * nrhs * NC + k];
+                  xv2[i][k] = srow < n2 ? xr : (S)0;
+                }
               }
             }
 #pragma unroll
             for (int i = 0; i < ITERS; ++i)
 #pragma unroll
-              for (int e = 0; e < EPL; ++e) racc[e] = fma(a[i].v[e], xv[i], racc[e]);
+              for (int e = 0; e < EPL; ++e) bfMacN<NC>(racc[e], &a[i].v[e * NC], xv[i]);
             if (dual) {
 #pragma unroll
               for (int i = 0; i < ITERS; ++i)
 #pragma unroll
-                for (int e = 0; e < EPL; ++e) racc[e] = fma(a2[i].v[e], xv2[i], racc[e]);
+                for (int e = 0; e < EPL; ++e) bfMacN<NC>(racc[e], &a2[i].v[e * NC], xv2[i]);
               pi += pstep;                                          // the second piece is done
             }
             continue;
@@ -690,13 +742,8 @@ __device__ __forceinline__ void bfStageBodyT(StageParams const &p, uint32_t cons
 #pragma unroll
           for (int cq = 0; cq < NQ; ++cq) {
             if ((uint32_t)cq >= nq) continue;
-            if (Traits<DT>::CPLX) {
-              acc[cq][0] = fma(a[cq].v[0], xv[0], acc[cq][0]); acc[cq][0] = fma(-a[cq].v[1], xv[NC - 1], acc[cq][0]);
-              acc[cq][NC - 1] = fma(a[cq].v[0], xv[NC - 1], acc[cq][NC - 1]); acc[cq][NC - 1] = fma(a[cq].v[1], xv[0], acc[cq][NC - 1]);
-            } else {
 #pragma unroll
-              for (int e = 0; e < EPL; ++e) acc[cq][0] = fma(a[cq].v[e], xv[e], acc[cq][0]);
-            }
+            for (int e = 0; e < EPL; ++e) bfMacN<NC>(acc[cq], &a[cq].v[e * NC], &xv[e * NC]);
           }
         }
       }
@@ -708,21 +755,25 @@ __device__ __forceinline__ void bfStageBodyT(StageParams const &p, uint32_t cons
       for (int cq = 0; cq < NQ; ++cq)
 #pragma unroll
         for (int k = 0; k < NC; ++k) acc[cq][k] += __shfl_xor(acc[cq][k], m, R);
-    if constexpr (!Traits<DT>::CPLX) {
+    if constexpr (EPL > 1) {
       if (anyRowMajor) {      // wave-uniform: same pieces for every lane
 #pragma unroll
         for (int e = 0; e < EPL; ++e)
 #pragma unroll
-          for (int m = CG_RM; m < 64; m <<= 1) racc[e] += __shfl_xor(racc[e], m, 64);     // over the row lanes, fixed order
+          for (int k = 0; k < NC; ++k)
+#pragma unroll
+            for (int m = CG_RM; m < 64; m <<= 1) racc[e][k] += __shfl_xor(racc[e][k], m, 64);     // over the row lanes, fixed order
         // column col's total sits in lane col / EPL, element col % EPL: hand it to the lane that stores col
 #pragma unroll
         for (int cq = 0; cq < NQ; ++cq) {
           uint32_t const col = c4 + C * cq < mr ? c4 + C * cq : 0;
 #pragma unroll
-          for (int e = 0; e < EPL; ++e) {
-            S const t = __shfl(racc[e], (int)(col / EPL), 64);
-            if ((int)(col % EPL) == e) acc[cq][0] += t;
-          }
+          for (int e = 0; e < EPL; ++e)
+#pragma unroll
+            for (int k = 0; k < NC; ++k) {
+              A const t = __shfl(racc[e][k], (int)(col / EPL), 64);
+              if ((int)(col % EPL) == e) acc[cq][k] += t;
+            }
         }
       }
     }
@@ -739,7 +790,7 @@ __device__ __forceinline__ void bfStageBodyT(StageParams const &p, uint32_t cons
         for (int cq = 0; cq < NQ; ++cq)
 #pragma unroll
           for (int k = 0; k < NC; ++k) {
-            S t = coopBuf[0][c4 + C * cq][k];
+            A t = coopBuf[0][c4 + C * cq][k];
 #pragma unroll
             for (int w = 1; w < BF_WAVES_PER_WG; ++w) t += coopBuf[w][c4 + C * cq][k];
             acc[cq][k] = t;
@@ -753,16 +804,16 @@ __device__ __forceinline__ void bfStageBodyT(StageParams const &p, uint32_t cons
       for (int cq = 0; cq < NQ; ++cq)
         if (c4 + C * cq < mr)
 #pragma unroll
-          for (int k = 0; k < NC; ++k) out[(((uint64_t)it.outOff + c4 + C * cq) * nrhs + q) * NC + k] = acc[cq][k];
+          for (int k = 0; k < NC; ++k) out[(((uint64_t)it.outOff + c4 + C * cq) * nrhs + q) * NC + k] = (S)acc[cq][k];
     }
   }
 }
 
 template <int DT, int R, int NQ, bool COOP, bool ONE>
 __global__ __launch_bounds__(BF_WAVES_PER_WG * 64) void bfStageKernelT(StageParams p) {
-  using S = typename Traits<DT>::S;
+  using A = typename Traits<DT>::A;
   constexpr int NC = Traits<DT>::CPLX ? 2 : 1;
-  __shared__ S coopBuf[COOP ? BF_WAVES_PER_WG : 1][COOP ? NQ * (64 / R) : 1][NC];
+  __shared__ A coopBuf[COOP ? BF_WAVES_PER_WG : 1][COOP ? NQ * (64 / R) : 1][NC];
   bfStageBodyT<DT, R, NQ, COOP, ONE>(p, blockIdx.x, coopBuf);
 }
 
@@ -773,8 +824,9 @@ __global__ __launch_bounds__(BF_WAVES_PER_WG * 64) void bfStageKernelT(StagePara
 // lost by giving them one register allocation.
 template <int DT, bool ONE>
 __global__ __launch_bounds__(BF_WAVES_PER_WG * 64) void bfStageKernelTBoth(StageParams pn, StageParams pw, uint32_t gridNarrow) {
-  using S = typename Traits<DT>::S;
-  __shared__ S coopBuf[BF_WAVES_PER_WG][64][1];
+  using A = typename Traits<DT>::A;
+  constexpr int NC = Traits<DT>::CPLX ? 2 : 1;
+  __shared__ A coopBuf[BF_WAVES_PER_WG][64][NC];
   if (blockIdx.x < gridNarrow) bfStageBodyT<DT, 16, 4, true, ONE>(pn, blockIdx.x, coopBuf);
   else bfStageBodyT<DT, BF_T_WIDE_R, BF_T_WIDE_R, true, ONE>(pw, blockIdx.x - gridNarrow, coopBuf);
 }
@@ -801,6 +853,7 @@ struct ReduceBatch {
 
 template <typename T, int NC, bool LONG = false>   // NC = scalar components per element; LONG: some row has >= 64 partial sums
 __global__ __launch_bounds__(256) void bfReduceKernel(ReduceBatch const B) {
+  using TA = typename std::conditional<NC == 2 && sizeof(T) == 4, double, T>::type;   // complex64 partial sums add in double
   uint32_t k = 0;
   while (k + 1 < B.count && B.e[k + 1].blockBegin <= blockIdx.x) ++k;
   ReduceBatch::Entry const &E = B.e[k];
@@ -815,7 +868,7 @@ __global__ __launch_bounds__(256) void bfReduceKernel(ReduceBatch const B) {
   uint32_t b = E.ivBegin[iv], e = E.ivBegin[iv + 1];
   T const *temp = (T const *)B.temp;
   T *dest = (T *)E.dest;
-  T acc[NC];
+  TA acc[NC];
 #pragma unroll
   for (int c = 0; c < NC; ++c) acc[c] = 0;
   uint32_t s = b;
@@ -844,7 +897,7 @@ __global__ __launch_bounds__(256) void bfReduceKernel(ReduceBatch const B) {
     for (int c = 0; c < NC; ++c) acc[c] += src[c];
   }
 #pragma unroll
-  for (int c = 0; c < NC; ++c) dest[idx * NC + c] = acc[c];
+  for (int c = 0; c < NC; ++c) dest[idx * NC + c] = (T)acc[c];
 }
 
 // dst[perm ? perm[i] : i] = src[i] * (scale ? scale[i]^power : 1): the vector plumbing around the two applies of a
@@ -1099,6 +1152,32 @@ __global__ __launch_bounds__(BF_GM_THREADS) void bfGmresProjectKernel(double2 co
   }
 }
 
+// A forward stage of the real family (f64, f32, complex64).  Items [firstSmall, numItems) are small (BF_ITEM_SMALL): four to
+// a wavefront; with items of both kinds one launch runs both bodies, which write disjoint rows.
+template <int DT>
+static int bfLaunchRealStage(BfLaunchArgs const *a, StageParams p, hipStream_t s) {
+  uint64_t const firstSmall = a->firstSmall < a->numItems ? a->firstSmall : a->numItems;
+  uint64_t const numSmall = a->numItems - firstSmall;
+  p.numItems = (uint32_t)firstSmall;
+  uint32_t grid = (uint32_t)((firstSmall + BF_WAVES_PER_WG - 1) / BF_WAVES_PER_WG);
+  if (grid && numSmall) {
+    StageParams ps = p;
+    ps.items = (BfDevItem const *)a->items + firstSmall;
+    ps.numItems = (uint32_t)numSmall;
+    uint32_t const gridSmall = (uint32_t)((numSmall + 4 * BF_WAVES_PER_WG - 1) / (4 * BF_WAVES_PER_WG));
+    hipLaunchKernelGGL(bfStageKernelRealBoth<DT>, dim3(grid + gridSmall), dim3(BF_WAVES_PER_WG * 64), 0, s, p, ps, grid);
+    return hipFail(hipGetLastError(), "stage launch");
+  }
+  if (grid) hipLaunchKernelGGL(bfStageKernelReal<DT>, dim3(grid), dim3(BF_WAVES_PER_WG * 64), 0, s, p);
+  if (numSmall) {
+    p.items = (BfDevItem const *)a->items + firstSmall;
+    p.numItems = (uint32_t)numSmall;
+    grid = (uint32_t)((numSmall + 4 * BF_WAVES_PER_WG - 1) / (4 * BF_WAVES_PER_WG));
+    hipLaunchKernelGGL(bfStageKernelSmall<DT>, dim3(grid), dim3(BF_WAVES_PER_WG * 64), 0, s, p);
+  }
+  return hipFail(hipGetLastError(), "stage launch");
+}
+
 // ---------------------------------------------------------------------------
 // host-callable wrappers
 // ---------------------------------------------------------------------------
@@ -1153,6 +1232,7 @@ int bfdevSynthFill(void *arena, uint32_t dtype, BfSynthPiece const *hostPieces, 
       uint32_t n = (uint32_t)((count - done) > (1u << 23) ? (1u << 23) : (count - done));
       if (dtype == BFHIP_C128) hipLaunchKernelGGL(bfSynthKernel<BFHIP_C128>, dim3(n), dim3(256), 0, 0, arena, d + done, seed);
       else if (dtype == BFHIP_F64) hipLaunchKernelGGL(bfSynthKernel<BFHIP_F64>, dim3(n), dim3(256), 0, 0, arena, d + done, seed);
+      else if (dtype == BFHIP_C64) hipLaunchKernelGGL(bfSynthKernel<BFHIP_C64>, dim3(n), dim3(256), 0, 0, arena, d + done, seed);
       else hipLaunchKernelGGL(bfSynthKernel<BFHIP_F32>, dim3(n), dim3(256), 0, 0, arena, d + done, seed);
       rc = hipFail(hipGetLastError(), "synth fill launch");
       done += n;
@@ -1202,6 +1282,7 @@ int bfdevLaunchStage(BfLaunchArgs const *a, void *stream) {
                                  else hipLaunchKernelGGL((bfStageKernelTBoth<DT, false>), dim3(gridN + gridW), dim3(BF_WAVES_PER_WG * 64), 0, s, pn, pw, gridN); } while (0)
       if (a->dtype == BFHIP_F64) BF_LAUNCH_TBOTH(BFHIP_F64);
       else if (a->dtype == BFHIP_F32) BF_LAUNCH_TBOTH(BFHIP_F32);
+      else if (a->dtype == BFHIP_C64) BF_LAUNCH_TBOTH(BFHIP_C64);
       else return bfhipFail(BFABI_ERROR_TYPE_ERROR, "unknown dtype %u", a->dtype);
 #undef BF_LAUNCH_TBOTH
       return hipFail(hipGetLastError(), "transposed stage launch");
@@ -1225,6 +1306,7 @@ int bfdevLaunchStage(BfLaunchArgs const *a, void *stream) {
       if (a->dtype == BFHIP_C128) BF_LAUNCH_T(BFHIP_C128);
       else if (a->dtype == BFHIP_F64) BF_LAUNCH_T(BFHIP_F64);
       else if (a->dtype == BFHIP_F32) BF_LAUNCH_T(BFHIP_F32);
+      else if (a->dtype == BFHIP_C64) BF_LAUNCH_T(BFHIP_C64);
       else return bfhipFail(BFABI_ERROR_TYPE_ERROR, "unknown dtype %u", a->dtype);
 #undef BF_LAUNCH_T
 #undef BF_LAUNCH_T1
@@ -1252,34 +1334,9 @@ int bfdevLaunchStage(BfLaunchArgs const *a, void *stream) {
 #endif
     hipLaunchKernelGGL(bfStageKernelC128, dim3(grid), dim3(BF_C128_WG_WAVES * 64), 0, s, p);
   }
-  else if (a->dtype == BFHIP_F64 || a->dtype == BFHIP_F32) {
-    // items [firstSmall, numItems) are small (BF_ITEM_SMALL): their own launch, four to a wavefront; the two launches
-    // write disjoint rows
-    uint64_t const firstSmall = a->firstSmall < a->numItems ? a->firstSmall : a->numItems;
-    uint64_t const numSmall = a->numItems - firstSmall;
-    p.numItems = (uint32_t)firstSmall;
-    grid = (uint32_t)((firstSmall + BF_WAVES_PER_WG - 1) / BF_WAVES_PER_WG);
-    if (grid && numSmall) {
-      StageParams ps = p;
-      ps.items = (BfDevItem const *)a->items + firstSmall;
-      ps.numItems = (uint32_t)numSmall;
-      uint32_t const gridSmall = (uint32_t)((numSmall + 4 * BF_WAVES_PER_WG - 1) / (4 * BF_WAVES_PER_WG));
-      if (a->dtype == BFHIP_F64) hipLaunchKernelGGL(bfStageKernelRealBoth<BFHIP_F64>, dim3(grid + gridSmall), dim3(BF_WAVES_PER_WG * 64), 0, s, p, ps, grid);
-      else hipLaunchKernelGGL(bfStageKernelRealBoth<BFHIP_F32>, dim3(grid + gridSmall), dim3(BF_WAVES_PER_WG * 64), 0, s, p, ps, grid);
-      return hipFail(hipGetLastError(), "stage launch");
-    }
-    if (grid) {
-      if (a->dtype == BFHIP_F64) hipLaunchKernelGGL(bfStageKernelReal<BFHIP_F64>, dim3(grid), dim3(BF_WAVES_PER_WG * 64), 0, s, p);
-      else hipLaunchKernelGGL(bfStageKernelReal<BFHIP_F32>, dim3(grid), dim3(BF_WAVES_PER_WG * 64), 0, s, p);
-    }
-    if (numSmall) {
-      p.items = (BfDevItem const *)a->items + firstSmall;
-      p.numItems = (uint32_t)numSmall;
-      grid = (uint32_t)((numSmall + 4 * BF_WAVES_PER_WG - 1) / (4 * BF_WAVES_PER_WG));
-      if (a->dtype == BFHIP_F64) hipLaunchKernelGGL(bfStageKernelSmall<BFHIP_F64>, dim3(grid), dim3(BF_WAVES_PER_WG * 64), 0, s, p);
-      else hipLaunchKernelGGL(bfStageKernelSmall<BFHIP_F32>, dim3(grid), dim3(BF_WAVES_PER_WG * 64), 0, s, p);
-    }
-  }
+  else if (a->dtype == BFHIP_F64) return bfLaunchRealStage<BFHIP_F64>(a, p, s);
+  else if (a->dtype == BFHIP_F32) return bfLaunchRealStage<BFHIP_F32>(a, p, s);
+  else if (a->dtype == BFHIP_C64) return bfLaunchRealStage<BFHIP_C64>(a, p, s);
   else return bfhipFail(BFABI_ERROR_TYPE_ERROR, "unknown dtype %u", a->dtype);
   return hipFail(hipGetLastError(), "stage launch");
 }
@@ -1316,6 +1373,8 @@ int bfdevLaunchReduce(BfReduceArgs const *a, uint32_t count, void *stream) {
     bool longLists = false;
     for (uint32_t k = 0; k < B.count; ++k) longLists = longLists || a[base + k].longLists;
     if (dtype == BFHIP_C128) hipLaunchKernelGGL((bfReduceKernel<double, 2>), dim3(blocks), dim3(256), 0, s, B);
+    else if (dtype == BFHIP_C64 && longLists) hipLaunchKernelGGL((bfReduceKernel<float, 2, true>), dim3(blocks), dim3(256), 0, s, B);
+    else if (dtype == BFHIP_C64) hipLaunchKernelGGL((bfReduceKernel<float, 2>), dim3(blocks), dim3(256), 0, s, B);
     else if (dtype == BFHIP_F64 && longLists) hipLaunchKernelGGL((bfReduceKernel<double, 1, true>), dim3(blocks), dim3(256), 0, s, B);
     else if (dtype == BFHIP_F64) hipLaunchKernelGGL((bfReduceKernel<double, 1>), dim3(blocks), dim3(256), 0, s, B);
     else if (longLists) hipLaunchKernelGGL((bfReduceKernel<float, 1, true>), dim3(blocks), dim3(256), 0, s, B);

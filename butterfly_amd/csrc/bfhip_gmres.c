@@ -79,6 +79,7 @@ int bfhipSolveGMRESOptsDevice(BfhipOperator *op, BfhipGmresOptions const *opt, v
   st.structSize = sizeof st;
   int rc = bfhipGetStats(op, &st);
   if (rc) return rc;
+  if (st.dtype == BFHIP_C64) return bfhipFail(BFABI_ERROR_NOT_IMPLEMENTED, "GMRES is not implemented for complex64 operators");
   if (st.dtype != BFHIP_C128) return bfhipFail(BFABI_ERROR_NOT_IMPLEMENTED, "GMRES is implemented for complex operators");
   if (st.numRows != st.numCols) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "GMRES needs a square operator (linalg.c:85-87)");
   int const dev = bfhipOperatorDevice(op);
@@ -108,6 +109,7 @@ int bfGmresSolve(BfGmresApplyFn apply, void *ctx, uint64_t n, int device, BfhipG
     ms.structSize = sizeof ms;
     int rcs = bfhipGetStats(solveM, &ms);
     if (rcs) return rcs;
+    if (ms.dtype == BFHIP_C64) return bfhipFail(BFABI_ERROR_NOT_IMPLEMENTED, "a complex64 preconditioner is not implemented");
     if (ms.dtype != BFHIP_C128) return bfhipFail(BFABI_ERROR_TYPE_ERROR, "the preconditioner must be a complex128 operator like the system it preconditions");
   }
   int prev = -1, dev = device;

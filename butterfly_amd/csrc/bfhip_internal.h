@@ -18,6 +18,12 @@ extern "C" {
  * ---------------------------------------------------------------------- */
 int bfhipFail(int code, char const *fmt, ...);   /* records message, returns code */
 
+/* element types: complex (C128, C64) vs real; the complex128 layout (one element per 16-byte lane load, its own kernels and
+ * plan shapes) vs the real family's (C64 is 8 bytes like F64 and gets exactly the F64 plan) */
+static inline int bfDtypeComplex(uint32_t dt) { return dt == BFHIP_C128 || dt == BFHIP_C64; }
+static inline int bfDtypeC128Layout(uint32_t dt) { return dt == BFHIP_C128; }
+static inline uint32_t bfDtypeElemSize(uint32_t dt) { return dt == BFHIP_C128 ? 16u : (dt == BFHIP_F64 || dt == BFHIP_C64) ? 8u : 4u; }
+
 /* ------------------------------------------------------------------------
  * IR: owned copy of a BfhipDesc (or of a walked BfMat graph)
  * ---------------------------------------------------------------------- */
@@ -151,7 +157,7 @@ typedef struct BfStage {
 } BfStage;
 
 typedef struct BfPlan {
-  uint32_t dtype;            /* storage/compute type: BFHIP_C128 / F64 / F32 */
+  uint32_t dtype;            /* storage/compute type: BFHIP_C128 / F64 / F32 / C64 */
   uint32_t elemSize;         /* bytes per element */
   uint32_t epl;              /* elements per 16-byte lane load */
   uint32_t maxItemRows;      /* 64 * epl */

@@ -639,6 +639,7 @@ int bfhipFacHelm2MakeMultilevel2(double const *points, double const *normals, do
   if (!points || !params || !out) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL argument");
   *out = NULL;
   if (params->structSize < sizeof *params) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "BfhipHelm2Problem.structSize too small");
+  if (opts && opts->demoteToF32) return bfhipFail(BFABI_ERROR_NOT_IMPLEMENTED, "the Helmholtz builder has no complex64 output (demoteToF32)");
   BfhipHelm2Layout *L = NULL;
   int rc = bfhipHelm2LayoutCreate2(points, numPoints, tgtPoints, tgtPoints ? numTgtPoints : 0, params->wavenumber, &L);
   if (rc) return rc;

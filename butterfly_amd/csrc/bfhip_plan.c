@@ -679,7 +679,7 @@ int bfPlanBuild(BfIr const *ir, BfPlanOptions const *po, BfPlan *plan) {
   int rc = 0;
 
   plan->dtype = po->storeDtype;
-  plan->elemSize = plan->dtype == BFHIP_C128 ? 16 : (plan->dtype == BFHIP_F64 ? 8 : 4);
+  plan->elemSize = bfDtypeElemSize(plan->dtype);
   plan->epl = 16 / plan->elemSize;
   plan->maxItemRows = 64 * plan->epl;
   int const T = po->fwdPieces != NULL;
@@ -960,7 +960,7 @@ int bfPlanBuild(BfIr const *ir, BfPlanOptions const *po, BfPlan *plan) {
             uint64_t lo = 0, hi = nbp;
             while (lo < hi) { uint64_t mid = (lo + hi) / 2; if (bp[mid] < groups[g].outOff) lo = mid + 1; else hi = mid; }
             uint64_t endRow = groups[g].outOff + groups[g].rows;
-            int alone = plan->dtype != BFHIP_C128;
+            int alone = !bfDtypeC128Layout(plan->dtype);
             for (uint64_t i = lo; alone && i < niv && bp[i] < endRow; ++i) alone = rd->ivBegin[i + 1] == 1;
             if (alone) {
               for (uint64_t i = lo; i < niv && bp[i] < endRow; ++i) { skip[i] = 1; rd->ivBegin[i + 1] = 0; --nsrc; }
@@ -1011,7 +1011,7 @@ int bfPlanBuild(BfIr const *ir, BfPlanOptions const *po, BfPlan *plan) {
 #ifndef BF_PLAN_BUNDLE_ORDER
 #define BF_PLAN_BUNDLE_ORDER 1     /* 1 = runs of equal inputs kept together (product); A/B builds: 0 = items by cost bucket and first input (round 4), 2 = full bundles first, leftovers after (for -DBF_MF_BUNDLES=1 kernels) */
 #endif
-    int const bundled = BF_PLAN_BUNDLE_ORDER && po->groupByInput && !T && plan->dtype == BFHIP_C128;
+    int const bundled = BF_PLAN_BUNDLE_ORDER && po->groupByInput && !T && bfDtypeC128Layout(plan->dtype);
     for (uint64_t g = 0; g < numGroups; ++g) {
       Group *gr = &groups[g];
       gr->colsSum = 0; gr->piecesPerChunk = 0;
@@ -1071,7 +1071,7 @@ int bfPlanBuild(BfIr const *ir, BfPlanOptions const *po, BfPlan *plan) {
           }
         }
         /* colsSum < 128 also means "not row-major" */
-        tmp[ni].small = !T && plan->dtype != BFHIP_C128 && rows <= 2 * plan->epl && colsSum < BF_SMALL_COLS && piecesPerChunk <= BF_SMALL_PIECES;
+        tmp[ni].small = !T && !bfDtypeC128Layout(plan->dtype) && rows <= 2 * plan->epl && colsSum < BF_SMALL_COLS && piecesPerChunk <= BF_SMALL_PIECES;
         tmp[ni].narrow = groups[g].cls;
         ++ni;
         numPieces += piecesPerChunk;
@@ -1140,7 +1140,7 @@ int bfPlanBuild(BfIr const *ir, BfPlanOptions const *po, BfPlan *plan) {
       /* (not a chunk made of hundreds of pieces a few columns wide -- the transposes of few-row leaves in a packed adjoint plan:
        * row-major each piece is a dependent step that keeps two lanes busy; column-major the kernel contracts runs of them as
        * one block) */
-      int const rowMajor = !T && plan->dtype != BFHIP_C128 && mr <= 2 * plan->epl &&
+      int const rowMajor = !T && !bfDtypeC128Layout(plan->dtype) && mr <= 2 * plan->epl &&
                            (tmp[i].small || (g->colsSum >= 128 && g->colsSum >= 16 * g->piecesPerChunk));
       if (rowMajor) flags |= BF_ITEM_ROWMAJOR;
       if (g->reduced) outOff = g->slotOff + r0;
@@ -1236,7 +1236,7 @@ int bfPlanBuild(BfIr const *ir, BfPlanOptions const *po, BfPlan *plan) {
       it->numPieces = (uint32_t)(np - it->pieceBegin);
       /* the pieces of an item are packed back to back: when they are few and narrow the kernel takes them as one
        * block (one LDS hand-off and one dependent load chain per item instead of one per piece) */
-      if (!T && !rowMajor && plan->dtype != BFHIP_C128 && it->numPieces <= 64) {
+      if (!T && !rowMajor && !bfDtypeC128Layout(plan->dtype) && it->numPieces <= 64) {
         uint64_t dense = 0;
         for (uint32_t k = 0; k < it->numPieces; ++k)
           if (!(st->pieces[it->pieceBegin + k].flags & BF_PIECE_IDENTITY)) dense += st->pieces[it->pieceBegin + k].ncols;
@@ -1261,7 +1261,7 @@ int bfPlanBuild(BfIr const *ir, BfPlanOptions const *po, BfPlan *plan) {
     }
     st->numItems = totalItems;
     st->numPieces = np;
-    if (!T && plan->dtype == BFHIP_C128 && totalItems && (rc = bfPlanBundles(st->items, st->pieces, totalItems, &st->bundleBegin, &st->numBundles))) { free(tmp); goto stage_fail; }
+    if (!T && bfDtypeC128Layout(plan->dtype) && totalItems && (rc = bfPlanBundles(st->items, st->pieces, totalItems, &st->bundleBegin, &st->numBundles))) { free(tmp); goto stage_fail; }
     st->numCoopNarrow = T ? bfPlanCountCoop(st->items, st->pieces, st->numNarrow, plan->elemSize) : 0;
     st->numCoop = T ? bfPlanCountCoop(st->items + st->numNarrow, st->pieces, numItems - st->numNarrow, plan->elemSize) : 0;
     /* algorithmic counts */

@@ -208,7 +208,7 @@ int bfhipShardedCreate(BfhipOperator *op, BfhipComm *comm, BfhipShardSpec const 
   BfhipSharded *s = (BfhipSharded *)calloc(1, sizeof *s);
   if (!s) return bfhipFail(BFABI_ERROR_MEMORY_ERROR, "host OOM");
   s->op = op; s->comm = comm; s->device = comm->device; s->mode = spec->mode; s->dtype = st.dtype;
-  s->elemSize = st.dtype == BFHIP_C128 ? 16 : st.dtype == BFHIP_F64 ? 8 : 4;
+  s->elemSize = bfDtypeElemSize(st.dtype);
   s->maxRhs = maxRhs ? maxRhs : 1;
   s->numRowsGlobal = spec->numRowsGlobal;
   int prev = -1;
@@ -323,7 +323,7 @@ int bfhipShardedCreate(BfhipOperator *op, BfhipComm *comm, BfhipShardSpec const 
   }
   {
     uint64_t const big = s->numRowsGlobal > s->numCols ? s->numRowsGlobal : s->numCols;
-    if (!rc && s->hasAdjoint && s->dtype != BFHIP_C128) rc = hipFailS(hipMalloc(&s->dCov, 2 * (size_t)big * s->elemSize + 32), "hipMalloc(covariance scratch)");
+    if (!rc && s->hasAdjoint && !bfDtypeComplex(s->dtype)) rc = hipFailS(hipMalloc(&s->dCov, 2 * (size_t)big * s->elemSize + 32), "hipMalloc(covariance scratch)");
     if (!rc) rc = hipFailS(hipMalloc(&s->dHostX, (size_t)big * s->maxRhs * s->elemSize + 16), "hipMalloc(host staging)");
     if (!rc) rc = hipFailS(hipMalloc(&s->dHostY, (size_t)big * s->maxRhs * s->elemSize + 16), "hipMalloc(host staging)");
   }
@@ -349,8 +349,8 @@ int bfhipShardedApplyDevice(BfhipSharded *s, void const *dX, size_t nrhs, void *
   (void)hipGetDevice(&prev);
   int rc = prev != s->device ? hipFailS(hipSetDevice(s->device), "hipSetDevice") : 0;
   if (rc) return rc;
-  ncclDataType_t const dt = s->dtype == BFHIP_F32 ? ncclFloat32 : ncclFloat64;
-  size_t const scalarsPerElem = s->dtype == BFHIP_C128 ? 2 : 1;
+  ncclDataType_t const dt = (s->dtype == BFHIP_F32 || s->dtype == BFHIP_C64) ? ncclFloat32 : ncclFloat64;
+  size_t const scalarsPerElem = bfDtypeComplex(s->dtype) ? 2 : 1;
   if (s->timing) (void)hipEventRecord(s->e0, stream);
   if (s->mode == BFHIP_SHARD_BLOCKS) {
     rc = bfhipApplyDevice(s->op, dX, nrhs, dY, stream);
@@ -371,7 +371,7 @@ int bfhipShardedApplyDevice(BfhipSharded *s, void const *dX, size_t nrhs, void *
       uint64_t const total = s->numRowsGlobal * scalarsPerRow;
       uint32_t const grid = (uint32_t)((total + 255) / 256);
       if (grid) {
-        if (s->dtype == BFHIP_F32) hipLaunchKernelGGL(bfSumSegmentsKernel<float>, dim3(grid), dim3(256), 0, stream, s->dGroups, s->numGroups, s->dSrcOff, s->numRowsGlobal, (float const *)s->dGather, (float *)dY, scalarsPerRow);
+        if (s->dtype == BFHIP_F32 || s->dtype == BFHIP_C64) hipLaunchKernelGGL(bfSumSegmentsKernel<float>, dim3(grid), dim3(256), 0, stream, s->dGroups, s->numGroups, s->dSrcOff, s->numRowsGlobal, (float const *)s->dGather, (float *)dY, scalarsPerRow);
         else hipLaunchKernelGGL(bfSumSegmentsKernel<double>, dim3(grid), dim3(256), 0, stream, s->dGroups, s->numGroups, s->dSrcOff, s->numRowsGlobal, (double const *)s->dGather, (double *)dY, scalarsPerRow);
         rc = hipFailS(hipGetLastError(), "segment sum launch");
       }
@@ -415,8 +415,8 @@ int bfhipShardedApplyTransposeDevice(BfhipSharded *s, void const *dV, size_t nrh
   (void)hipGetDevice(&prev);
   int rc = prev != s->device ? hipFailS(hipSetDevice(s->device), "hipSetDevice") : 0;
   if (rc) return rc;
-  ncclDataType_t const dt = s->dtype == BFHIP_F32 ? ncclFloat32 : ncclFloat64;
-  size_t const scalarsPerElem = s->dtype == BFHIP_C128 ? 2 : 1;
+  ncclDataType_t const dt = (s->dtype == BFHIP_F32 || s->dtype == BFHIP_C64) ? ncclFloat32 : ncclFloat64;
+  size_t const scalarsPerElem = bfDtypeComplex(s->dtype) ? 2 : 1;
   size_t const rowBytes = nrhs * s->elemSize;
   void const *vr = dV;                                   // blocks mode: the local operator has all rows
   if (s->mode == BFHIP_SHARD_ROWS) {
@@ -447,7 +447,7 @@ int bfhipShardedApplyTransposeDevice(BfhipSharded *s, void const *dV, size_t nrh
 
 int bfhipShardedCovMatvecDevice(BfhipSharded *s, void const *dGammaLam, uint64_t const *dRowPerm, uint64_t const *dRevRowPerm, void const *dV, void *dZ, void *stream) {
   if (!s || !dV || !dZ) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL argument");
-  if (s->dtype == BFHIP_C128) return bfhipFail(BFABI_ERROR_TYPE_ERROR, "covariance products are defined for real operators");
+  if (bfDtypeComplex(s->dtype)) return bfhipFail(BFABI_ERROR_TYPE_ERROR, "covariance products are defined for real operators (not complex128 / complex64)");
   if (!s->hasAdjoint || !s->dCov) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "the sharded operator was not compiled with BFHIP_FLAG_ADJOINT");
   int prev = -1;
   (void)hipGetDevice(&prev);
@@ -470,6 +470,7 @@ static int shardedMatvec(void *ctx, void const *dX, size_t nrhs, void *dY, void 
 int bfhipShardedSolveGMRESDevice(BfhipSharded *s, BfhipGmresOptions const *opt, void const *dB, size_t nrhs, void const *dX0,
                                  size_t *numIter, double *residual, void *dX, void *stream) {
   if (!s) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL sharded operator");
+  if (s->dtype == BFHIP_C64) return bfhipFail(BFABI_ERROR_NOT_IMPLEMENTED, "GMRES is not implemented for complex64 operators");
   if (s->dtype != BFHIP_C128) return bfhipFail(BFABI_ERROR_NOT_IMPLEMENTED, "GMRES is implemented for complex operators");
   if (s->numRowsGlobal != s->numCols) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "GMRES needs a square operator (linalg.c:85-87)");
   if (!nrhs || nrhs > s->maxRhs) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "nrhs %zu exceeds the %u this sharded apply was created for", nrhs, s->maxRhs);
@@ -493,17 +494,18 @@ int bfhipShardedApplyHost(BfhipSharded *s, int transpose, void const *X, size_t 
   int rc = prev != s->device ? hipFailS(hipSetDevice(s->device), "hipSetDevice") : 0;
   if (rc) return rc;
   uint64_t const n = transpose ? s->numRowsGlobal : s->numCols, m = transpose ? s->numCols : s->numRowsGlobal;
-  size_t const es = s->elemSize, hostEs = s->dtype == BFHIP_C128 ? 16 : 8;
+  size_t const es = s->elemSize, hostEs = bfDtypeComplex(s->dtype) ? 16 : 8;
+  size_t const nc = bfDtypeComplex(s->dtype) ? 2 : 1;     // scalars per element (the fp32 / complex64 conversions)
   void *hx = malloc((n * nrhs ? n * nrhs : 1) * es), *hy = malloc((m * nrhs ? m * nrhs : 1) * es);
   if (!hx || !hy) { free(hx); free(hy); if (prev >= 0 && prev != s->device) (void)hipSetDevice(prev); return bfhipFail(BFABI_ERROR_MEMORY_ERROR, "host OOM"); }
   if (es == hostEs) for (uint64_t i = 0; i < n; ++i) memcpy((char *)hx + i * nrhs * es, (char const *)X + i * ldx * es, nrhs * es);
-  else for (uint64_t i = 0; i < n; ++i) for (size_t q = 0; q < nrhs; ++q) ((float *)hx)[i * nrhs + q] = (float)((double const *)X)[i * ldx + q];
+  else for (uint64_t i = 0; i < n; ++i) for (size_t q = 0; q < nrhs * nc; ++q) ((float *)hx)[i * nrhs * nc + q] = (float)((double const *)X)[i * ldx * nc + q];
   rc = hipFailS(hipMemcpy(s->dHostX, hx, n * nrhs * es, hipMemcpyHostToDevice), "hipMemcpy H2D");
   if (!rc) rc = transpose ? bfhipShardedApplyTransposeDevice(s, s->dHostX, nrhs, s->dHostY, NULL) : bfhipShardedApplyDevice(s, s->dHostX, nrhs, s->dHostY, NULL);
   if (!rc) rc = hipFailS(hipMemcpy(hy, s->dHostY, m * nrhs * es, hipMemcpyDeviceToHost), "hipMemcpy D2H");
   if (!rc) {
     if (es == hostEs) for (uint64_t i = 0; i < m; ++i) memcpy((char *)Y + i * ldy * es, (char *)hy + i * nrhs * es, nrhs * es);
-    else for (uint64_t i = 0; i < m; ++i) for (size_t q = 0; q < nrhs; ++q) ((double *)Y)[i * ldy + q] = ((float *)hy)[i * nrhs + q];
+    else for (uint64_t i = 0; i < m; ++i) for (size_t q = 0; q < nrhs * nc; ++q) ((double *)Y)[i * ldy * nc + q] = ((float *)hy)[i * nrhs * nc + q];
   }
   free(hx); free(hy);
   if (prev >= 0 && prev != s->device) (void)hipSetDevice(prev);

@@ -15,7 +15,7 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from ._capi import BFHIP_C128, BFHIP_F32, BFHIP_F64, BfhipOptions, BfhipStats, DescArrays, check
+from ._capi import BFHIP_C64, BFHIP_C128, BFHIP_F32, BFHIP_F64, BfhipOptions, BfhipStats, DescArrays, check
 
 
 def _options(device=-1, flags=0, max_rhs=1, demote_to_f32=False, seed=0, row_blocks=None, row_range=None):
@@ -160,13 +160,21 @@ class HipOperator:
         return self.stats()["dtype"]
 
     def np_dtype(self):
-        return {BFHIP_C128: np.complex128, BFHIP_F64: np.float64, BFHIP_F32: np.float32}[self.dtype]
+        return {BFHIP_C128: np.complex128, BFHIP_F64: np.float64, BFHIP_F32: np.float32, BFHIP_C64: np.complex64}[self.dtype]
+
+    def _host_dtype(self):
+        # the host entries take double precision whatever the operator stores (fp32 / complex64 are demoted on upload)
+        return np.complex128 if self.dtype in (BFHIP_C128, BFHIP_C64) else np.float64
+
+    def _torch_dtype(self):
+        import torch
+        return {BFHIP_C128: torch.complex128, BFHIP_F64: torch.float64, BFHIP_F32: torch.float32, BFHIP_C64: torch.complex64}[self.dtype]
 
     # ---- apply -------------------------------------------------------------
     def apply_host(self, x: np.ndarray) -> np.ndarray:
         """bfhipApply on host arrays (H2D, all stages, D2H)."""
         m, n = self.shape
-        src_dtype = np.complex128 if self.dtype == BFHIP_C128 else np.float64
+        src_dtype = self._host_dtype()
         x2 = np.ascontiguousarray(x, dtype=src_dtype)
         one_d = x2.ndim == 1
         if one_d:
@@ -201,7 +209,7 @@ class HipOperator:
         current torch stream unless `stream` is given)."""
         import torch
         m, n = self.shape
-        tdt = {BFHIP_C128: torch.complex128, BFHIP_F64: torch.float64, BFHIP_F32: torch.float32}[self.dtype]
+        tdt = self._torch_dtype()
         if x.dtype != tdt or not x.is_cuda or not x.is_contiguous():
             raise ValueError(f"x must be a contiguous CUDA tensor of dtype {tdt}")
         nrhs = 1 if x.dim() == 1 else x.shape[1]
@@ -218,7 +226,7 @@ class HipOperator:
         """bfhipApplyTranspose: y = A^T x (plain transpose) on host arrays; the
         operator must have been compiled with FLAG_ADJOINT."""
         m, n = self.shape
-        src_dtype = np.complex128 if self.dtype == BFHIP_C128 else np.float64
+        src_dtype = self._host_dtype()
         x2 = np.ascontiguousarray(x, dtype=src_dtype)
         one_d = x2.ndim == 1
         if one_d:
@@ -233,6 +241,8 @@ class HipOperator:
     def apply_transpose_device(self, x, y=None, stream=None):
         import torch
         m, n = self.shape
+        if self.dtype == BFHIP_C64 and x.dtype != torch.complex64:
+            raise ValueError(f"a complex64 operator takes complex64 tensors, not {x.dtype}")
         nrhs = 1 if x.dim() == 1 else x.shape[1]
         if y is None:
             y = torch.empty((n,) if x.dim() == 1 else (n, nrhs), dtype=x.dtype, device=x.device)

@@ -40,7 +40,8 @@ typedef struct BfhipOperator BfhipOperator;
 enum {
   BFHIP_C128 = 0,  /* double _Complex: fac_helm2 operands (BfMatDenseComplex) */
   BFHIP_F64 = 1,   /* double: fac_streamer operands (BfMatDenseReal)          */
-  BFHIP_F32 = 2    /* float: build extension -- real leaves demoted on upload */
+  BFHIP_F32 = 2,   /* float: build extension -- real leaves demoted on upload */
+  BFHIP_C64 = 3    /* float _Complex: build extension -- complex leaves demoted on upload (the real family's plan, complex MACs in double) */
 };
 
 /* node kinds of the flat expression descriptor */
@@ -103,7 +104,10 @@ typedef struct BfhipOptions {
   int32_t device;           /* HIP ordinal; -1 = current device */
   uint32_t flags;           /* BFHIP_FLAG_* */
   uint32_t maxRhs;          /* intermediates preallocated for this many RHS (0 -> 1); grows on demand */
-  uint32_t demoteToF32;     /* 1: store/compute BFHIP_F64 operands in fp32 (config 5 extension) */
+  uint32_t demoteToF32;     /* 1: store/compute BFHIP_F64 operands in fp32 and BFHIP_C128 operands in complex64 (BFHIP_C64; config 5
+                             * extension).  A complex64 operator's bfhipApplyDevice / bfhipApplyTransposeDevice take complex64 device
+                             * vectors (interleaved float re / im); its host entries (bfhipApply, the vtable shim) keep taking complex128.
+                             * GMRES, covariance products and the Helmholtz builders refuse complex64 (NOT_IMPLEMENTED / TYPE_ERROR). */
   uint32_t reserved0;
   uint64_t seed;            /* value seed for synthetic (data == NULL) leaves */
   /* row sharding: keep only block rows
