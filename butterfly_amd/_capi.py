@@ -17,6 +17,13 @@ FLAG_ADJOINT = 4
 FLAG_FLOW = 8
 FLAG_ADJOINT_PACKED = 16
 FLAG_EXACT_COMPLEX = 32
+KERNEL_COUNT = 61          # BFHIP_KERNEL_COUNT (include/bfhip.h): kernel ids of the apply path
+
+
+def kernel_name(kernel_id):
+    """bfhipKernelName: the kernel instantiation behind a BfhipKernelId."""
+    n = load().bfhipKernelName(int(kernel_id))
+    return None if n is None else n.decode()
 
 ERROR_NAMES = {0: "BF_ERROR_NONE", 1: "BF_ERROR_INVALID_ARGUMENTS", 2: "BF_ERROR_RUNTIME_ERROR",
                3: "BF_ERROR_NOT_IMPLEMENTED", 4: "BF_ERROR_MEMORY_ERROR", 5: "BF_ERROR_OUT_OF_RANGE",
@@ -400,6 +407,10 @@ def load():
     lib.bfhipPlanGetStage.restype = C.c_int
     lib.bfhipPlanGetReduce.argtypes = [vp, C.c_uint64, C.c_uint64, C.POINTER(BfhipReduceView)]
     lib.bfhipPlanGetReduce.restype = C.c_int
+    lib.bfhipKernelName.argtypes = [C.c_uint32]
+    lib.bfhipKernelName.restype = C.c_char_p
+    lib.bfhipPlanStageKernels.argtypes = [vp, C.c_uint64, C.c_uint32, vp, C.c_uint32, C.POINTER(C.c_uint32)]
+    lib.bfhipPlanStageKernels.restype = C.c_int
     lib.bfhipPlanPackArena.argtypes = [vp, vp]
     lib.bfhipPlanPackArena.restype = C.c_int
     lib.bfhipPlanPackArenaT.argtypes = [vp, vp]

@@ -720,6 +720,16 @@ int bfhipSetProfileSampling(BfhipOperator *op, uint32_t every) {
 }
 
 /* ---- apply ------------------------------------------------------------------ */
+/* what bfdevLaunchStage gets for stage `st` of `plan` (x and y left NULL) */
+static void stageLaunchArgs(BfhipOperator const *op, BfPlan const *plan, BfStage const *st, uint32_t nrhs, BfLaunchArgs *a) {
+  a->arena = (plan == &op->tplan && op->dArenaT) ? op->dArenaT : op->dArena; a->items = st->dItems; a->pieces = st->dPieces; a->numItems = st->numItems; a->firstSmall = st->firstSmall; a->numCoop = st->numCoop; a->numNarrow = st->numNarrow; a->numCoopNarrow = st->numCoopNarrow; a->maxRowsRest = st->maxRowsRest;
+  a->x = NULL; a->y = NULL; a->temp = op->dTemp; a->zero = op->dZero; a->nrhs = nrhs; a->dtype = plan->dtype; a->maxRows = st->maxRows;
+  a->transposed = plan->transposed;
+  a->tickets = NULL;
+  a->exactComplex = (op->flags & BFHIP_FLAG_EXACT_COMPLEX) != 0; a->pad2 = 0;
+  a->bundles = st->dBundleBegin; a->numBundles = st->numBundles;
+}
+
 static int runPlan(BfhipOperator *op, BfPlan *plan, void const *dX, size_t nrhs, void *dY, void *stream) {
   if (!op || !dX || !dY) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL argument");
   if (nrhs == 0 || nrhs > 0xffffu) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "nrhs out of range");
@@ -792,12 +802,8 @@ static int runPlan(BfhipOperator *op, BfPlan *plan, void const *dX, size_t nrhs,
   for (uint64_t s = 0; s < plan->numStages; ++s) {
     BfStage *st = &plan->stages[s];
     BfLaunchArgs a;
-    a.arena = (plan == &op->tplan && op->dArenaT) ? op->dArenaT : op->dArena; a.items = st->dItems; a.pieces = st->dPieces; a.numItems = st->numItems; a.firstSmall = st->firstSmall; a.numCoop = st->numCoop; a.numNarrow = st->numNarrow; a.numCoopNarrow = st->numCoopNarrow; a.maxRowsRest = st->maxRowsRest;
-    a.x = dX; a.y = dY; a.temp = op->dTemp; a.zero = op->dZero; a.nrhs = (uint32_t)nrhs; a.dtype = plan->dtype; a.maxRows = st->maxRows;
-    a.transposed = plan->transposed;
-    a.tickets = NULL;
-    a.exactComplex = (op->flags & BFHIP_FLAG_EXACT_COMPLEX) != 0; a.pad2 = 0;
-    a.bundles = st->dBundleBegin; a.numBundles = st->numBundles;
+    stageLaunchArgs(op, plan, st, (uint32_t)nrhs, &a);
+    a.x = dX; a.y = dY;
     if (plan->dtype == BFHIP_C128 && !plan->transposed && nrhs < 2) a.tickets = st->dTickets;      /* NULL unless this is an EXPERIMENTAL build run with BFHIP_PERSISTENT=1 (allocated at compile time) */
     if (prof && (rc = bfdevEventRecord(op->evStart[evBase + s], stream))) goto out;
     if ((rc = bfdevLaunchStage(&a, stream))) goto out;
@@ -1085,6 +1091,57 @@ int bfhipPlanGetStage(BfhipOperator const *op, uint64_t stage, BfhipStageView *v
   v->numItems = st->numItems; v->numPieces = st->numPieces; v->numReduce = st->numReduce;
   v->items = st->items; v->pieces = st->pieces;
   if (v->structSize >= sizeof *v) { v->numBundles = st->numBundles; v->bundleBegin = st->bundleBegin; }
+  return 0;
+}
+static char const *const kernelNames[BFHIP_KERNEL_COUNT] = {
+  "bfStageKernelC128", "bfStageKernelC128Mfma1", "bfStageKernelC128Mfma2", "bfStageKernelC128Mfma",
+  "bfStageKernelC128Mfma1Exact", "bfStageKernelC128Mfma2Exact", "bfStageKernelC128MfmaExact",
+  "bfStageKernelReal<F64>", "bfStageKernelReal<F32>", "bfStageKernelReal<C64>",
+  "bfStageKernelRealBoth<F64>", "bfStageKernelRealBoth<F32>", "bfStageKernelRealBoth<C64>",
+  "bfStageKernelSmall<F64>", "bfStageKernelSmall<F32>", "bfStageKernelSmall<C64>",
+#define BF_T_NAMES(DT) "bfStageKernelT<" DT ", narrow, nrhs>1>", "bfStageKernelT<" DT ", narrow, nrhs=1>", \
+                       "bfStageKernelT<" DT ", narrow, coop, nrhs>1>", "bfStageKernelT<" DT ", narrow, coop, nrhs=1>", \
+                       "bfStageKernelT<" DT ", wide, nrhs>1>", "bfStageKernelT<" DT ", wide, nrhs=1>", \
+                       "bfStageKernelT<" DT ", wide, coop, nrhs>1>", "bfStageKernelT<" DT ", wide, coop, nrhs=1>"
+  BF_T_NAMES("C128"), BF_T_NAMES("F64"), BF_T_NAMES("F32"), BF_T_NAMES("C64"),
+#undef BF_T_NAMES
+  "bfStageKernelTBoth<F64, nrhs>1>", "bfStageKernelTBoth<F64, nrhs=1>", "bfStageKernelTBoth<F32, nrhs>1>",
+  "bfStageKernelTBoth<F32, nrhs=1>", "bfStageKernelTBoth<C64, nrhs>1>", "bfStageKernelTBoth<C64, nrhs=1>",
+  "bfReduceKernel<C128>", "bfReduceKernel<F64>", "bfReduceKernel<F64, long>", "bfReduceKernel<F32>",
+  "bfReduceKernel<F32, long>", "bfReduceKernel<C64>", "bfReduceKernel<C64, long>",
+};
+char const *bfhipKernelName(uint32_t id) { return id < BFHIP_KERNEL_COUNT ? kernelNames[id] : NULL; }
+
+int bfhipPlanStageKernels(BfhipOperator const *op, uint64_t stage, uint32_t nrhs, uint32_t *ids, uint32_t cap, uint32_t *count) {
+  if (!op || !count || (cap && !ids) || !nrhs) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "bad stage kernel request");
+  BfPlan const *pl = &op->plan;
+  if (stage >= pl->numStages && op->hasTplan) { stage -= pl->numStages; pl = &op->tplan; }
+  if (stage >= pl->numStages) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "bad stage kernel request");
+  BfStage const *st = &pl->stages[stage];
+  BfLaunchArgs a;
+  stageLaunchArgs(op, pl, st, nrhs, &a);
+  BfKernelLaunch L[2];
+  uint32_t const nl = bfSelectStageKernels(&a, L);
+  uint32_t n = 0;
+  for (uint32_t i = 0; i < nl; ++i, ++n) if (n < cap) ids[n] = L[i].kernel;
+  /* the reduce launches of runPlan: groups of 16, each split by bfdevLaunchReduce into batches of BF_REDUCE_BATCH; a batch
+   * of no rows launches nothing */
+  for (uint64_t r0 = 0; r0 < st->numReduce; r0 += 16) {
+    uint64_t const cnt = st->numReduce - r0 < 16 ? st->numReduce - r0 : 16;
+    for (uint64_t base = 0; base < cnt; base += BF_REDUCE_BATCH) {
+      uint64_t const bc = cnt - base < BF_REDUCE_BATCH ? cnt - base : BF_REDUCE_BATCH;
+      int longLists = 0, rows = 0;
+      for (uint64_t k = 0; k < bc; ++k) {
+        BfReduce const *rd = &st->reduce[r0 + base + k];
+        longLists = longLists || rd->maxSrc >= 64;
+        rows = rows || rd->numRows;
+      }
+      if (!rows) continue;
+      if (n < cap) ids[n] = bfSelectReduceKernel(pl->dtype, longLists);
+      ++n;
+    }
+  }
+  *count = n;
   return 0;
 }
 int bfhipPlanGetReduce(BfhipOperator const *op, uint64_t stage, uint64_t index, BfhipReduceView *v) {

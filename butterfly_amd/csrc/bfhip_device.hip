@@ -837,8 +837,7 @@ __global__ __launch_bounds__(BF_WAVES_PER_WG * 64) void bfStageKernelTBoth(Stage
 // ---------------------------------------------------------------------------
 // All reduces of a stage run in one launch (they are a few microseconds each: 12 separate
 // launches cost 5 % of an apply at N = 65536): the descriptors travel by value in the kernel
-// arguments, a workgroup finds its reduce by scanning <= BF_REDUCE_BATCH block offsets.
-#define BF_REDUCE_BATCH 16
+// arguments, a workgroup finds its reduce by scanning <= BF_REDUCE_BATCH (bfhip_internal.h) block offsets.
 struct ReduceBatch {
   uint32_t count, nrhs;
   void const *temp;
@@ -1152,31 +1151,53 @@ __global__ __launch_bounds__(BF_GM_THREADS) void bfGmresProjectKernel(double2 co
   }
 }
 
-// A forward stage of the real family (f64, f32, complex64).  Items [firstSmall, numItems) are small (BF_ITEM_SMALL): four to
-// a wavefront; with items of both kinds one launch runs both bodies, which write disjoint rows.
-template <int DT>
-static int bfLaunchRealStage(BfLaunchArgs const *a, StageParams p, hipStream_t s) {
-  uint64_t const firstSmall = a->firstSmall < a->numItems ? a->firstSmall : a->numItems;
-  uint64_t const numSmall = a->numItems - firstSmall;
-  p.numItems = (uint32_t)firstSmall;
-  uint32_t grid = (uint32_t)((firstSmall + BF_WAVES_PER_WG - 1) / BF_WAVES_PER_WG);
-  if (grid && numSmall) {
-    StageParams ps = p;
-    ps.items = (BfDevItem const *)a->items + firstSmall;
-    ps.numItems = (uint32_t)numSmall;
-    uint32_t const gridSmall = (uint32_t)((numSmall + 4 * BF_WAVES_PER_WG - 1) / (4 * BF_WAVES_PER_WG));
-    hipLaunchKernelGGL(bfStageKernelRealBoth<DT>, dim3(grid + gridSmall), dim3(BF_WAVES_PER_WG * 64), 0, s, p, ps, grid);
-    return hipFail(hipGetLastError(), "stage launch");
+// One launch of a stage as bfSelectStageKernels (bfhip_internal.h) chose it.  Real family, forward: items [firstSmall,
+// numItems) are small (BF_ITEM_SMALL): four to a wavefront; with items of both kinds one launch runs both bodies, which write
+// disjoint rows.  Transposed: the leading L.coop items of a range get a workgroup each, the rest one wavefront.
+#define BF_REAL_CASES(DT, NAME) \
+  case BFHIP_KERNEL_REAL_##NAME: hipLaunchKernelGGL(bfStageKernelReal<DT>, dim3(grid), dim3(BF_WAVES_PER_WG * 64), 0, s, p); break; \
+  case BFHIP_KERNEL_SMALL_##NAME: hipLaunchKernelGGL(bfStageKernelSmall<DT>, dim3(grid), dim3(BF_WAVES_PER_WG * 64), 0, s, p); break; \
+  case BFHIP_KERNEL_REALBOTH_##NAME: hipLaunchKernelGGL(bfStageKernelRealBoth<DT>, dim3(grid + grid2), dim3(BF_WAVES_PER_WG * 64), 0, s, p, p2, grid); break;
+#define BF_T_CASES(DT, NAME) \
+  case BFHIP_KERNEL_T_##NAME##_NARROW_N: hipLaunchKernelGGL((bfStageKernelT<DT, 16, 4, false, false>), dim3(grid), dim3(BF_WAVES_PER_WG * 64), 0, s, p); break; \
+  case BFHIP_KERNEL_T_##NAME##_NARROW_ONE: hipLaunchKernelGGL((bfStageKernelT<DT, 16, 4, false, true>), dim3(grid), dim3(BF_WAVES_PER_WG * 64), 0, s, p); break; \
+  case BFHIP_KERNEL_T_##NAME##_NARROW_COOP_N: hipLaunchKernelGGL((bfStageKernelT<DT, 16, 4, true, false>), dim3(grid), dim3(BF_WAVES_PER_WG * 64), 0, s, p); break; \
+  case BFHIP_KERNEL_T_##NAME##_NARROW_COOP_ONE: hipLaunchKernelGGL((bfStageKernelT<DT, 16, 4, true, true>), dim3(grid), dim3(BF_WAVES_PER_WG * 64), 0, s, p); break; \
+  case BFHIP_KERNEL_T_##NAME##_WIDE_N: hipLaunchKernelGGL((bfStageKernelT<DT, BF_T_WIDE_R, BF_T_WIDE_R, false, false>), dim3(grid), dim3(BF_WAVES_PER_WG * 64), 0, s, p); break; \
+  case BFHIP_KERNEL_T_##NAME##_WIDE_ONE: hipLaunchKernelGGL((bfStageKernelT<DT, BF_T_WIDE_R, BF_T_WIDE_R, false, true>), dim3(grid), dim3(BF_WAVES_PER_WG * 64), 0, s, p); break; \
+  case BFHIP_KERNEL_T_##NAME##_WIDE_COOP_N: hipLaunchKernelGGL((bfStageKernelT<DT, BF_T_WIDE_R, BF_T_WIDE_R, true, false>), dim3(grid), dim3(BF_WAVES_PER_WG * 64), 0, s, p); break; \
+  case BFHIP_KERNEL_T_##NAME##_WIDE_COOP_ONE: hipLaunchKernelGGL((bfStageKernelT<DT, BF_T_WIDE_R, BF_T_WIDE_R, true, true>), dim3(grid), dim3(BF_WAVES_PER_WG * 64), 0, s, p); break;
+#define BF_TBOTH_CASES(DT, NAME) \
+  case BFHIP_KERNEL_TBOTH_##NAME##_N: hipLaunchKernelGGL((bfStageKernelTBoth<DT, false>), dim3(grid + grid2), dim3(BF_WAVES_PER_WG * 64), 0, s, p, p2, grid); break; \
+  case BFHIP_KERNEL_TBOTH_##NAME##_ONE: hipLaunchKernelGGL((bfStageKernelTBoth<DT, true>), dim3(grid + grid2), dim3(BF_WAVES_PER_WG * 64), 0, s, p, p2, grid); break;
+static int bfLaunchWaveStage(BfKernelLaunch const &L, BfLaunchArgs const *a, StageParams p, hipStream_t s) {
+  bool const small = L.kernel >= BFHIP_KERNEL_SMALL_F64 && L.kernel <= BFHIP_KERNEL_SMALL_C64;
+  uint32_t const perWg = small ? 4 * BF_WAVES_PER_WG : BF_WAVES_PER_WG;      // small items: four to a wavefront
+  p.items = (BfDevItem const *)a->items + L.first[0];
+  p.numItems = (uint32_t)L.count[0];
+  p.coopItems = (uint32_t)L.coop[0];
+  uint32_t const grid = (uint32_t)(L.coop[0] + (L.count[0] - L.coop[0] + perWg - 1) / perWg);
+  StageParams p2 = p;
+  uint32_t grid2 = 0;
+  if (L.numRanges == 2) {
+    bool const tboth = L.kernel >= BFHIP_KERNEL_TBOTH_F64_N && L.kernel <= BFHIP_KERNEL_TBOTH_C64_ONE;
+    uint32_t const perWg2 = tboth ? BF_WAVES_PER_WG : 4 * BF_WAVES_PER_WG;   // REALBOTH: the second range is the small items
+    p2.items = (BfDevItem const *)a->items + L.first[1];
+    p2.numItems = (uint32_t)L.count[1];
+    p2.coopItems = (uint32_t)L.coop[1];
+    grid2 = (uint32_t)(L.coop[1] + (L.count[1] - L.coop[1] + perWg2 - 1) / perWg2);
   }
-  if (grid) hipLaunchKernelGGL(bfStageKernelReal<DT>, dim3(grid), dim3(BF_WAVES_PER_WG * 64), 0, s, p);
-  if (numSmall) {
-    p.items = (BfDevItem const *)a->items + firstSmall;
-    p.numItems = (uint32_t)numSmall;
-    grid = (uint32_t)((numSmall + 4 * BF_WAVES_PER_WG - 1) / (4 * BF_WAVES_PER_WG));
-    hipLaunchKernelGGL(bfStageKernelSmall<DT>, dim3(grid), dim3(BF_WAVES_PER_WG * 64), 0, s, p);
+  switch (L.kernel) {
+    BF_REAL_CASES(BFHIP_F64, F64) BF_REAL_CASES(BFHIP_F32, F32) BF_REAL_CASES(BFHIP_C64, C64)
+    BF_T_CASES(BFHIP_C128, C128) BF_T_CASES(BFHIP_F64, F64) BF_T_CASES(BFHIP_F32, F32) BF_T_CASES(BFHIP_C64, C64)
+    BF_TBOTH_CASES(BFHIP_F64, F64) BF_TBOTH_CASES(BFHIP_F32, F32) BF_TBOTH_CASES(BFHIP_C64, C64)
+    default: return bfhipFail(BFABI_ERROR_RUNTIME_ERROR, "internal: kernel id %u is not a wavefront-per-item stage kernel", L.kernel);
   }
-  return hipFail(hipGetLastError(), "stage launch");
+  return 0;
 }
+#undef BF_REAL_CASES
+#undef BF_T_CASES
+#undef BF_TBOTH_CASES
 
 // ---------------------------------------------------------------------------
 // host-callable wrappers
@@ -1260,85 +1281,43 @@ int bfdevLaunchStage(BfLaunchArgs const *a, void *stream) {
   p.y = a->y;
   p.temp = a->temp;
   p.zero = a->zero;
-  uint32_t grid = (uint32_t)((a->numItems + BF_WAVES_PER_WG - 1) / BF_WAVES_PER_WG);
   hipStream_t s = (hipStream_t)stream;
-  if (a->transposed) {
-    // two ranges of items, two launches: [0, numNarrow) are <= 16 columns of tall leaves (16 row lanes, whole 256-byte
-    // runs, streamed loads), the rest up to 64 columns of short pieces (4 row lanes) unless the stage has none wider
-    // than 16.  In either range the leading big items of many pieces get a workgroup each -- except on the complex
-    // 16-column kernel, which needs 98 VGPRs with the shared-item code (4 wavefronts per SIMD instead of 5) and loses
-    // 5 % on fac_helm2's adjoint.
-    uint64_t const numNarrow = a->numNarrow < a->numItems ? a->numNarrow : a->numItems;
-    if (a->dtype != BFHIP_C128 && numNarrow && numNarrow < a->numItems && a->maxRowsRest > 16) {
-      // real operands with both item families: one launch (bfStageKernelTBoth)
-      StageParams pn = p, pw = p;
-      uint64_t const cntW = a->numItems - numNarrow;
-      uint64_t ncN = a->numCoopNarrow < numNarrow ? a->numCoopNarrow : numNarrow, ncW = a->numCoop < cntW ? a->numCoop : cntW;
-      pn.items = (BfDevItem const *)a->items; pn.numItems = (uint32_t)numNarrow; pn.coopItems = (uint32_t)ncN;
-      pw.items = (BfDevItem const *)a->items + numNarrow; pw.numItems = (uint32_t)cntW; pw.coopItems = (uint32_t)ncW;
-      uint32_t const gridN = (uint32_t)(ncN + (numNarrow - ncN + BF_WAVES_PER_WG - 1) / BF_WAVES_PER_WG);
-      uint32_t const gridW = (uint32_t)(ncW + (cntW - ncW + BF_WAVES_PER_WG - 1) / BF_WAVES_PER_WG);
-#define BF_LAUNCH_TBOTH(DT) do { if (a->nrhs == 1) hipLaunchKernelGGL((bfStageKernelTBoth<DT, true>), dim3(gridN + gridW), dim3(BF_WAVES_PER_WG * 64), 0, s, pn, pw, gridN); \
-                                 else hipLaunchKernelGGL((bfStageKernelTBoth<DT, false>), dim3(gridN + gridW), dim3(BF_WAVES_PER_WG * 64), 0, s, pn, pw, gridN); } while (0)
-      if (a->dtype == BFHIP_F64) BF_LAUNCH_TBOTH(BFHIP_F64);
-      else if (a->dtype == BFHIP_F32) BF_LAUNCH_TBOTH(BFHIP_F32);
-      else if (a->dtype == BFHIP_C64) BF_LAUNCH_TBOTH(BFHIP_C64);
-      else return bfhipFail(BFABI_ERROR_TYPE_ERROR, "unknown dtype %u", a->dtype);
-#undef BF_LAUNCH_TBOTH
-      return hipFail(hipGetLastError(), "transposed stage launch");
-    }
-    for (int range = 0; range < 2; ++range) {
-      uint64_t const first = range ? numNarrow : 0, count = range ? a->numItems - numNarrow : numNarrow;
-      if (!count) continue;
-      bool const wide = range == 1 && a->maxRowsRest > 16;
-      uint64_t nc = range ? a->numCoop : a->numCoopNarrow;
-      if (nc > count) nc = count;
-      if (a->dtype == BFHIP_C128 && !wide) nc = 0;
-      p.items = (BfDevItem const *)a->items + first;
-      p.numItems = (uint32_t)count;
-      p.coopItems = (uint32_t)nc;
-      grid = (uint32_t)(nc + (count - nc + BF_WAVES_PER_WG - 1) / BF_WAVES_PER_WG);
-#define BF_LAUNCH_T1(DT, ONE) do { if (wide && nc) hipLaunchKernelGGL((bfStageKernelT<DT, BF_T_WIDE_R, BF_T_WIDE_R, true, ONE>), dim3(grid), dim3(BF_WAVES_PER_WG * 64), 0, s, p); \
-                             else if (wide) hipLaunchKernelGGL((bfStageKernelT<DT, BF_T_WIDE_R, BF_T_WIDE_R, false, ONE>), dim3(grid), dim3(BF_WAVES_PER_WG * 64), 0, s, p); \
-                             else if (nc) hipLaunchKernelGGL((bfStageKernelT<DT, 16, 4, true, ONE>), dim3(grid), dim3(BF_WAVES_PER_WG * 64), 0, s, p); \
-                             else hipLaunchKernelGGL((bfStageKernelT<DT, 16, 4, false, ONE>), dim3(grid), dim3(BF_WAVES_PER_WG * 64), 0, s, p); } while (0)
-#define BF_LAUNCH_T(DT) do { if (a->nrhs == 1) BF_LAUNCH_T1(DT, true); else BF_LAUNCH_T1(DT, false); } while (0)
-      if (a->dtype == BFHIP_C128) BF_LAUNCH_T(BFHIP_C128);
-      else if (a->dtype == BFHIP_F64) BF_LAUNCH_T(BFHIP_F64);
-      else if (a->dtype == BFHIP_F32) BF_LAUNCH_T(BFHIP_F32);
-      else if (a->dtype == BFHIP_C64) BF_LAUNCH_T(BFHIP_C64);
-      else return bfhipFail(BFABI_ERROR_TYPE_ERROR, "unknown dtype %u", a->dtype);
-#undef BF_LAUNCH_T
-#undef BF_LAUNCH_T1
-    }
-    return hipFail(hipGetLastError(), "transposed stage launch");
-  }
-  if (a->dtype == BFHIP_C128 && a->nrhs >= BF_MFMA_MIN_RHS) {
-    dim3 const g((uint32_t)((a->numItems + BF_MF_WG_WAVES - 1) / BF_MF_WG_WAVES)), b(64 * BF_MF_WG_WAVES);
-    /* more than 32 right-hand sides: one workgroup of four wavefronts per BUNDLE of items that read the same X rows */
-    if (a->nrhs > 32 && BF_MF_BUNDLES && (!a->bundles || !a->numBundles)) return bfhipFail(BFABI_ERROR_RUNTIME_ERROR, "internal: a forward complex128 stage without its bundle table");
-    dim3 const gB(BF_MF_BUNDLES ? (uint32_t)a->numBundles : g.x), bB(BF_MF_BUNDLES ? 256u : b.x);
-    if (a->exactComplex) {                                                                   /* BFHIP_FLAG_EXACT_COMPLEX: four real products per complex one */
-      if (a->nrhs <= 16) hipLaunchKernelGGL(bfStageKernelC128Mfma1Exact, g, b, 0, s, p);
-      else if (a->nrhs <= 32) hipLaunchKernelGGL(bfStageKernelC128Mfma2Exact, g, b, 0, s, p);
-      else hipLaunchKernelGGL(bfStageKernelC128MfmaExact, gB, bB, 0, s, p);
-    }
-    else if (a->nrhs <= 16) hipLaunchKernelGGL(bfStageKernelC128Mfma1, g, b, 0, s, p);       /* one RHS tile: 5 wavefronts per SIMD */
-    else if (a->nrhs <= 32) hipLaunchKernelGGL(bfStageKernelC128Mfma2, g, b, 0, s, p);       /* two: 3 */
-    else hipLaunchKernelGGL(bfStageKernelC128Mfma, gB, bB, 0, s, p);                         /* up to four per pass: 2 */
-  }
-  else if (a->dtype == BFHIP_C128) {
-    grid = (uint32_t)((a->numItems + BF_C128_WG_WAVES - 1) / BF_C128_WG_WAVES);
+  if (!bfDtypeKnown(a->dtype)) return bfhipFail(BFABI_ERROR_TYPE_ERROR, "unknown dtype %u", a->dtype);
+  // Transposed stages: two ranges of items, two launches: [0, numNarrow) are <= 16 columns of tall leaves (16 row lanes,
+  // whole 256-byte runs, streamed loads), the rest up to 64 columns of short pieces (4 row lanes) unless the stage has none
+  // wider than 16; real operands with both item families run them in one launch (bfStageKernelTBoth).  In either range the
+  // leading big items of many pieces get a workgroup each -- except on the complex 16-column kernel, which needs 98 VGPRs
+  // with the shared-item code (4 wavefronts per SIMD instead of 5) and loses 5 % on fac_helm2's adjoint.
+  BfKernelLaunch L[2];
+  uint32_t const nl = bfSelectStageKernels(a, L);
+  for (uint32_t i = 0; i < nl; ++i) {
+    if (L[i].kernel == BFHIP_KERNEL_C128) {
+      uint32_t const grid = (uint32_t)((a->numItems + BF_C128_WG_WAVES - 1) / BF_C128_WG_WAVES);
 #ifdef BFHIP_EXPERIMENTAL
-    { int handled = 0; int const rcx = bfdevLaunchStageExperimental(a, &p, grid, stream, &handled); if (handled) return rcx; }     /* EXPERIMENTAL=1 builds only */
+      { int handled = 0; int const rcx = bfdevLaunchStageExperimental(a, &p, grid, stream, &handled); if (handled) return rcx; }     /* EXPERIMENTAL=1 builds only */
 #endif
-    hipLaunchKernelGGL(bfStageKernelC128, dim3(grid), dim3(BF_C128_WG_WAVES * 64), 0, s, p);
+      hipLaunchKernelGGL(bfStageKernelC128, dim3(grid), dim3(BF_C128_WG_WAVES * 64), 0, s, p);
+    }
+    else if (L[i].kernel <= BFHIP_KERNEL_C128_MFMA4_EXACT) {
+      dim3 const g((uint32_t)((a->numItems + BF_MF_WG_WAVES - 1) / BF_MF_WG_WAVES)), b(64 * BF_MF_WG_WAVES);
+      /* more than 32 right-hand sides: one workgroup of four wavefronts per BUNDLE of items that read the same X rows */
+      if (a->nrhs > 32 && BF_MF_BUNDLES && (!a->bundles || !a->numBundles)) return bfhipFail(BFABI_ERROR_RUNTIME_ERROR, "internal: a forward complex128 stage without its bundle table");
+      dim3 const gB(BF_MF_BUNDLES ? (uint32_t)a->numBundles : g.x), bB(BF_MF_BUNDLES ? 256u : b.x);
+      switch (L[i].kernel) {
+        case BFHIP_KERNEL_C128_MFMA1_EXACT: hipLaunchKernelGGL(bfStageKernelC128Mfma1Exact, g, b, 0, s, p); break;   /* BFHIP_FLAG_EXACT_COMPLEX: four real products per complex one */
+        case BFHIP_KERNEL_C128_MFMA2_EXACT: hipLaunchKernelGGL(bfStageKernelC128Mfma2Exact, g, b, 0, s, p); break;
+        case BFHIP_KERNEL_C128_MFMA4_EXACT: hipLaunchKernelGGL(bfStageKernelC128MfmaExact, gB, bB, 0, s, p); break;
+        case BFHIP_KERNEL_C128_MFMA1: hipLaunchKernelGGL(bfStageKernelC128Mfma1, g, b, 0, s, p); break;               /* one RHS tile: 5 wavefronts per SIMD */
+        case BFHIP_KERNEL_C128_MFMA2: hipLaunchKernelGGL(bfStageKernelC128Mfma2, g, b, 0, s, p); break;               /* two: 3 */
+        default: hipLaunchKernelGGL(bfStageKernelC128Mfma, gB, bB, 0, s, p); break;                                   /* up to four per pass: 2 */
+      }
+    }
+    else {
+      int const rc = bfLaunchWaveStage(L[i], a, p, s);
+      if (rc) return rc;
+    }
   }
-  else if (a->dtype == BFHIP_F64) return bfLaunchRealStage<BFHIP_F64>(a, p, s);
-  else if (a->dtype == BFHIP_F32) return bfLaunchRealStage<BFHIP_F32>(a, p, s);
-  else if (a->dtype == BFHIP_C64) return bfLaunchRealStage<BFHIP_C64>(a, p, s);
-  else return bfhipFail(BFABI_ERROR_TYPE_ERROR, "unknown dtype %u", a->dtype);
-  return hipFail(hipGetLastError(), "stage launch");
+  return hipFail(hipGetLastError(), a->transposed ? "transposed stage launch" : "stage launch");
 }
 
 
@@ -1372,13 +1351,16 @@ int bfdevLaunchReduce(BfReduceArgs const *a, uint32_t count, void *stream) {
     uint32_t const dtype = a[base].dtype;
     bool longLists = false;
     for (uint32_t k = 0; k < B.count; ++k) longLists = longLists || a[base + k].longLists;
-    if (dtype == BFHIP_C128) hipLaunchKernelGGL((bfReduceKernel<double, 2>), dim3(blocks), dim3(256), 0, s, B);
-    else if (dtype == BFHIP_C64 && longLists) hipLaunchKernelGGL((bfReduceKernel<float, 2, true>), dim3(blocks), dim3(256), 0, s, B);
-    else if (dtype == BFHIP_C64) hipLaunchKernelGGL((bfReduceKernel<float, 2>), dim3(blocks), dim3(256), 0, s, B);
-    else if (dtype == BFHIP_F64 && longLists) hipLaunchKernelGGL((bfReduceKernel<double, 1, true>), dim3(blocks), dim3(256), 0, s, B);
-    else if (dtype == BFHIP_F64) hipLaunchKernelGGL((bfReduceKernel<double, 1>), dim3(blocks), dim3(256), 0, s, B);
-    else if (longLists) hipLaunchKernelGGL((bfReduceKernel<float, 1, true>), dim3(blocks), dim3(256), 0, s, B);
-    else hipLaunchKernelGGL((bfReduceKernel<float, 1>), dim3(blocks), dim3(256), 0, s, B);
+    switch (bfSelectReduceKernel(dtype, longLists)) {
+      case BFHIP_KERNEL_REDUCE_C128: hipLaunchKernelGGL((bfReduceKernel<double, 2>), dim3(blocks), dim3(256), 0, s, B); break;
+      case BFHIP_KERNEL_REDUCE_C64_LONG: hipLaunchKernelGGL((bfReduceKernel<float, 2, true>), dim3(blocks), dim3(256), 0, s, B); break;
+      case BFHIP_KERNEL_REDUCE_C64: hipLaunchKernelGGL((bfReduceKernel<float, 2>), dim3(blocks), dim3(256), 0, s, B); break;
+      case BFHIP_KERNEL_REDUCE_F64_LONG: hipLaunchKernelGGL((bfReduceKernel<double, 1, true>), dim3(blocks), dim3(256), 0, s, B); break;
+      case BFHIP_KERNEL_REDUCE_F64: hipLaunchKernelGGL((bfReduceKernel<double, 1>), dim3(blocks), dim3(256), 0, s, B); break;
+      case BFHIP_KERNEL_REDUCE_F32_LONG: hipLaunchKernelGGL((bfReduceKernel<float, 1, true>), dim3(blocks), dim3(256), 0, s, B); break;
+      case BFHIP_KERNEL_REDUCE_F32: hipLaunchKernelGGL((bfReduceKernel<float, 1>), dim3(blocks), dim3(256), 0, s, B); break;
+      default: return bfhipFail(BFABI_ERROR_TYPE_ERROR, "reduce: unknown dtype %u", dtype);
+    }
     int rc = hipFail(hipGetLastError(), "reduce launch");
     if (rc) return rc;
   }

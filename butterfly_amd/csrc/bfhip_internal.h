@@ -299,6 +299,90 @@ typedef struct BfLaunchArgs {
 #define BF_TICKET_POOLS 64u
 #define BF_TICKET_STRIDE 64u      /* uint32 between two pools' counters: a 256-byte block each -- counters that share a cache line share its atomic unit (measured: 64 packed counters behaved like one) */
 int bfdevLaunchStage(BfLaunchArgs const *a, void *stream);
+
+/* Which stage kernels bfdevLaunchStage runs (host-only: bfhipPlanStageKernels reports the same choice without a device).
+ * A launch covers one or two item ranges [first, first + count); the leading `coop` items of a transposed range get a
+ * workgroup each.  Two-range launches (REALBOTH: ordinary then small items; TBOTH: narrow then wide) are one kernel. */
+#ifndef BF_MFMA_MIN_RHS
+#define BF_MFMA_MIN_RHS 2
+#endif
+typedef struct BfKernelLaunch {
+  uint32_t kernel;                 /* BfhipKernelId */
+  uint32_t numRanges;
+  uint64_t first[2], count[2], coop[2];
+} BfKernelLaunch;
+static inline uint32_t bfDtypeRealIndex(uint32_t dt) { return dt == BFHIP_F64 ? 0u : dt == BFHIP_F32 ? 1u : 2u; }   /* F64, F32, C64 */
+static inline uint32_t bfDtypeKnown(uint32_t dt) { return dt == BFHIP_C128 || dt == BFHIP_F64 || dt == BFHIP_F32 || dt == BFHIP_C64; }
+/* returns the number of launches (0 - 2) written to out[]; an unknown dtype gives 0 */
+static inline uint32_t bfSelectStageKernels(BfLaunchArgs const *a, BfKernelLaunch out[2]) {
+  if (!a->numItems || !bfDtypeKnown(a->dtype)) return 0;
+  uint32_t const one = a->nrhs == 1;
+  if (a->transposed) {
+    uint64_t const numNarrow = a->numNarrow < a->numItems ? a->numNarrow : a->numItems;
+    if (a->dtype != BFHIP_C128 && numNarrow && numNarrow < a->numItems && a->maxRowsRest > 16) {
+      uint64_t const cntW = a->numItems - numNarrow;
+      out[0].kernel = BFHIP_KERNEL_TBOTH_F64_N + 2u * bfDtypeRealIndex(a->dtype) + one;
+      out[0].numRanges = 2;
+      out[0].first[0] = 0; out[0].count[0] = numNarrow; out[0].coop[0] = a->numCoopNarrow < numNarrow ? a->numCoopNarrow : numNarrow;
+      out[0].first[1] = numNarrow; out[0].count[1] = cntW; out[0].coop[1] = a->numCoop < cntW ? a->numCoop : cntW;
+      return 1;
+    }
+    uint32_t n = 0;
+    /* dtype-major blocks of 8 in BfhipKernelId: C128, F64, F32, C64 */
+    uint32_t const dtBase = BFHIP_KERNEL_T_C128_NARROW_N + 8u * (a->dtype == BFHIP_C128 ? 0u : 1u + bfDtypeRealIndex(a->dtype));
+    for (int range = 0; range < 2; ++range) {
+      uint64_t const first = range ? numNarrow : 0, count = range ? a->numItems - numNarrow : numNarrow;
+      if (!count) continue;
+      uint32_t const wide = range == 1 && a->maxRowsRest > 16;
+      uint64_t nc = range ? a->numCoop : a->numCoopNarrow;
+      if (nc > count) nc = count;
+      /* complex128 16-column kernel: no shared items (98 VGPRs with the shared-item code: 4 wavefronts per SIMD instead of 5) */
+      if (a->dtype == BFHIP_C128 && !wide) nc = 0;
+      out[n].kernel = dtBase + 4u * wide + 2u * (nc != 0) + one;
+      out[n].numRanges = 1;
+      out[n].first[0] = first; out[n].count[0] = count; out[n].coop[0] = nc;
+      ++n;
+    }
+    return n;
+  }
+  if (a->dtype == BFHIP_C128) {
+    out[0].numRanges = 1; out[0].first[0] = 0; out[0].count[0] = a->numItems; out[0].coop[0] = 0;
+    if (a->nrhs < BF_MFMA_MIN_RHS) out[0].kernel = BFHIP_KERNEL_C128;
+    else out[0].kernel = (a->exactComplex ? BFHIP_KERNEL_C128_MFMA1_EXACT : BFHIP_KERNEL_C128_MFMA1) + (a->nrhs <= 16 ? 0u : a->nrhs <= 32 ? 1u : 2u);
+    return 1;
+  }
+  /* the real family: items [firstSmall, numItems) are small (four to a wavefront) */
+  uint32_t const r = bfDtypeRealIndex(a->dtype);
+  uint64_t const firstSmall = a->firstSmall < a->numItems ? a->firstSmall : a->numItems;
+  uint64_t const numSmall = a->numItems - firstSmall;
+  uint32_t n = 0;
+  if (firstSmall && numSmall) {
+    out[0].kernel = BFHIP_KERNEL_REALBOTH_F64 + r;
+    out[0].numRanges = 2;
+    out[0].first[0] = 0; out[0].count[0] = firstSmall; out[0].coop[0] = 0;
+    out[0].first[1] = firstSmall; out[0].count[1] = numSmall; out[0].coop[1] = 0;
+    return 1;
+  }
+  if (firstSmall) {
+    out[n].kernel = BFHIP_KERNEL_REAL_F64 + r; out[n].numRanges = 1;
+    out[n].first[0] = 0; out[n].count[0] = firstSmall; out[n].coop[0] = 0; ++n;
+  }
+  if (numSmall) {
+    out[n].kernel = BFHIP_KERNEL_SMALL_F64 + r; out[n].numRanges = 1;
+    out[n].first[0] = firstSmall; out[n].count[0] = numSmall; out[n].coop[0] = 0; ++n;
+  }
+  return n;
+}
+/* bfReduceKernel of one batch: `longLists` = some reduce of the batch has a row of >= 64 partial sums (complex128 has no
+ * long instantiation); BFHIP_KERNEL_COUNT for an unknown dtype */
+static inline uint32_t bfSelectReduceKernel(uint32_t dtype, int longLists) {
+  if (dtype == BFHIP_C128) return BFHIP_KERNEL_REDUCE_C128;
+  if (dtype == BFHIP_C64) return longLists ? BFHIP_KERNEL_REDUCE_C64_LONG : BFHIP_KERNEL_REDUCE_C64;
+  if (dtype == BFHIP_F64) return longLists ? BFHIP_KERNEL_REDUCE_F64_LONG : BFHIP_KERNEL_REDUCE_F64;
+  if (dtype == BFHIP_F32) return longLists ? BFHIP_KERNEL_REDUCE_F32_LONG : BFHIP_KERNEL_REDUCE_F32;
+  return BFHIP_KERNEL_COUNT;
+}
+#define BF_REDUCE_BATCH 16        /* reduces per bfReduceKernel launch (their descriptors travel in the kernel arguments) */
 /* bfhip_persist.hip (experimental persistent launch of the complex128 stage kernel) */
 uint32_t bfdevPersistentGrid(void);
 int bfdevLaunchPersistC128(void const *stageParams, uint32_t grid, void *tickets, void *timeline, void *stream);

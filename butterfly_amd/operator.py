@@ -143,6 +143,25 @@ class HipOperator:
     def num_bytes(self):
         return int(self._lib.bfhipNumBytes(self._h))
 
+    def stage_kernels(self, nrhs=1):
+        """bfhipPlanStageKernels over every stage (forward, then the adjoint plan's): per stage the kernel ids an apply of
+        `nrhs` right-hand sides launches, in launch order.  Needs FLAG_PLAN_ONLY (no device is touched)."""
+        info = _capi.BfhipPlanInfo()
+        info.structSize = C.sizeof(info)
+        check(self._lib.bfhipPlanGetInfo(self._h, C.byref(info)))
+        out = []
+        ids = (C.c_uint32 * 64)()
+        for s in range(int(info.numStages) + int(info.numStagesT)):
+            cnt = C.c_uint32(0)
+            check(self._lib.bfhipPlanStageKernels(self._h, s, nrhs, ids, 64, C.byref(cnt)))
+            if cnt.value > 64:
+                ids2 = (C.c_uint32 * cnt.value)()
+                check(self._lib.bfhipPlanStageKernels(self._h, s, nrhs, ids2, cnt.value, C.byref(cnt)))
+                out.append(list(ids2))
+            else:
+                out.append(list(ids[:cnt.value]))
+        return out
+
     def stats(self):
         st = BfhipStats()
         st.structSize = C.sizeof(BfhipStats)

@@ -439,6 +439,39 @@ typedef struct BfhipReduceView {
 int bfhipPlanGetInfo(const BfhipOperator *op, BfhipPlanInfo *info);
 int bfhipPlanGetStage(const BfhipOperator *op, uint64_t stage, BfhipStageView *view);
 int bfhipPlanGetReduce(const BfhipOperator *op, uint64_t stage, uint64_t index, BfhipReduceView *view);
+/* Which kernels an apply runs: one value per instantiation of the apply path's stage and reduce kernels (the experimental
+ * library's executors are not listed).  T = transposed (shared-leaf adjoint); NARROW / WIDE = the 16- and 4-row-lane tilings
+ * of bfStageKernelT, COOP = its workgroup-shared leading items; ONE = the nrhs == 1 instantiation, N = the others. */
+typedef enum BfhipKernelId {
+  BFHIP_KERNEL_C128 = 0,                                  /* forward complex128, nrhs < 2: bfStageKernelC128 */
+  BFHIP_KERNEL_C128_MFMA1, BFHIP_KERNEL_C128_MFMA2, BFHIP_KERNEL_C128_MFMA4,                     /* nrhs <= 16, <= 32, more */
+  BFHIP_KERNEL_C128_MFMA1_EXACT, BFHIP_KERNEL_C128_MFMA2_EXACT, BFHIP_KERNEL_C128_MFMA4_EXACT,   /* BFHIP_FLAG_EXACT_COMPLEX */
+  BFHIP_KERNEL_REAL_F64, BFHIP_KERNEL_REAL_F32, BFHIP_KERNEL_REAL_C64,                           /* bfStageKernelReal */
+  BFHIP_KERNEL_REALBOTH_F64, BFHIP_KERNEL_REALBOTH_F32, BFHIP_KERNEL_REALBOTH_C64,               /* ordinary + small items */
+  BFHIP_KERNEL_SMALL_F64, BFHIP_KERNEL_SMALL_F32, BFHIP_KERNEL_SMALL_C64,                        /* small items alone */
+  /* transposed: 8 per dtype, dtype-major in BFHIP_C128, F64, F32, C64 order */
+  BFHIP_KERNEL_T_C128_NARROW_N, BFHIP_KERNEL_T_C128_NARROW_ONE, BFHIP_KERNEL_T_C128_NARROW_COOP_N, BFHIP_KERNEL_T_C128_NARROW_COOP_ONE,
+  BFHIP_KERNEL_T_C128_WIDE_N, BFHIP_KERNEL_T_C128_WIDE_ONE, BFHIP_KERNEL_T_C128_WIDE_COOP_N, BFHIP_KERNEL_T_C128_WIDE_COOP_ONE,
+  BFHIP_KERNEL_T_F64_NARROW_N, BFHIP_KERNEL_T_F64_NARROW_ONE, BFHIP_KERNEL_T_F64_NARROW_COOP_N, BFHIP_KERNEL_T_F64_NARROW_COOP_ONE,
+  BFHIP_KERNEL_T_F64_WIDE_N, BFHIP_KERNEL_T_F64_WIDE_ONE, BFHIP_KERNEL_T_F64_WIDE_COOP_N, BFHIP_KERNEL_T_F64_WIDE_COOP_ONE,
+  BFHIP_KERNEL_T_F32_NARROW_N, BFHIP_KERNEL_T_F32_NARROW_ONE, BFHIP_KERNEL_T_F32_NARROW_COOP_N, BFHIP_KERNEL_T_F32_NARROW_COOP_ONE,
+  BFHIP_KERNEL_T_F32_WIDE_N, BFHIP_KERNEL_T_F32_WIDE_ONE, BFHIP_KERNEL_T_F32_WIDE_COOP_N, BFHIP_KERNEL_T_F32_WIDE_COOP_ONE,
+  BFHIP_KERNEL_T_C64_NARROW_N, BFHIP_KERNEL_T_C64_NARROW_ONE, BFHIP_KERNEL_T_C64_NARROW_COOP_N, BFHIP_KERNEL_T_C64_NARROW_COOP_ONE,
+  BFHIP_KERNEL_T_C64_WIDE_N, BFHIP_KERNEL_T_C64_WIDE_ONE, BFHIP_KERNEL_T_C64_WIDE_COOP_N, BFHIP_KERNEL_T_C64_WIDE_COOP_ONE,
+  /* transposed real-family stages with both item ranges in one launch (bfStageKernelTBoth) */
+  BFHIP_KERNEL_TBOTH_F64_N, BFHIP_KERNEL_TBOTH_F64_ONE, BFHIP_KERNEL_TBOTH_F32_N, BFHIP_KERNEL_TBOTH_F32_ONE,
+  BFHIP_KERNEL_TBOTH_C64_N, BFHIP_KERNEL_TBOTH_C64_ONE,
+  /* bfReduceKernel; LONG: some row of the batch has >= 64 partial sums */
+  BFHIP_KERNEL_REDUCE_C128, BFHIP_KERNEL_REDUCE_F64, BFHIP_KERNEL_REDUCE_F64_LONG, BFHIP_KERNEL_REDUCE_F32,
+  BFHIP_KERNEL_REDUCE_F32_LONG, BFHIP_KERNEL_REDUCE_C64, BFHIP_KERNEL_REDUCE_C64_LONG,
+  BFHIP_KERNEL_COUNT
+} BfhipKernelId;
+/* "bfStageKernelT<F64, wide, coop, nrhs=1>"-style name of a kernel id; NULL when id >= BFHIP_KERNEL_COUNT */
+const char *bfhipKernelName(uint32_t id);
+/* The kernels, in launch order, that applying stage `stage` (numbering as bfhipPlanGetStage) to `nrhs` right-hand sides
+ * launches: the stage's own kernels, then one reduce kernel per reduce launch.  Works under BFHIP_FLAG_PLAN_ONLY (no device).
+ * *count = the number of launches; at most `cap` ids are written. */
+int bfhipPlanStageKernels(const BfhipOperator *op, uint64_t stage, uint32_t nrhs, uint32_t *ids, uint32_t cap, uint32_t *count);
 /* Write the packed leaf arena (arenaElems elements) to host memory; the
  * descriptor's / graph's leaf values must still be alive.  Synthetic leaves
  * are generated with the host copy of the value stream. */

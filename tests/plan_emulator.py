@@ -38,7 +38,9 @@ def run_plan(op, x, transpose=False):
     info = _capi.BfhipPlanInfo()
     info.structSize = C.sizeof(info)
     _capi.check(lib.bfhipPlanGetInfo(op.handle, C.byref(info)))
-    dt = {0: np.complex128, 1: np.float64, 2: np.float32}[info.dtype]
+    dt = {0: np.complex128, 1: np.float64, 2: np.float32, 3: np.complex64}[info.dtype]
+    # what the kernels accumulate in: complex64 MACs and reduces run in double (one rounding to float per stored result)
+    at = np.complex128 if info.dtype == 3 else dt
     epl = info.epl
     # BFHIP_FLAG_ADJOINT_PACKED: the adjoint plan is a FORWARD plan of the transposed expression over an arena of its own --
     # its stages are run with the forward kernels' semantics on that arena
@@ -81,7 +83,7 @@ def run_plan(op, x, transpose=False):
         for it in items:
             mr = int(it["mrFlags"]) & 0xFFFF
             mr_pad = mr if transpose else (mr + epl - 1) // epl * epl
-            acc = np.zeros((mr, nrhs), dtype=dt)
+            acc = np.zeros((mr, nrhs), dtype=at)
             if int(it["mrFlags"]) & BF_ITEM_SMALL:
                 assert int(it["mrFlags"]) & BF_ITEM_ROWMAJOR and not int(it["mrFlags"]) & BF_ITEM_MERGED      # small items: row-major pieces
             if int(it["mrFlags"]) & BF_ITEM_MERGED and (int(it["mrFlags"]) & BF_ITEM_MERGED or any(not int(pc["flags"]) & BF_PIECE_IDENTITY for pc in pieces[int(it["pieceBegin"]):int(it["pieceBegin"]) + int(it["numPieces"])])):
@@ -98,7 +100,7 @@ def run_plan(op, x, transpose=False):
                 src = x if (int(pc["flags"]) & BF_PIECE_IN_X) else temp
                 io, n = int(pc["inOff"]), int(pc["ncols"])
                 if int(pc["flags"]) & BF_PIECE_IDENTITY:
-                    acc += src[io:io + mr]
+                    acc += src[io:io + mr].astype(at)
                     continue
                 d0 = int(pc["dataOff"])
                 rowmajor = bool(int(pc["flags"]) & BF_PIECE_ROWMAJOR)
@@ -109,12 +111,12 @@ def run_plan(op, x, transpose=False):
                     if transpose:       # n rows of the forward piece, mr of its columns starting at d0
                         assert d0 + (n - 1) * ld + (mr + epl - 1) // epl * epl <= len(arena)
                         idx = d0 + np.arange(n)[None, :] * ld + np.arange(mr)[:, None]
-                        acc += arena[idx] @ src[io:io + n]
+                        acc += arena[idx].astype(at) @ src[io:io + n].astype(at)
                     else:
                         assert int(it["mrFlags"]) & BF_ITEM_ROWMAJOR and ld >= n and mr <= 2 * epl
                         blk = arena[d0:d0 + mr * ld].reshape(mr, ld)
                         assert not blk[:, n:].any(), "row padding must be zero"
-                        acc += blk[:, :n] @ src[io:io + n]
+                        acc += blk[:, :n].astype(at) @ src[io:io + n].astype(at)
                     continue
                 if transpose:
                     # lanes j < mr on the columns of a forward piece: element (step s, lane j) = arena[d0 + j*ld + s]
@@ -123,11 +125,11 @@ def run_plan(op, x, transpose=False):
                     # what bfStageKernelT may touch: columns j < mr, units clamped into the column
                     assert d0 + (mr - 1) * ld + (n + epl - 1) // epl * epl <= len(arena), "transposed piece reaches past the leaf arena"
                     idx = d0 + np.arange(mr)[:, None] * ld + np.arange(n)[None, :]
-                    acc += arena[idx] @ src[io:io + n]
+                    acc += arena[idx].astype(at) @ src[io:io + n].astype(at)
                     continue
                 assert n <= info.xcap
                 a = arena[d0:d0 + mr_pad * n].reshape(n, mr_pad).T[:mr]
-                acc += a @ src[io:io + n]
+                acc += a.astype(at) @ src[io:io + n].astype(at)
             dst = y if (int(it["mrFlags"]) & BF_ITEM_OUT_Y) else temp
             oo = int(it["outOff"])
             dst[oo:oo + mr] = acc
@@ -140,7 +142,7 @@ def run_plan(op, x, transpose=False):
             bias = _view(rv.srcBias, int(rv.numSrc), np.dtype("<i8"))
             dest = y if rv.destIsY else temp[int(rv.destOff):]
             rows = np.arange(int(rv.numRows))
-            out = np.zeros((int(rv.numRows), nrhs), dtype=dt)
+            out = np.zeros((int(rv.numRows), nrhs), dtype=at)
             keep = row_iv != 0xFFFFFFFF           # BF_REDUCE_SKIP: written directly by the one group that owns the row
             assert keep.all() or info.dtype != 0
             riv = np.where(keep, row_iv, 0)
