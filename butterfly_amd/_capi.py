@@ -64,6 +64,11 @@ class BfhipGmresOptions(C.Structure):
                 ("maxNumIter", C.c_size_t), ("solveM", C.c_void_p)]
 
 
+class BfhipGmresRefineOptions(C.Structure):
+    _fields_ = [("structSize", C.c_uint32), ("orthogonalization", C.c_uint32), ("tol", C.c_double),
+                ("innerTol", C.c_double), ("maxOuter", C.c_size_t), ("maxInner", C.c_size_t), ("solveM", C.c_void_p)]
+
+
 class BfhipShardSpec(C.Structure):
     _fields_ = [("structSize", C.c_uint32), ("mode", C.c_uint32), ("numRowsGlobal", C.c_uint64),
                 ("numSegments", C.c_uint32), ("reserved", C.c_uint32), ("segRows", C.c_void_p), ("segOwner", C.c_void_p),
@@ -383,6 +388,12 @@ def load():
     lib.bfhipSolveGMRESOptsDevice.argtypes = [vp, C.POINTER(BfhipGmresOptions), vp, C.c_size_t, vp, C.POINTER(C.c_size_t),
                                               C.POINTER(C.c_double), vp, vp]
     lib.bfhipSolveGMRESOptsDevice.restype = C.c_int
+    sz, pd = C.POINTER(C.c_size_t), C.POINTER(C.c_double)
+    lib.bfhipSolveGMRESRefineDevice.argtypes = [vp, vp, C.POINTER(BfhipGmresRefineOptions), vp, C.c_size_t, vp, sz, sz, pd, pd, vp, vp]
+    lib.bfhipSolveGMRESRefineDevice.restype = C.c_int
+    lib.bfhipSolveGMRESRefine.argtypes = [vp, vp, C.POINTER(BfhipGmresRefineOptions), vp, C.c_size_t, C.c_size_t, vp, C.c_size_t,
+                                          sz, sz, pd, pd, vp, C.c_size_t]
+    lib.bfhipSolveGMRESRefine.restype = C.c_int
     lib.bfhipFlowStatus.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     lib.bfhipFlowStatus.restype = C.c_int
     lib.bfhipGetStats.argtypes = [vp, C.POINTER(BfhipStats)]

@@ -1151,6 +1151,57 @@ __global__ __launch_bounds__(BF_GM_THREADS) void bfGmresProjectKernel(double2 co
   }
 }
 
+// ---- mixed-precision GMRES refinement (bfhip_refine.c): the complex64 inner operator sits between a demote and a promote of
+// the complex128 Krylov vectors; the outer loop scales each residual column to norm 1 and adds the scaled correction.  Streaming
+// kernels, one complex element per thread, bounds-checked against count = n * nrhs.
+__global__ __launch_bounds__(BF_GM_THREADS) void bfRefineDemoteKernel(double2 const *src, float2 *dst, uint64_t count) {
+  uint64_t const e = (uint64_t)blockIdx.x * BF_GM_THREADS + threadIdx.x;
+  if (e >= count) return;
+  double2 const v = src[e];
+  dst[e] = make_float2((float)v.x, (float)v.y);      // round to nearest, each component
+}
+
+__global__ __launch_bounds__(BF_GM_THREADS) void bfRefinePromoteKernel(float2 const *src, double2 *dst, uint64_t count) {
+  uint64_t const e = (uint64_t)blockIdx.x * BF_GM_THREADS + threadIdx.x;
+  if (e >= count) return;
+  float2 const v = src[e];
+  dst[e] = make_double2((double)v.x, (double)v.y);
+}
+
+// per column q: nrm = sqrt(sum of the |R|^2 partials of bfGmresResidualKernel); scale[q] = nrm (as computed: the host reads it);
+// Rhat = R / nrm, or the unit vector 1/sqrt(n) where nrm is not positive (a zero column must not become 0/0)
+__global__ __launch_bounds__(BF_GM_THREADS) void bfRefineScaleKernel(double2 const *R, double2 const *partialIn, double2 *Rhat, double *scale,
+                                                                    uint64_t n, uint32_t nrhs, uint32_t nb) {
+  __shared__ double2 sh[BF_GM_THREADS];
+  uint32_t const q = blockIdx.y;
+  double2 const s = bfSumPartials(partialIn, q, nb, sh);
+  double const nrm = sqrt(s.x);
+  if (blockIdx.x == 0 && threadIdx.x == 0) scale[q] = nrm;
+  bool const live = nrm > 0.0;
+  double const unit = 1.0 / sqrt((double)n);
+  uint64_t r0, r1;
+  bfRowRange(n, nb, r0, r1);
+  for (uint64_t r = r0 + threadIdx.x; r < r1; r += BF_GM_THREADS) {
+    if (live) { double2 const v = R[r * nrhs + q]; Rhat[r * nrhs + q] = make_double2(v.x / nrm, v.y / nrm); }
+    else Rhat[r * nrhs + q] = make_double2(unit, 0.0);
+  }
+}
+
+// Xout = Xin + scale[q] * D; where scale[q] is not positive the column is Xin bit for bit (D is not read)
+__global__ __launch_bounds__(BF_GM_THREADS) void bfRefineUpdateKernel(double2 const *Xin, double2 const *D, double const *scale, double2 *Xout,
+                                                                     uint64_t n, uint32_t nrhs) {
+  uint64_t const e = (uint64_t)blockIdx.x * BF_GM_THREADS + threadIdx.x;
+  if (e >= n * nrhs) return;
+  double const s = scale[e % nrhs];
+  double2 x = Xin ? Xin[e] : make_double2(0.0, 0.0);
+  if (s > 0.0) {
+    double2 const d = D[e];
+    x.x += s * d.x;
+    x.y += s * d.y;
+  }
+  Xout[e] = x;
+}
+
 // One launch of a stage as bfSelectStageKernels (bfhip_internal.h) chose it.  Real family, forward: items [firstSmall,
 // numItems) are small (BF_ITEM_SMALL): four to a wavefront; with items of both kinds one launch runs both bodies, which write
 // disjoint rows.  Transposed: the leading L.coop items of a range get a workgroup each, the rest one wavefront.
@@ -1403,6 +1454,28 @@ int bfdevGmresUpdate(void const *X0, void const *V, void const *y, uint32_t j, v
   uint64_t total = n * nrhs;
   hipLaunchKernelGGL(bfGmresUpdateKernel, dim3((uint32_t)((total + BF_GM_THREADS - 1) / BF_GM_THREADS)), dim3(BF_GM_THREADS), 0, (hipStream_t)stream, (double2 const *)X0, (double2 const *)V, (double2 const *)y, j, (double2 *)X, n, nrhs);
   return hipFail(hipGetLastError(), "gmres update launch");
+}
+static inline dim3 bfRefineGrid(uint64_t count) { return dim3((uint32_t)((count + BF_GM_THREADS - 1) / BF_GM_THREADS)); }
+int bfdevRefineDemote(void const *src128, void *dst64, uint64_t count, void *stream) {
+  if (!count) return 0;
+  hipLaunchKernelGGL(bfRefineDemoteKernel, bfRefineGrid(count), dim3(BF_GM_THREADS), 0, (hipStream_t)stream, (double2 const *)src128, (float2 *)dst64, count);
+  return hipFail(hipGetLastError(), "refine demote launch");
+}
+int bfdevRefinePromote(void const *src64, void *dst128, uint64_t count, void *stream) {
+  if (!count) return 0;
+  hipLaunchKernelGGL(bfRefinePromoteKernel, bfRefineGrid(count), dim3(BF_GM_THREADS), 0, (hipStream_t)stream, (float2 const *)src64, (double2 *)dst128, count);
+  return hipFail(hipGetLastError(), "refine promote launch");
+}
+int bfdevRefineScale(void const *R, void const *partialIn, void *Rhat, double *scale, uint64_t n, uint32_t nrhs, uint32_t nb, void *stream) {
+  hipLaunchKernelGGL(bfRefineScaleKernel, dim3(nb, nrhs), dim3(BF_GM_THREADS), 0, (hipStream_t)stream, (double2 const *)R, (double2 const *)partialIn,
+                     (double2 *)Rhat, scale, n, nrhs, nb);
+  return hipFail(hipGetLastError(), "refine scale launch");
+}
+int bfdevRefineUpdate(void const *Xin, void const *D, double const *scale, void *Xout, uint64_t n, uint32_t nrhs, void *stream) {
+  if (!n) return 0;
+  hipLaunchKernelGGL(bfRefineUpdateKernel, bfRefineGrid(n * nrhs), dim3(BF_GM_THREADS), 0, (hipStream_t)stream, (double2 const *)Xin, (double2 const *)D,
+                     scale, (double2 *)Xout, n, nrhs);
+  return hipFail(hipGetLastError(), "refine update launch");
 }
 int bfdevMemcpyD2HAsync(void *dst, void const *src, size_t bytes, void *stream) { return bytes ? hipFail(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, (hipStream_t)stream), "hipMemcpyAsync D2H") : 0; }
 int bfdevMemcpyH2DAsync(void *dst, void const *src, size_t bytes, void *stream) { return bytes ? hipFail(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, (hipStream_t)stream), "hipMemcpyAsync H2D") : 0; }

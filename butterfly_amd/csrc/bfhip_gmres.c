@@ -95,11 +95,7 @@ int bfGmresSolve(BfGmresApplyFn apply, void *ctx, uint64_t n, int device, BfhipG
   double const tol = opt->tol;
   size_t const maxNumIter = opt->maxNumIter;
   if (opt->orthogonalization > BFHIP_GMRES_ORTH_MGS) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "unknown orthogonalization %u", opt->orthogonalization);
-  int orth = (int)opt->orthogonalization;
-  if (orth == BFHIP_GMRES_ORTH_DEFAULT) {       /* the environment decides only where the caller did not */
-    char const *mgsEnv = getenv("BFHIP_GMRES_MGS");
-    orth = mgsEnv && mgsEnv[0] == '1' ? BFHIP_GMRES_ORTH_MGS : BFHIP_GMRES_ORTH_CGS2;
-  }
+  int const orth = bfGmresResolveOrth(opt->orthogonalization);   /* the environment decides only where the caller did not */
   if (solveM && (bfhipOperatorDevice(solveM) != device || bfhipGetNumRows(solveM) != n || bfhipGetNumCols(solveM) != n))
     return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "the preconditioner must be an n x n operator on the operator's device (linalg.c:92-97)");
   if (solveM) {
@@ -126,62 +122,99 @@ static int solveDevice(BfGmresApplyFn apply, void *ctx, uint64_t n, BfhipOperato
   if (!dB || !dX) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL argument");
   if (maxNumIter == 0) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "maxNumIter must be positive (linalg.c:81-82)");
   if (nrhs == 0 || nrhs > 0xffffu) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "nrhs out of range");
+  BfGmresWork w;
+  int rc = bfGmresWorkInit(&w, n, maxNumIter, nrhs, orth, precond != NULL, dX0 != NULL);
+  if (!rc) rc = bfGmresRun(&w, apply, ctx, precond ? applyOperator : NULL, precond, dB, dX0, tol, numIter, residual, dX, stream);
+  bfGmresWorkRelease(&w);
+  return rc;
+}
+
+int bfGmresResolveOrth(uint32_t orthogonalization) {
+  if (orthogonalization > BFHIP_GMRES_ORTH_MGS) return -1;
+  if (orthogonalization != BFHIP_GMRES_ORTH_DEFAULT) return (int)orthogonalization;
+  char const *mgsEnv = getenv("BFHIP_GMRES_MGS");          /* the environment decides only where the caller did not */
+  return mgsEnv && mgsEnv[0] == '1' ? BFHIP_GMRES_ORTH_MGS : BFHIP_GMRES_ORTH_CGS2;
+}
+
+void bfGmresWorkRelease(BfGmresWork *w) {
+  bfdevFree(w->dV); bfdevFree(w->dW); bfdevFree(w->dPartA); bfdevFree(w->dPartB); bfdevFree(w->dH); bfdevFree(w->dY); bfdevFree(w->dAX0);
+  bfdevFree(w->dPartAll); bfdevFree(w->dH1); bfdevFree(w->dH2); bfdevFree(w->dPre);
+  bfdevEventDestroy(w->evCol[0]); bfdevEventDestroy(w->evCol[1]);
+  bfdevHostFreePinned(w->hHpinned);
+  free(w->H); free(w->S); free(w->Jc); free(w->Js); free(w->y); free(w->rnorm);
+  memset(w, 0, sizeof *w);
+}
+
+int bfGmresWorkInit(BfGmresWork *w, uint64_t n, size_t m, size_t nrhs, int orth, int hasPrecond, int hasX0) {
+  memset(w, 0, sizeof *w);
   int rc = 0;
-  size_t const m = maxNumIter;
   size_t const vecBytes = (size_t)n * nrhs * 16;
   uint32_t nb = (uint32_t)((n + 255) / 256);          /* row blocks = partial sums per RHS and dot */
   if (nb > 1024) nb = 1024;
   if (nb == 0) nb = 1;
-  int const useMgs = orth == BFHIP_GMRES_ORTH_MGS;
+  w->n = n; w->m = m; w->nrhs = nrhs; w->nb = nb;
+  w->useMgs = orth == BFHIP_GMRES_ORTH_MGS; w->hasPrecond = hasPrecond; w->hasX0 = hasX0;
+#define CHECK(expr) do { rc = (expr); if (rc) goto fail; } while (0)
+  CHECK(bfdevMalloc(&w->dV, (m + 1) * vecBytes));
+  CHECK(bfdevMalloc(&w->dW, vecBytes));
+  CHECK(bfdevMalloc(&w->dPartA, (size_t)nb * nrhs * 16));
+  CHECK(bfdevMalloc(&w->dPartB, (size_t)nb * nrhs * 16));
+  CHECK(bfdevMalloc(&w->dH, (m + 2) * nrhs * 16));
+  CHECK(bfdevMalloc(&w->dY, (m + 1) * nrhs * 16));
+  if (!w->useMgs) {
+    CHECK(bfdevMalloc(&w->dPartAll, (size_t)nb * nrhs * (m + 1) * 16));
+    CHECK(bfdevMalloc(&w->dH1, (m + 1) * nrhs * 16));
+    CHECK(bfdevMalloc(&w->dH2, (m + 1) * nrhs * 16));
+  }
+  if (hasX0) CHECK(bfdevMalloc(&w->dAX0, vecBytes));
+  if (hasPrecond) CHECK(bfdevMalloc(&w->dPre, vecBytes));   /* left preconditioner: the vector it is applied to */
+  CHECK(bfdevHostAllocPinned(&w->hHpinned, 2 * (m + 2) * nrhs * sizeof(cplx)));
+  CHECK(bfdevEventCreate(&w->evCol[0]));
+  CHECK(bfdevEventCreate(&w->evCol[1]));
+  w->H = malloc((m + 2) * m * nrhs * sizeof(cplx));   /* H[(j*(m+2) + i)*nrhs + p] */
+  w->S = malloc((m + 1) * nrhs * sizeof(cplx));
+  w->Jc = malloc(m * nrhs * sizeof(cplx));
+  w->Js = malloc(m * nrhs * sizeof(cplx));
+  w->y = malloc((m + 1) * nrhs * sizeof(cplx));
+  w->rnorm = malloc(nrhs * sizeof(double));
+  if (!w->H || !w->S || !w->Jc || !w->Js || !w->y || !w->rnorm) { rc = bfhipFail(BFABI_ERROR_MEMORY_ERROR, "host OOM"); goto fail; }
+  return 0;
+fail:
+  bfGmresWorkRelease(w);
+  return rc;
+#undef CHECK
+}
 
-  void *dV = NULL, *dW = NULL, *dPartA = NULL, *dPartB = NULL, *dH = NULL, *dY = NULL, *dAX0 = NULL;
-  void *dPartAll = NULL, *dH1 = NULL, *dH2 = NULL;     /* CGS2: partials of all dots, coefficients of the two passes */
-  void *dPre = NULL;                                   /* left preconditioner: the vector it is applied to */
-  void *hHpinned = NULL;
-  void *evCol[2] = {NULL, NULL};      /* "column j is in host memory", two in flight */
-  cplx *hHslot[2] = {NULL, NULL};
-  cplx *hH = NULL, *H = NULL, *S = NULL, *Jc = NULL, *Js = NULL, *y = NULL;
-  double *rnorm = NULL;
+int bfGmresRun(BfGmresWork *w, BfGmresApplyFn apply, void *ctx, BfGmresApplyFn precond, void *pctx, void const *dB, void const *dX0,
+               double tol, size_t *numIter, double *residual, void *dX, void *stream) {
+  if ((dX0 && !w->hasX0) || (!precond != !w->hasPrecond)) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "internal: GMRES workspace made for another call");
+  int rc = 0;
+  uint64_t const n = w->n;
+  size_t const m = w->m, nrhs = w->nrhs;
+  size_t const vecBytes = (size_t)n * nrhs * 16;
+  uint32_t const nb = w->nb;
+  int const useMgs = w->useMgs;
+  void *const dV = w->dV, *const dW = w->dW, *const dPartA = w->dPartA, *const dPartB = w->dPartB, *const dH = w->dH, *const dY = w->dY;
+  void *const dAX0 = dX0 ? w->dAX0 : NULL, *const dPartAll = w->dPartAll, *const dH1 = w->dH1, *const dH2 = w->dH2, *const dPre = w->dPre;
+  void *const *evCol = w->evCol;
+  cplx *const hH = w->hHpinned;
+  cplx *const hHslot[2] = {hH, hH + (m + 2) * nrhs};   /* "column j is in host memory", two in flight */
+  cplx *const H = w->H, *const S = w->S, *const Jc = w->Jc, *const Js = w->Js, *const y = w->y;
+  double *const rnorm = w->rnorm;
   size_t j = 0;
   int converged = 0;
   double lastResidual = INFINITY;
+  memset(H, 0, (m + 2) * m * nrhs * sizeof(cplx));
+  memset(S, 0, (m + 1) * nrhs * sizeof(cplx));
 
 #define CHECK(expr) do { rc = (expr); if (rc) goto done; } while (0)
-  CHECK(bfdevMalloc(&dV, (m + 1) * vecBytes));
-  CHECK(bfdevMalloc(&dW, vecBytes));
-  CHECK(bfdevMalloc(&dPartA, (size_t)nb * nrhs * 16));
-  CHECK(bfdevMalloc(&dPartB, (size_t)nb * nrhs * 16));
-  CHECK(bfdevMalloc(&dH, (m + 2) * nrhs * 16));
-  CHECK(bfdevMalloc(&dY, (m + 1) * nrhs * 16));
-  if (!useMgs) {
-    CHECK(bfdevMalloc(&dPartAll, (size_t)nb * nrhs * (m + 1) * 16));
-    CHECK(bfdevMalloc(&dH1, (m + 1) * nrhs * 16));
-    CHECK(bfdevMalloc(&dH2, (m + 1) * nrhs * 16));
-  }
-  CHECK(bfdevHostAllocPinned(&hHpinned, 2 * (m + 2) * nrhs * sizeof(cplx)));
-  hH = hHpinned;
-  hHslot[0] = hH; hHslot[1] = hH + (m + 2) * nrhs;
-  CHECK(bfdevEventCreate(&evCol[0]));
-  CHECK(bfdevEventCreate(&evCol[1]));
-  H = calloc((m + 2) * m * nrhs, sizeof(cplx));       /* H[(j*(m+2) + i)*nrhs + p] */
-  S = calloc((m + 1) * nrhs, sizeof(cplx));
-  Jc = malloc(m * nrhs * sizeof(cplx));
-  Js = malloc(m * nrhs * sizeof(cplx));
-  y = malloc((m + 1) * nrhs * sizeof(cplx));
-  rnorm = malloc(nrhs * sizeof(double));
-  if (!H || !S || !Jc || !Js || !y || !rnorm) { rc = bfhipFail(BFABI_ERROR_MEMORY_ERROR, "host OOM"); goto done; }
-
   /* R = B - A X0 (linalg.c:127-131); X0 == NULL means zeros (:120-123) */
-  if (dX0) {
-    CHECK(bfdevMalloc(&dAX0, vecBytes));
-    CHECK(apply(ctx, dX0, nrhs, dAX0, stream));
-  }
+  if (dX0) CHECK(apply(ctx, dX0, nrhs, dAX0, stream));
   if (precond) {
     /* R = M^{-1} (B - A X0) (:127-135): the difference goes to a scratch vector, the preconditioner writes W,
      * and the norm partials are taken from W */
-    CHECK(bfdevMalloc(&dPre, vecBytes));
     CHECK(bfdevGmresResidual(dB, dAX0, dPre, dPartA, n, (uint32_t)nrhs, nb, stream));
-    CHECK(bfhipApplyDevice(precond, dPre, nrhs, dW, stream));
+    CHECK(precond(pctx, dPre, nrhs, dW, stream));
     CHECK(bfdevGmresResidual(dW, NULL, dW, dPartA, n, (uint32_t)nrhs, nb, stream));
   } else
   CHECK(bfdevGmresResidual(dB, dAX0, dW, dPartA, n, (uint32_t)nrhs, nb, stream));
@@ -209,7 +242,7 @@ static int solveDevice(BfGmresApplyFn apply, void *ctx, uint64_t n, BfhipOperato
     char *Vj = (char *)dV + j_ * vecBytes; \
     if (precond) { \
       CHECK(apply(ctx, Vj, nrhs, dPre, stream));                   /* W = M^{-1} (A V[j])  (:155-163) */ \
-      CHECK(bfhipApplyDevice(precond, dPre, nrhs, dW, stream)); \
+      CHECK(precond(pctx, dPre, nrhs, dW, stream)); \
     } else \
     CHECK(apply(ctx, Vj, nrhs, dW, stream));                       /* W = A V[j]  (:157) */ \
     void *pin = dPartA, *pout = dPartB; \
@@ -278,12 +311,7 @@ finish:
   if (numIter) *numIter = j;
   if (residual) *residual = lastResidual;
 done:
-  (void)bfdevSync(stream);   /* a speculative iteration may still be in flight: drain before its buffers go */
-  bfdevFree(dV); bfdevFree(dW); bfdevFree(dPartA); bfdevFree(dPartB); bfdevFree(dH); bfdevFree(dY); bfdevFree(dAX0);
-  bfdevFree(dPartAll); bfdevFree(dH1); bfdevFree(dH2); bfdevFree(dPre);
-  bfdevEventDestroy(evCol[0]); bfdevEventDestroy(evCol[1]);
-  bfdevHostFreePinned(hHpinned);
-  free(H); free(S); free(Jc); free(Js); free(y); free(rnorm);
+  (void)bfdevSync(stream);   /* a speculative iteration may still be in flight: drain before its buffers go or are reused */
   return rc;
 #undef CHECK
 }

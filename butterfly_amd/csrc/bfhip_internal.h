@@ -237,6 +237,27 @@ typedef int (*BfGmresApplyFn)(void *ctx, void const *dX, size_t nrhs, void *dY, 
 struct BfhipGmresOptions;
 int bfGmresSolve(BfGmresApplyFn apply, void *ctx, uint64_t n, int device, struct BfhipGmresOptions const *opt, void const *dB, size_t nrhs,
                  void const *dX0, size_t *numIter, double *residual, void *dX, void *stream);
+/* BFHIP_GMRES_ORTH_DEFAULT resolved (the environment decides: BFHIP_GMRES_MGS=1 -> MGS, else CGS2); -1 for an unknown value */
+int bfGmresResolveOrth(uint32_t orthogonalization);
+/* The workspace of one solver configuration (order n, at most m Krylov vectors, nrhs columns, orthogonalisation, with or without a
+ * left preconditioner and x0): Krylov basis, partials, pinned Hessenberg slots, host Givens state.  Allocated once and reused by
+ * any number of bfGmresRun calls (the refinement solver of bfhip_refine.c runs one per outer step); on the current device. */
+typedef struct BfGmresWork {
+  uint64_t n;
+  size_t m, nrhs;
+  uint32_t nb;
+  int useMgs, hasPrecond, hasX0;
+  void *dV, *dW, *dPartA, *dPartB, *dH, *dY, *dAX0, *dPartAll, *dH1, *dH2, *dPre, *hHpinned;
+  void *evCol[2];
+  void *H, *S, *Jc, *Js, *y;   /* double _Complex host arrays */
+  double *rnorm;
+} BfGmresWork;
+int bfGmresWorkInit(BfGmresWork *w, uint64_t n, size_t m, size_t nrhs, int orth, int hasPrecond, int hasX0);
+void bfGmresWorkRelease(BfGmresWork *w);   /* idempotent; a zeroed struct is released as a no-op */
+/* One GMRES solve on the workspace: `precond` (may be NULL when the workspace has none) applies M^{-1} like `apply` applies A.
+ * dX0 may be non-NULL only if the workspace was made with hasX0.  Synchronous on return (the stream is drained on every path). */
+int bfGmresRun(BfGmresWork *w, BfGmresApplyFn apply, void *ctx, BfGmresApplyFn precond, void *pctx, void const *dB, void const *dX0,
+               double tol, size_t *numIter, double *residual, void *dX, void *stream);
 
 /* the sharded step on host vectors (bfhip_shard.hip): staging buffers of the sharded object; used by the vtable shim */
 struct BfhipSharded;
@@ -435,6 +456,15 @@ int bfdevGmresProject(void const *V, void *W, void const *h, void *partialOut, u
 int bfdevGmresFinish(void const *W, void const *partialIn, void *Vout, void *hOut, uint64_t n, uint32_t nrhs, uint32_t nb, void *stream);
 /* X = X0 + sum_{i<j} V_i * y[i] ; V = (j) vectors of n*nrhs, y = [j][nrhs] */
 int bfdevGmresUpdate(void const *X0, void const *V, void const *y, uint32_t j, void *X, uint64_t n, uint32_t nrhs, void *stream);
+/* mixed-precision refinement (bfhip_refine.c drives them; streaming kernels, not stage kernels: no BfhipKernelId).
+ * count = complex elements.  Demote rounds each component to nearest. */
+int bfdevRefineDemote(void const *src128, void *dst64, uint64_t count, void *stream);
+int bfdevRefinePromote(void const *src64, void *dst128, uint64_t count, void *stream);
+/* per column q: s = sqrt(sum of the nb |R|^2 partials); s > 0: Rhat = R / s, scale[q] = s; s == 0: Rhat = 1/sqrt(n) (a unit
+ * right-hand side), scale[q] = 0.  scale: nrhs doubles on the device */
+int bfdevRefineScale(void const *R, void const *partialIn, void *Rhat, double *scale, uint64_t n, uint32_t nrhs, uint32_t nb, void *stream);
+/* Xout = Xin + scale[q] * D per column (Xin NULL = zeros); a column with scale 0 is Xin exactly, whatever D holds */
+int bfdevRefineUpdate(void const *Xin, void const *D, double const *scale, void *Xout, uint64_t n, uint32_t nrhs, void *stream);
 int bfdevMemcpyD2HAsync(void *dst, void const *src, size_t bytes, void *stream);
 
 /* ------------------------------------------------------------------------

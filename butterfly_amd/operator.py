@@ -312,6 +312,63 @@ class HipOperator:
                                                   C.byref(it), C.byref(res), C.c_void_p(x.data_ptr()), C.c_void_p(s.cuda_stream)))
         return x, int(it.value), float(res.value)
 
+    _ORTH = {"default": _capi.GMRES_ORTH_DEFAULT, "cgs2": _capi.GMRES_ORTH_CGS2, "mgs": _capi.GMRES_ORTH_MGS}
+
+    def _refine_options(self, tol, inner_tol, max_outer, max_inner, precond, orth):
+        o = _capi.BfhipGmresRefineOptions()
+        o.structSize = C.sizeof(o)
+        o.orthogonalization = self._ORTH[orth]
+        o.tol, o.innerTol, o.maxOuter, o.maxInner = tol, inner_tol, max_outer, max_inner
+        o.solveM = precond.handle if precond is not None else None
+        return o
+
+    def solve_gmres_refine_device(self, b, low, x0=None, tol=1e-12, inner_tol=0.0, max_outer=10, max_inner=100, precond=None,
+                                  orth="default"):
+        """Mixed-precision GMRES refinement (bfhipSolveGMRESRefineDevice): this complex128 operator gives the true residuals,
+        `low` (a complex64 HipOperator, e.g. the demote_to_f32 compile of the same operand) the inner correction solves.
+        b, x0: complex128 torch tensors on the operator's device ([n] or [n, nrhs]).  `precond`: inner left preconditioner
+        (complex64 or complex128 HipOperator).  inner_tol = 0: the library default (1e-6).  Returns
+        (x, num_outer, num_inner, residual, history), history = the true residual of x0 and of each step's iterate."""
+        import torch
+        for name, t in (("b", b), ("x0", x0)):
+            if t is not None and t.dtype != torch.complex128:
+                raise ValueError(f"refinement takes complex128 tensors ({name} is {t.dtype}); the complex64 work is internal")
+        nrhs = 1 if b.dim() == 1 else b.shape[1]
+        x = torch.empty_like(b)
+        no, ni, res = C.c_size_t(0), C.c_size_t(0), C.c_double(0)
+        hist = np.full(max_outer + 1, np.nan)
+        s = torch.cuda.current_stream(b.device)
+        o = self._refine_options(tol, inner_tol, max_outer, max_inner, precond, orth)
+        check(self._lib.bfhipSolveGMRESRefineDevice(self._h, low.handle, C.byref(o), C.c_void_p(b.data_ptr()), nrhs,
+                                                    C.c_void_p(x0.data_ptr()) if x0 is not None else None, C.byref(no), C.byref(ni),
+                                                    C.byref(res), hist.ctypes.data_as(C.POINTER(C.c_double)), C.c_void_p(x.data_ptr()),
+                                                    C.c_void_p(s.cuda_stream)))
+        return x, int(no.value), int(ni.value), float(res.value), hist[:int(no.value) + 1].copy()
+
+    def solve_gmres_refine(self, b: np.ndarray, low, x0=None, tol=1e-12, inner_tol=0.0, max_outer=10, max_inner=100, precond=None,
+                           orth="default"):
+        """bfhipSolveGMRESRefine on host arrays; same arguments and results as solve_gmres_refine_device."""
+        b2 = np.asarray(b)
+        if b2.dtype == np.complex64 or (x0 is not None and np.asarray(x0).dtype == np.complex64):
+            raise ValueError("refinement takes complex128 arrays; the complex64 work is internal")
+        b2 = np.ascontiguousarray(b2, dtype=np.complex128)
+        one_d = b2.ndim == 1
+        if one_d:
+            b2 = b2[:, None]
+        n, nrhs = b2.shape
+        x = np.empty((n, nrhs), dtype=np.complex128)
+        x0p = None
+        if x0 is not None:
+            x02 = np.ascontiguousarray(x0, dtype=np.complex128).reshape(n, nrhs)
+            x0p = x02.ctypes.data
+        no, ni, res = C.c_size_t(0), C.c_size_t(0), C.c_double(0)
+        hist = np.full(max_outer + 1, np.nan)
+        o = self._refine_options(tol, inner_tol, max_outer, max_inner, precond, orth)
+        check(self._lib.bfhipSolveGMRESRefine(self._h, low.handle, C.byref(o), b2.ctypes.data, max(nrhs, 1), nrhs, x0p, max(nrhs, 1),
+                                              C.byref(no), C.byref(ni), C.byref(res), hist.ctypes.data_as(C.POINTER(C.c_double)),
+                                              x.ctypes.data, max(nrhs, 1)))
+        return (x[:, 0] if one_d else x), int(no.value), int(ni.value), float(res.value), hist[:int(no.value) + 1].copy()
+
     def stage_profile(self, reset=False):
         """(ms, launches, bytes) per stage, from hipEvents (needs FLAG_PROFILE)."""
         S = self.stats()["numStages"]

@@ -107,7 +107,8 @@ typedef struct BfhipOptions {
   uint32_t demoteToF32;     /* 1: store/compute BFHIP_F64 operands in fp32 and BFHIP_C128 operands in complex64 (BFHIP_C64; config 5
                              * extension).  A complex64 operator's bfhipApplyDevice / bfhipApplyTransposeDevice take complex64 device
                              * vectors (interleaved float re / im); its host entries (bfhipApply, the vtable shim) keep taking complex128.
-                             * GMRES, covariance products and the Helmholtz builders refuse complex64 (NOT_IMPLEMENTED / TYPE_ERROR). */
+                             * GMRES, covariance products and the Helmholtz builders refuse complex64 (NOT_IMPLEMENTED / TYPE_ERROR);
+                             * bfhipSolveGMRESRefine[Device] takes one as its inner operator. */
   uint32_t reserved0;
   uint64_t seed;            /* value seed for synthetic (data == NULL) leaves */
   /* row sharding: keep only block rows
@@ -350,6 +351,38 @@ typedef struct BfhipGmresOptions {
 } BfhipGmresOptions;
 int bfhipSolveGMRESOptsDevice(BfhipOperator *op, const BfhipGmresOptions *opt, const void *dB, size_t nrhs, const void *dX0,
                               size_t *numIter, double *residual, void *dX, void *stream);
+
+/* Mixed-precision GMRES refinement: complex128 accuracy from mostly complex64 work.  The outer loop computes TRUE residuals
+ * r = b - A x with `op` (complex128); each correction A d = r is solved by an inner GMRES (unrestarted, `maxInner` Krylov
+ * vectors, from zero, to `innerTol`) that applies only `opLow` (complex64), and x += d.  Each column's correction is solved
+ * on r_p / ||r_p||, so every column gains the full inner reduction.  `opLow` may be any complex64 approximation of `op` (the
+ * demoteToF32 compile of the same operand is the intended one); it is not checked against `op`, and a worse approximation
+ * only converges more slowly.  Stops when max_p ||b_p - A x_p|| / ||b_p|| <= tol (a column with b_p = 0: ||A x_p||), after
+ * maxOuter steps, or on stagnation: a step that does not bring that residual below 0.5 x the previous one.  Stagnation and
+ * the step cap return 0 with the residual as it is, like bfhipSolveGMRES when it does not converge.  dX receives the iterate
+ * of the smallest residual seen (x0 itself if no step improved on it).  A column whose residual is exactly zero keeps its
+ * x_p bit for bit.  Outputs (each may be NULL): numOuter = refinement steps taken, numInner = inner iterations summed over
+ * the steps, residual = the true relative residual of dX, history = maxOuter + 1 doubles: the residual of x0, then of each
+ * step's iterate (entries past numOuter: NaN).  Types: `op` complex128 and `opLow` complex64 (TYPE_ERROR otherwise), both
+ * n x n on one device; dB, dX0 (NULL = zeros) and dX complex128 row-major n x nrhs as for bfhipSolveGMRESDevice.  Every
+ * argument is checked before the operator's device is (plan-only operators reach each refusal).  Device operators
+ * compiled from a BfMat or a descriptor only: the Helmholtz builders make no complex64 operator. */
+typedef struct BfhipGmresRefineOptions {
+  uint32_t structSize;          /* = sizeof(BfhipGmresRefineOptions) */
+  uint32_t orthogonalization;   /* inner GMRES: BFHIP_GMRES_ORTH_* (as BfhipGmresOptions) */
+  double tol;                   /* outer: max_p ||b_p - A x_p|| / ||b_p|| <= tol, A = `op`; > 0 */
+  double innerTol;              /* relative tolerance of each correction solve; 0 = 1e-6 */
+  size_t maxOuter;              /* refinement steps, > 0 */
+  size_t maxInner;              /* Krylov vectors per correction solve, > 0 */
+  BfhipOperator *solveM;        /* inner left preconditioner (action of M^{-1}, n x n, complex64 or complex128) or NULL */
+} BfhipGmresRefineOptions;
+int bfhipSolveGMRESRefineDevice(BfhipOperator *op, BfhipOperator *opLow, const BfhipGmresRefineOptions *opt, const void *dB, size_t nrhs,
+                                const void *dX0, size_t *numOuter, size_t *numInner, double *residual, double *history, void *dX,
+                                void *stream);
+/* Host-array form (row-major with leading dimensions in elements, like bfhipSolveGMRES); runs on the default stream. */
+int bfhipSolveGMRESRefine(BfhipOperator *op, BfhipOperator *opLow, const BfhipGmresRefineOptions *opt, const void *B, size_t ldb, size_t nrhs,
+                          const void *X0, size_t ldx0, size_t *numOuter, size_t *numInner, double *residual, double *history, void *X,
+                          size_t ldx);
 
 /* ---- introspection ------------------------------------------------------- */
 int bfhipGetStats(const BfhipOperator *op, BfhipStats *stats);

@@ -1,0 +1,75 @@
+"""Test infrastructure: a numpy restatement of mixed-precision GMRES refinement
+(butterfly_amd/csrc/bfhip_refine.c).  The outer loop computes true residuals
+with a complex128 matvec; each correction is solved by oracle/linalg_ref.py's
+GMRES on a complex64 model of the operator, on the residual scaled to unit norm
+per column; the solve stops at tol, after max_outer steps, or when a step does
+not halve the residual, and returns the iterate of the smallest residual."""
+from __future__ import annotations
+
+import numpy as np
+
+from oracle import linalg_ref
+
+INNER_TOL_DEFAULT = 1e-6          # BfhipGmresRefineOptions.innerTol = 0
+# outer steps the restatement needs on bie.second_kind_case(2048, 128), three random columns (seed 7), tol 1e-12,
+# default inner tolerance (tests/test_gmres_refine_cpu.py checks it; the GPU tests allow one more)
+OUTER_STEPS_2048 = 3
+
+
+def c64_model(plan_only_c64_op):
+    """The complex64 operator as the device applies it inside refinement: the input rounded to complex64, the plan
+    run with double accumulation (tests/plan_emulator.py), the result stored as complex64, promoted back."""
+    import plan_emulator
+
+    def mv(v):
+        v = np.asarray(v)
+        v2 = v if v.ndim == 2 else v[:, None]
+        y = plan_emulator.run_plan(plan_only_c64_op, v2.astype(np.complex64)).astype(np.complex128)
+        return y if v.ndim == 2 else y[:, 0]
+    return mv
+
+
+def true_residual(matmul, B, X):
+    """max_p ||b_p - A x_p|| / ||b_p|| (a column with b_p = 0: ||A x_p||)."""
+    B = B if B.ndim == 2 else B[:, None]
+    X = X if X.ndim == 2 else X[:, None]
+    rn = np.linalg.norm(B - matmul(X), axis=0)
+    bn = np.linalg.norm(B, axis=0)
+    return float(np.max(np.where(bn > 0, rn / np.where(bn > 0, bn, 1), rn)))
+
+
+def solve_refine(matmul, matmul_low, B, X0=None, tol=1e-12, inner_tol=INNER_TOL_DEFAULT, max_outer=10, max_inner=100, msolve=None):
+    """Returns (X, num_outer, num_inner, history)."""
+    B = np.asarray(B, dtype=np.complex128)
+    one_d = B.ndim == 1
+    if one_d:
+        B = B[:, None]
+    n, nrhs = B.shape
+    X = np.zeros_like(B) if X0 is None else np.asarray(X0, dtype=np.complex128).reshape(n, nrhs).copy()
+    bn = np.linalg.norm(B, axis=0)
+
+    def residual(X):
+        R = B - matmul(X)
+        rn = np.linalg.norm(R, axis=0)
+        return R, rn, float(np.max(np.where(bn > 0, rn / np.where(bn > 0, bn, 1), rn)))
+
+    R, rn, r = residual(X)
+    history = [r]
+    best, best_res = X, r
+    k = inner = 0
+    while k < max_outer and not r <= tol and np.isfinite(r):
+        live = rn > 0
+        Rhat = np.where(live, R / np.where(live, rn, 1), 1 / np.sqrt(n))       # zero column: unit right-hand side, scale 0
+        D, it, _ = linalg_ref.solve_gmres(matmul_low, Rhat, tol=inner_tol, max_num_iter=max_inner, msolve=msolve)
+        inner += it
+        X = X + np.where(live, rn, 0) * D
+        k += 1
+        R, rn, rk = residual(X)
+        history.append(rk)
+        if rk < best_res:
+            best, best_res = X, rk
+        stagnated = not rk < 0.5 * r
+        r = rk
+        if stagnated:
+            break
+    return (best[:, 0] if one_d else best), k, inner, history
