@@ -335,6 +335,13 @@ class DescArrays:
         return C.byref(self.struct)
 
 
+BFHIP_EXTRACT_VIA_ADJOINT = 1
+
+
+class BfhipExtractOptions(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("panel", C.c_uint32)]
+
+
 class BfhipError(RuntimeError):
     def __init__(self, code, msg=""):
         self.code = code
@@ -376,6 +383,17 @@ def load():
     lib.bfhipApplyTranspose.restype = C.c_int
     lib.bfhipApplyTransposeDevice.argtypes = [vp, vp, C.c_size_t, vp, vp]
     lib.bfhipApplyTransposeDevice.restype = C.c_int
+    lib.bfhipOperatorDevice.argtypes = [vp]       # (internal: the HIP ordinal an operator lives on, -1 for a plan-only one)
+    lib.bfhipOperatorDevice.restype = C.c_int
+    lib.bfhipSetHostApplyBudget.argtypes = [vp, C.c_uint64]
+    lib.bfhipSetHostApplyBudget.restype = C.c_int
+    u64p = C.POINTER(C.c_uint64)
+    lib.bfhipExtractDevice.argtypes = [vp, u64p, C.c_size_t, u64p, C.c_size_t, vp, C.c_size_t, C.POINTER(BfhipExtractOptions), vp]
+    lib.bfhipExtractDevice.restype = C.c_int
+    lib.bfhipExtract.argtypes = [vp, u64p, C.c_size_t, u64p, C.c_size_t, vp, C.c_size_t, C.POINTER(BfhipExtractOptions)]
+    lib.bfhipExtract.restype = C.c_int
+    lib.bfhipExtractWorkspaceBytes.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(BfhipExtractOptions), u64p]
+    lib.bfhipExtractWorkspaceBytes.restype = C.c_int
     lib.bfhipSolveGMRES.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp, C.c_size_t, C.c_double, C.c_size_t,
                                     C.POINTER(C.c_size_t), C.POINTER(C.c_double), vp, C.c_size_t]
     lib.bfhipSolveGMRES.restype = C.c_int

@@ -86,11 +86,15 @@ struct BfhipOperator {
   uint32_t flowNumItems, flowGrid, flowEpoch, flowQueueBase, flowMaxWriters;
   uint64_t flowNumBufs;
   uint8_t evFlow[64];               /* per event set: that apply ran as ONE launch (its time is recorded under stage 0) */
+  uint64_t hostApplyBudget;         /* device bytes the host-vector apply may use for vectors; 0 = free memory - BF_HOST_BUDGET_MARGIN */
+  void *extract;                    /* workspace of the dense extraction (bfhip_extract.c), released by extractRelease */
+  void (*extractRelease)(void *);
 };
 
 #define BF_ARENA_SLACK 256u
 #define BF_HOST_PIECE_ROWS 8192u    /* host vectors of more than 4 x this many rows cross PCIe in 4 pieces, copy and DMA overlapped */
 #define BF_EV_POOL 64u
+#define BF_HOST_BUDGET_MARGIN (512ull << 20)   /* automatic host-apply budget: what the device has free, less this */
 
 static void freeDevicePlanOf(BfPlan *plan) {
   for (uint64_t s = 0; s < plan->numStages && plan->stages; ++s) {
@@ -118,6 +122,7 @@ void bfhipFree(BfhipOperator **pop) {
     bfdevGetDevice(&prev);
     bfdevSetDevice(op->device);
   }
+  if (op->extractRelease) op->extractRelease(op->extract);
   if (op->evStart && op->evStop) for (uint64_t s = 0; s < BF_EV_POOL * op->plan.numStages; ++s) { bfdevEventDestroy(op->evStart[s]); bfdevEventDestroy(op->evStop[s]); }
   free(op->evStart); free(op->evStop); free(op->stageMs); free(op->stageLaunches);
   freeDevicePlan(op);
@@ -936,15 +941,10 @@ out:
  * The wait is on the apply's own stream, not on the device.  The library never registers a caller's buffer by itself: a cached
  * registration of memory the caller has since freed (glibc hands 4 MB vectors back to the kernel) would leave the GPU with a stale
  * mapping. */
-static int applyHost(BfhipOperator *op, int transpose, void const *X, size_t ldx, size_t nrhs, void *Y, size_t ldy) {
-  if (!op || !X || !Y) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL argument");
-  if (transpose && !op->hasTplan) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "operator was not compiled with BFHIP_FLAG_ADJOINT");
-  if (nrhs == 0 || ldx < nrhs || ldy < nrhs) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "bad nrhs / leading dimension");
-  if (op->flags & BFHIP_FLAG_PLAN_ONLY) return bfhipFail(BFABI_ERROR_RUNTIME_ERROR, "operator was compiled with BFHIP_FLAG_PLAN_ONLY: no device operator exists");
+/* One piece of it: all `nrhs` columns (<= 0xffff) in one apply, with the staging buffers and the vector arena sized for them.
+ * The operator's device is current. */
+static int applyHostPiece(BfhipOperator *op, int transpose, void const *X, size_t ldx, size_t nrhs, void *Y, size_t ldy) {
   int rc;
-  int prev = -1;
-  bfdevGetDevice(&prev);
-  if ((rc = bfdevSetDevice(op->device))) return rc;
   size_t es = op->plan.elemSize;
   size_t hostEs = op->srcDtype == BFHIP_C128 ? 16 : 8;      /* host side is always double precision */
   size_t const nc = bfDtypeComplex(op->plan.dtype) ? 2 : 1;  /* scalars per element (the fp32 / complex64 conversions below) */
@@ -1010,8 +1010,87 @@ static int applyHost(BfhipOperator *op, int transpose, void const *X, size_t ldx
     if (m == 0 && (rc = bfdevSync(NULL))) goto out;
   }
 out:
+  return rc;
+}
+
+int bfhipHostApplyPanelWidth(uint64_t nrhs, uint64_t perColBytes, uint64_t budget, uint64_t *width) {
+  if (!width || !nrhs) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL width / zero nrhs");
+  uint64_t const fit = perColBytes ? budget / perColBytes : UINT64_MAX;      /* columns the budget holds */
+  if (nrhs <= 0xffffu && nrhs <= fit) { *width = nrhs; return 0; }
+  uint64_t w = (fit < 0xffffu ? fit : 0xffffu) / 64 * 64;
+  if (w > nrhs) w = nrhs;
+  if (w < 64) {
+    *width = 0;
+    return bfhipFail(BFABI_ERROR_MEMORY_ERROR, "host apply: %llu device bytes per column, budget %llu bytes: %llu columns fit, a panel needs %llu",
+                     (unsigned long long)perColBytes, (unsigned long long)budget, (unsigned long long)fit, (unsigned long long)(nrhs < 64 ? nrhs : 64));
+  }
+  *width = w;
+  return 0;
+}
+
+/* Columns per piece of a host-vector apply.  The call runs in one piece -- today's path, bit for bit -- unless it cannot:
+ * more than 0xffff columns (what one apply takes), or a working set (two staging vectors of the longer side + the vector
+ * arena, per column) larger than the budget.  The budget is bfhipSetHostApplyBudget's, or, when that is 0, the free device
+ * memory plus what the operator already holds for vectors, less BF_HOST_BUDGET_MARGIN; the automatic budget is only consulted
+ * when the call would grow the buffers and has more than 64 columns.  Pieces are the widest multiple of 64 columns that fits;
+ * they are packed through the staging buffers, so vectors in device memory cannot be panelled (refused past 0xffff
+ * columns, run in one piece otherwise). */
+static int hostApplyWidth(BfhipOperator *op, int transpose, void const *X, void const *Y, size_t nrhs, uint64_t *width) {
+  *width = nrhs;
+  uint64_t const es = op->plan.elemSize;
+  uint64_t const n = transpose ? op->plan.numRows : op->plan.numCols, m = transpose ? op->plan.numCols : op->plan.numRows;
+  uint64_t const big = n > m ? n : m;
+  uint64_t const te = op->plan.tempElems > op->tplan.tempElems ? op->plan.tempElems : op->tplan.tempElems;
+  uint64_t const perCol = (2 * big + te) * es;
+  uint64_t budget = op->hostApplyBudget;
+  int rc;
+  if (!budget) {
+    if (nrhs <= 0xffffu && (nrhs <= 64 || (op->xyRhs >= nrhs && op->tempRhs >= nrhs))) return 0;     /* nothing grows */
+    uint64_t freeBytes = 0;
+    if ((rc = bfdevMemFree(&freeBytes))) return rc;
+    uint64_t const held = (uint64_t)op->xyRhs * 2 * big * es + (uint64_t)op->tempRhs * te * es;
+    budget = freeBytes + held > BF_HOST_BUDGET_MARGIN ? freeBytes + held - BF_HOST_BUDGET_MARGIN : 1;
+  }
+  if ((rc = bfhipHostApplyPanelWidth(nrhs, perCol, budget, width))) return rc;
+  if (*width < nrhs) {
+    int const kx = bfdevPointerKind(X), ky = bfdevPointerKind(Y);
+    if (kx == 1 || kx == 3 || ky == 1 || ky == 3) {
+      if (nrhs > 0xffffu) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "host apply of %llu > 65535 columns needs host vectors (device memory cannot be panelled)", (unsigned long long)nrhs);
+      *width = nrhs;
+    }
+  }
+  return 0;
+}
+
+static int applyHost(BfhipOperator *op, int transpose, void const *X, size_t ldx, size_t nrhs, void *Y, size_t ldy) {
+  if (!op || !X || !Y) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL argument");
+  if (transpose && !op->hasTplan) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "operator was not compiled with BFHIP_FLAG_ADJOINT");
+  if (nrhs == 0 || ldx < nrhs || ldy < nrhs) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "bad nrhs / leading dimension");
+  if (op->flags & BFHIP_FLAG_PLAN_ONLY) return bfhipFail(BFABI_ERROR_RUNTIME_ERROR, "operator was compiled with BFHIP_FLAG_PLAN_ONLY: no device operator exists");
+  int rc;
+  int prev = -1;
+  bfdevGetDevice(&prev);
+  if ((rc = bfdevSetDevice(op->device))) return rc;
+  uint64_t width = nrhs;
+  if ((rc = hostApplyWidth(op, transpose, X, Y, nrhs, &width))) goto out;
+  if (width >= nrhs) rc = applyHostPiece(op, transpose, X, ldx, nrhs, Y, ldy);
+  else {
+    /* column panels: each is packed into the staging buffers (ld != width), applied and unpacked like a call of its own */
+    size_t const hostEs = op->srcDtype == BFHIP_C128 ? 16 : 8;
+    for (uint64_t c0 = 0; c0 < nrhs && !rc; c0 += width) {
+      uint64_t const w = nrhs - c0 < width ? nrhs - c0 : width;
+      rc = applyHostPiece(op, transpose, (char const *)X + c0 * hostEs, ldx, w, (char *)Y + c0 * hostEs, ldy);
+    }
+  }
+out:
   if (prev >= 0 && prev != op->device) bfdevSetDevice(prev);
   return rc;
+}
+
+int bfhipSetHostApplyBudget(BfhipOperator *op, uint64_t bytes) {
+  if (!op) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL operator");
+  op->hostApplyBudget = bytes;
+  return 0;
 }
 
 /* A caller who knows the lifetime of its vectors (the Krylov basis of a solver, a right-hand side applied many times) registers
@@ -1033,6 +1112,9 @@ int bfhipApplyTranspose(BfhipOperator *op, void const *X, size_t ldx, size_t nrh
 }
 
 /* ---- introspection ---------------------------------------------------------- */
+void **bfhipOperatorExtractSlot(BfhipOperator *op, void (*release)(void *)) { op->extractRelease = release; return &op->extract; }
+uint64_t bfhipOperatorTempElems(BfhipOperator const *op) { return op->plan.tempElems > op->tplan.tempElems ? op->plan.tempElems : op->tplan.tempElems; }
+uint32_t bfhipOperatorElemSize(BfhipOperator const *op) { return op ? op->plan.elemSize : 0; }
 int bfhipOperatorHasAdjoint(BfhipOperator const *op) { return op ? op->hasTplan : 0; }
 uint32_t bfhipOperatorSrcDtype(BfhipOperator const *op) { return op ? op->srcDtype : BFHIP_C128; }
 int bfhipOperatorDevice(BfhipOperator const *op) { return (!op || (op->flags & BFHIP_FLAG_PLAN_ONLY)) ? -1 : op->device; }
@@ -1750,6 +1832,10 @@ static BfAbiVec *shimApplyVec(BfAbiMat const *lhs, BfAbiVec const *vec, int rmul
 static BfAbiVec *shimMulVec(BfAbiMat const *lhs, BfAbiVec const *vec) { return shimApplyVec(lhs, vec, 0); }
 static BfAbiVec *shimRmulVec(BfAbiMat const *lhs, BfAbiVec const *vec) { return shimApplyVec(lhs, vec, 1); }
 
+/* ToType (slot 54, bfMatToType) densifies through the extraction of bfhip_extract.c.  The slot is referenced weakly so that this
+ * file still links without that one (the host sanitizer harness links the plan-side files alone: there the slot stays NULL). */
+extern BfAbiMat *bfhipShimToType(BfAbiMat const *m, int type) __attribute__((weak));
+
 static BfAbiMatVtable ShimVtable = {.slot = {
   [BFABI_SLOT_GetView] = (void *)shimGetView,
   [BFABI_SLOT_RmulVec] = (void *)shimRmulVec,
@@ -1762,7 +1848,18 @@ static BfAbiMatVtable ShimVtable = {.slot = {
   [BFABI_SLOT_Rmul] = (void *)shimRmul,
   [BFABI_SLOT_MulVec] = (void *)shimMulVec,
   [BFABI_SLOT_Transpose] = (void *)shimTranspose,
+  [BFABI_SLOT_ToType] = (void *)bfhipShimToType,
 }};
+
+int bfhipShimGet(void const *mat, BfhipOperator **op, int *transposed, int *sharded) {
+  BfhipMat const *s = mat;
+  if (!s || s->super.vtbl != &ShimVtable) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "not a bfhipMatNew object");
+  if (op) *op = s->op;
+  if (transposed) *transposed = s->transposed;
+  if (sharded) *sharded = s->sh != NULL;
+  return 0;
+}
+void bfhipShimRaise(int code) { shimRaise(code); }
 
 void *bfhipMatNew(BfhipOperator *op, int ownsOperator) {
   if (!op) { bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL operator"); return NULL; }

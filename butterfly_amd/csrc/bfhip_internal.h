@@ -556,6 +556,38 @@ int bfdevEventRecord(void *ev, void *stream);
 int bfdevEventElapsed(void *start, void *stop, float *ms);
 int bfdevEventSync(void *ev);
 
+/* dense extraction A[I, J] (bfhip_extract.hip; driven by bfhip_extract.c only -- no file of the host sanitizer harness calls
+ * these).  Index lists are (idx, base): entry k is idx[base + k], or base + k when idx == NULL (all rows / columns).
+ * Unit panel: X[prev(k) * prevLd + k] = 0 for k < prevCount, then X[new(k) * ld + k] = 1 for k < count (<= 64 each).
+ * Gather: Out[i * ldOut + k] = Y[rows(i) * p + k].  Transposed gather: Out[k * ldOut + j] = P[cols(j) * p + k] (p <= 64).
+ * An index >= ext is skipped (unit) or reads as zero (gathers). */
+int bfdevExtractUnit(void *X, uint32_t dtype, uint64_t ext, uint64_t const *prevIdx, uint64_t prevBase, uint32_t prevCount, uint32_t prevLd,
+                     uint64_t const *idx, uint64_t base, uint32_t count, uint32_t ld, void *stream);
+int bfdevExtractGather(void *Out, uint64_t ldOut, void const *Y, uint64_t ext, uint32_t p, uint64_t const *rows, uint64_t rowBase, uint64_t numRows,
+                       uint32_t elemSize, void *stream);
+int bfdevExtractGatherT(void *Out, uint64_t ldOut, void const *P, uint64_t ext, uint32_t p, uint64_t const *cols, uint64_t colBase, uint64_t numCols,
+                        uint32_t elemSize, void *stream);
+int bfdevStreamCreateNonBlocking(void **stream);
+void bfdevStreamDestroy(void *stream);
+int bfdevStreamWaitEvent(void *stream, void *ev);
+int bfdevMemcpy2DAsync(void *dst, size_t dpitch, void const *src, size_t spitch, size_t width, size_t height, void *stream);
+
+/* host side of the extraction (bfhip_api.c keeps the state on the operator; bfhip_extract.c owns what it means) */
+/* the operator's extraction workspace slot; `release` is stored and called on it by bfhipFree */
+void **bfhipOperatorExtractSlot(struct BfhipOperator *op, void (*release)(void *));
+/* largest vector-arena elements per right-hand side of the operator's plans (what bfhipOperatorReserveRhs allocates per RHS) */
+uint64_t bfhipOperatorTempElems(struct BfhipOperator const *op);
+/* element size of the operator on the device; 0 for NULL */
+uint32_t bfhipOperatorElemSize(struct BfhipOperator const *op);
+/* the vtable shim object behind a BfMat of bfhipMatNew / bfhipShardedMatNew: its operator, whether it is transposed and whether
+ * it is sharded.  INVALID_ARGUMENTS if `mat` is not a shim object. */
+int bfhipShimGet(void const *mat, struct BfhipOperator **op, int *transposed, int *sharded);
+void bfhipShimRaise(int code);     /* the reference's bfSetError(code), when forwarding is on and the host process has it */
+/* Panel width of a host-vector apply of `nrhs` columns, `perColBytes` device bytes per column, under `budget` bytes:
+ * *width = nrhs when the call runs in one piece (nrhs <= 0xffff and nrhs * perColBytes <= budget), else the widest multiple
+ * of 64 (<= 0xffff, <= nrhs) that fits; MEMORY_ERROR when not even min(64, nrhs) columns fit.  Host-only. */
+int bfhipHostApplyPanelWidth(uint64_t nrhs, uint64_t perColBytes, uint64_t budget, uint64_t *width);
+
 #ifdef __cplusplus
 }
 #endif

@@ -241,6 +241,61 @@ class HipOperator:
                                          C.c_void_p(s.cuda_stream)))
         return y
 
+    # ---- dense extraction ----------------------------------------------------
+    def _extract_args(self, rows, cols, via_adjoint, panel):
+        m, n = self.shape
+        idx = []
+        for sel, ext in ((rows, m), (cols, n)):
+            if sel is None:
+                idx.append((None, ext, None))
+            else:
+                a = np.ascontiguousarray(np.asarray(sel).reshape(-1), dtype=np.uint64)
+                idx.append((a.ctypes.data_as(C.POINTER(C.c_uint64)), a.size, a))
+        o = _capi.BfhipExtractOptions(_capi.BFHIP_EXTRACT_VIA_ADJOINT if via_adjoint else 0, int(panel))
+        return idx[0], idx[1], o
+
+    def extract(self, rows=None, cols=None, via_adjoint=False, panel=64, device=True, out=None, stream=None):
+        """A[rows, cols] (None = all): bfhipExtractDevice into a torch tensor on the operator's GPU in the compute dtype
+        (device=True; async on the current torch stream unless `stream` is given), or bfhipExtract into a double-precision numpy
+        array (device=False).  `out` may be given (2-D, its row stride is ldOut)."""
+        (rp, nr, ra), (cp, nc, ca), o = self._extract_args(rows, cols, via_adjoint, panel)
+        if device:
+            import torch
+            tdt = self._torch_dtype()
+            if out is None:
+                ordinal = self._lib.bfhipOperatorDevice(self._h)
+                if ordinal < 0:
+                    check(self._lib.bfhipExtractDevice(self._h, rp, nr, cp, nc, None, nc, C.byref(o), None))   # the refusal
+                out = torch.empty((nr, nc), dtype=tdt, device=torch.device("cuda", ordinal))
+            if out.dtype != tdt or not out.is_cuda or out.dim() != 2 or out.stride(1) != 1 or tuple(out.shape) != (nr, nc):
+                raise ValueError(f"out must be a CUDA tensor of dtype {tdt}, shape ({nr}, {nc}) and unit column stride")
+            s = stream if stream is not None else torch.cuda.current_stream(out.device)
+            check(self._lib.bfhipExtractDevice(self._h, rp, nr, cp, nc, C.c_void_p(out.data_ptr()), max(out.stride(0), nc), C.byref(o),
+                                               C.c_void_p(s.cuda_stream)))
+            return out
+        hdt = self._host_dtype()
+        if out is None:
+            out = np.empty((nr, nc), dtype=hdt)
+        if out.dtype != hdt or out.ndim != 2 or out.shape != (nr, nc) or out.strides[1] != out.itemsize:
+            raise ValueError(f"out must be a numpy array of dtype {np.dtype(hdt)}, shape ({nr}, {nc}) and unit column stride")
+        check(self._lib.bfhipExtract(self._h, rp, nr, cp, nc, C.c_void_p(out.ctypes.data), max(out.strides[0] // out.itemsize, nc), C.byref(o)))
+        return out
+
+    def extract_workspace_bytes(self, num_rows, num_cols, via_adjoint=False, panel=64):
+        """bfhipExtractWorkspaceBytes: device bytes an extraction of num_rows x num_cols entries may hold beyond the operator."""
+        o = _capi.BfhipExtractOptions(_capi.BFHIP_EXTRACT_VIA_ADJOINT if via_adjoint else 0, int(panel))
+        b = C.c_uint64()
+        check(self._lib.bfhipExtractWorkspaceBytes(self._h, num_rows, num_cols, C.byref(o), C.byref(b)))
+        return int(b.value)
+
+    def to_dense(self, device=False):
+        """The whole operator as a dense matrix (numpy, double precision; a torch tensor in the compute dtype with device=True)."""
+        return self.extract(device=device)
+
+    def set_host_apply_budget(self, nbytes):
+        """bfhipSetHostApplyBudget: device bytes the host-vector applies may use for vectors (0 = automatic)."""
+        check(self._lib.bfhipSetHostApplyBudget(self._h, int(nbytes)))
+
     def apply_transpose_host(self, x: np.ndarray) -> np.ndarray:
         """bfhipApplyTranspose: y = A^T x (plain transpose) on host arrays; the
         operator must have been compiled with FLAG_ADJOINT."""

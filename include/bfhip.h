@@ -223,6 +223,49 @@ int bfhipApplyDevice(BfhipOperator *op, const void *dX, size_t nrhs, void *dY, v
 int bfhipApplyTranspose(BfhipOperator *op, const void *X, size_t ldx, size_t nrhs, void *Y, size_t ldy);
 int bfhipApplyTransposeDevice(BfhipOperator *op, const void *dX, size_t nrhs, void *dY, void *stream);
 
+/* Device bytes bfhipApply / bfhipApplyTranspose / the vtable shim may use for vectors (two staging vectors of the longer side and
+ * the vector arena, per right-hand side).  A call that needs more, or has more than 65535 right-hand sides, runs in column panels
+ * of the widest multiple of 64 that fits, each packed through the staging buffers (MEMORY_ERROR if not even 64 columns fit).
+ * 0 (the default) = automatic: the device's free memory plus what the operator holds for vectors, less 512 MiB, consulted only
+ * when a call of more than 64 right-hand sides would grow those buffers.  A call that fits runs in one piece as before. */
+int bfhipSetHostApplyBudget(BfhipOperator *op, uint64_t bytes);
+
+/* ---- dense extraction ------------------------------------------------------ */
+/* Entries of the operator, Out[i * ldOut + j] = A[rows[i], cols[j]]: a block A[I, J] (a near-field block, a check against the
+ * dense kernel) or, with rows = cols = NULL, the whole matrix (what the reference's bfMatToType densifies, src/mat_product.c:377-407).
+ * The operator is applied to panels of `panel` (<= 64) unit vectors and the wanted rows of each result are gathered: the cost is
+ * ceil(numCols / panel) applies of `panel` right-hand sides, and the memory is bounded by bfhipExtractWorkspaceBytes whatever the
+ * block's size.  With BFHIP_EXTRACT_VIA_ADJOINT the panels run over the ROW set through the adjoint plan (A^T applied to unit
+ * vectors; plain transpose, no conjugation: A[I, J] = (A^T)[J, I]), the cheaper route when numRows < numCols.
+ *   rows / cols: HOST arrays of uint64 indices (any order, repeats allowed); NULL = all rows (numRows must then equal the
+ *                operator's rows), likewise cols.  numRows or numCols == 0: nothing is done.
+ * Every argument is checked on the host before anything is enqueued -- INVALID_ARGUMENTS (NULL operator / output, ldOut <
+ * numCols, panel > 64, unknown flags, VIA_ADJOINT without BFHIP_FLAG_ADJOINT, a NULL set with the wrong count), OUT_OF_RANGE (an
+ * index) -- also on a BFHIP_FLAG_PLAN_ONLY operator, which is then refused (RUNTIME_ERROR).  Sharded operators are not supported. */
+typedef struct BfhipExtractOptions {
+  uint32_t flags;        /* BFHIP_EXTRACT_VIA_ADJOINT: panels run over the row set through the adjoint plan */
+  uint32_t panel;        /* columns per panel, 1..64; 0 = 64 */
+} BfhipExtractOptions;
+#define BFHIP_EXTRACT_VIA_ADJOINT 1u
+/* dOut: DEVICE memory of the operator's GPU, in the operator's compute element type (complex64 / f32 for a demoted operator),
+ * numRows rows of ldOut elements.  Setup may synchronise (uploading the indices, growing the workspace and the vector arena);
+ * every launch after it goes on `stream`, and the call returns without waiting for them.  Not graph-capturable (unlike
+ * bfhipApplyDevice).  `opt` may be NULL (forward route, panels of 64). */
+int bfhipExtractDevice(BfhipOperator *op, const uint64_t *rows, size_t numRows, const uint64_t *cols, size_t numCols,
+                       void *dOut, size_t ldOut, const BfhipExtractOptions *opt, void *stream);
+/* Out: HOST memory, double precision (complex128 or f64, a demoted operator's results promoted as bfhipApply does); synchronous.
+ * The copy of one panel's gathered block overlaps the apply of the next; a pinned or registered Out (bfhipHostRegister) of the
+ * operator's own element size is the target of the DMA itself, anything else is unpacked from pinned staging on the CPU. */
+int bfhipExtract(BfhipOperator *op, const uint64_t *rows, size_t numRows, const uint64_t *cols, size_t numCols,
+                 void *Out, size_t ldOut, const BfhipExtractOptions *opt);
+/* Device bytes the two entries may hold beyond the operator, with p = the panel width and es = the device element size:
+ *   (numRows_A + numCols_A) * p * es        input and result panel
+ * + (numRows + numCols) * 8                 index copies
+ * + tempElems * p * es                      vector arena at p right-hand sides (BfhipStats.tempElems, both plans)
+ * + 2 * g * p * es                          the host entry's two gathered blocks, g = numRows (forward) or numCols (VIA_ADJOINT).
+ * Host-only: works on a BFHIP_FLAG_PLAN_ONLY operator.  The workspace is kept on the operator (grown, never shrunk) until bfhipFree. */
+int bfhipExtractWorkspaceBytes(const BfhipOperator *op, size_t numRows, size_t numCols, const BfhipExtractOptions *opt, uint64_t *bytes);
+
 /* ---- GMRES (the production caller of the apply path) --------------------- */
 
 /* Solve A X = B with the operator as A, mirroring the reference's

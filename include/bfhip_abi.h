@@ -114,6 +114,7 @@ enum {
   BFABI_SLOT_MulInplace = 43,
   BFABI_SLOT_Rmul = 44,
   BFABI_SLOT_RmulVec = 45,
+  BFABI_SLOT_ToType = 54,          /* bfMatToType(mat, BfType) -> BfMat * */
   BFABI_SLOT_Transpose = 63,
   BFABI_NUM_MAT_SLOTS = 66
 };
