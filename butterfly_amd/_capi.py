@@ -342,6 +342,23 @@ class BfhipExtractOptions(C.Structure):
     _fields_ = [("flags", C.c_uint32), ("panel", C.c_uint32)]
 
 
+BFHIP_BJ_NO_INVERT = 1
+
+
+class BfhipBlockJacobiOptions(C.Structure):
+    _fields_ = [("structSize", C.c_uint32), ("flags", C.c_uint32), ("maxBlock", C.c_uint32), ("outDtype", C.c_uint32),
+                ("cuts", C.c_void_p), ("numBlocks", C.c_uint64), ("device", C.c_int32), ("maxRhs", C.c_uint32)]
+
+
+class BfhipBlockJacobiInfo(C.Structure):
+    _fields_ = [("structSize", C.c_uint32), ("reserved", C.c_uint32), ("numBlocks", C.c_uint64), ("maxBlockRows", C.c_uint64),
+                ("uncoveredRows", C.c_uint64), ("firstSingularBlock", C.c_int64), ("minPivotRel", C.c_double),
+                ("gatherSeconds", C.c_double), ("invertSeconds", C.c_double), ("compileSeconds", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k not in ("structSize", "reserved")}
+
+
 class BfhipError(RuntimeError):
     def __init__(self, code, msg=""):
         self.code = code
@@ -394,6 +411,10 @@ def load():
     lib.bfhipExtract.restype = C.c_int
     lib.bfhipExtractWorkspaceBytes.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(BfhipExtractOptions), u64p]
     lib.bfhipExtractWorkspaceBytes.restype = C.c_int
+    lib.bfhipBlockJacobiPartition.argtypes = [vp, C.c_uint32, u64p, C.c_uint64, u64p]
+    lib.bfhipBlockJacobiPartition.restype = C.c_int
+    lib.bfhipBlockJacobi.argtypes = [vp, C.POINTER(BfhipBlockJacobiOptions), C.POINTER(vp), C.POINTER(BfhipBlockJacobiInfo)]
+    lib.bfhipBlockJacobi.restype = C.c_int
     lib.bfhipSolveGMRES.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp, C.c_size_t, C.c_double, C.c_size_t,
                                     C.POINTER(C.c_size_t), C.POINTER(C.c_double), vp, C.c_size_t]
     lib.bfhipSolveGMRES.restype = C.c_int

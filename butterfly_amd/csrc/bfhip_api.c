@@ -1118,6 +1118,8 @@ uint32_t bfhipOperatorElemSize(BfhipOperator const *op) { return op ? op->plan.e
 int bfhipOperatorHasAdjoint(BfhipOperator const *op) { return op ? op->hasTplan : 0; }
 uint32_t bfhipOperatorSrcDtype(BfhipOperator const *op) { return op ? op->srcDtype : BFHIP_C128; }
 int bfhipOperatorDevice(BfhipOperator const *op) { return (!op || (op->flags & BFHIP_FLAG_PLAN_ONLY)) ? -1 : op->device; }
+BfPlan const *bfhipOperatorPlan(BfhipOperator const *op) { return op ? &op->plan : NULL; }
+void const *bfhipOperatorArena(BfhipOperator const *op) { return op ? op->dArena : NULL; }
 size_t bfhipGetNumRows(BfhipOperator const *op) { return op ? op->plan.numRows : 0; }
 size_t bfhipGetNumCols(BfhipOperator const *op) { return op ? op->plan.numCols : 0; }
 size_t bfhipNumBytes(BfhipOperator const *op) { return op ? op->plan.leafElems * (op->srcDtype == BFHIP_C128 ? 16 : 8) : 0; }

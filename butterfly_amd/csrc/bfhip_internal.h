@@ -588,6 +588,42 @@ void bfhipShimRaise(int code);     /* the reference's bfSetError(code), when for
  * of 64 (<= 0xffff, <= nrhs) that fits; MEMORY_ERROR when not even min(64, nrhs) columns fit.  Host-only. */
 int bfhipHostApplyPanelWidth(uint64_t nrhs, uint64_t perColBytes, uint64_t budget, uint64_t *width);
 
+/* block-Jacobi preconditioner (bfhip_precond.c reads the operator through these; bfhip_api.c does not call it) */
+/* the forward plan: host mirrors on a plan-only operator, device tables (dItems, dPieces, reduce d*) otherwise */
+BfPlan const *bfhipOperatorPlan(struct BfhipOperator const *op);
+void const *bfhipOperatorArena(struct BfhipOperator const *op);    /* leaf arena on the device; NULL for a plan-only operator */
+
+/* bfhip_precond.hip (driven by bfhip_precond.c only -- no file of the host sanitizer harness calls these).
+ * Workspace: per block b a row-major m_b x m_b matrix at element wsOff[b] (complex double for complex operands, double for
+ * real ones).  Task t of block b (tasks [taskBegin[b], taskBegin[b + 1]), walked in order, one workgroup per block):
+ * ws[b](br + r, bc + c) += arena[dataOff + r * ldr + c * ldc] for r < nr, c < nc; an identity task (ldr == ldc == 0) adds 1 at
+ * (br + r, bc + r) for r < nr. */
+typedef struct BfBjTask {
+  uint64_t dataOff;
+  uint32_t br, bc, nr, nc;
+  uint32_t ldr, ldc;
+} BfBjTask;
+typedef struct BfBjBlock {
+  uint64_t wsOff;
+  uint32_t m, taskBegin, taskEnd, pad;
+} BfBjBlock;
+/* per block of the inversion: status 0 = inverted, 1 = zero or non-finite pivot (the block is left as it is); the smallest
+ * |pivot| seen and the largest |B_b(i, j)| */
+typedef struct BfBjResult {
+  double minPivot, maxAbs;
+  uint32_t status, step;
+} BfBjResult;
+/* srcDtype = the operator's storage dtype; the workspace is complex iff it is complex */
+int bfdevBjGather(void *ws, void const *arena, uint64_t arenaElems, uint32_t srcDtype, BfBjBlock const *dBlocks, BfBjTask const *dTasks, uint64_t numBlocks,
+                  void *stream);
+int bfdevBjInvert(void *ws, int cplx, BfBjBlock const *dBlocks, BfBjResult *dResults, uint64_t numBlocks, void *stream);
+/* arena[dataOff + e] of a result piece = ws element (row0 + r, col0 + c) of its block, converted to outDtype (padding: 0) */
+typedef struct BfBjFillPiece {
+  uint64_t dataOff, wsOff;
+  uint32_t m, row0, col0, mr, mrPad, ncols, rowMajor, ld;
+} BfBjFillPiece;
+int bfdevBjFill(void *arena, uint32_t outDtype, void const *ws, BfBjFillPiece const *dPieces, uint64_t numPieces, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

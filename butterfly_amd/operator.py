@@ -292,6 +292,49 @@ class HipOperator:
         """The whole operator as a dense matrix (numpy, double precision; a torch tensor in the compute dtype with device=True)."""
         return self.extract(device=device)
 
+    # ---- block-Jacobi preconditioner ---------------------------------------------
+    def block_jacobi_partition(self, max_block=128) -> np.ndarray:
+        """bfhipBlockJacobiPartition: the automatic diagonal-block cuts (numBlocks + 1 row offsets from 0 to n).  Works on a
+        FLAG_PLAN_ONLY operator."""
+        n = self.shape[0]
+        cuts = np.zeros(n + 1, dtype=np.uint64)
+        nb = C.c_uint64(0)
+        check(self._lib.bfhipBlockJacobiPartition(self._h, int(max_block), cuts.ctypes.data_as(C.POINTER(C.c_uint64)), cuts.size, C.byref(nb)))
+        return cuts[:nb.value + 1].astype(np.int64)
+
+    def block_jacobi(self, cuts=None, max_block=128, invert=True, dtype=None, **opts):
+        """bfhipBlockJacobi: M = blockdiag(B_b^{-1}) over the operator's direct part (blockdiag(B_b) with invert=False), a new
+        HipOperator usable as `precond` of the GMRES entries.  `cuts`: None (automatic) or numBlocks + 1 increasing row
+        offsets from 0 to n; `dtype`: None (the operator's) or BFHIP_C64 / BFHIP_F32 (the demotion); `opts`: device (of the
+        result, -1 = the operator's), max_rhs.  Returns (operator, info); a refusal raises BfhipError with `.info` set."""
+        unknown = set(opts) - {"device", "max_rhs"}
+        if unknown:
+            raise TypeError(f"unknown options {sorted(unknown)}")
+        device, max_rhs = opts.get("device", -1), opts.get("max_rhs", 0)
+        o = _capi.BfhipBlockJacobiOptions()
+        o.structSize = C.sizeof(o)
+        o.flags = 0 if invert else _capi.BFHIP_BJ_NO_INVERT
+        o.maxBlock = int(max_block)
+        o.outDtype = 0 if dtype is None else int(dtype)
+        o.device = int(device)
+        o.maxRhs = int(max_rhs)
+        keep = None
+        if cuts is not None:
+            keep = np.ascontiguousarray(np.asarray(cuts).reshape(-1), dtype=np.uint64)
+            if keep.size < 1:
+                raise ValueError("cuts must hold numBlocks + 1 offsets")
+            o.cuts = keep.ctypes.data
+            o.numBlocks = keep.size - 1
+        info = _capi.BfhipBlockJacobiInfo()
+        info.structSize = C.sizeof(info)
+        h = C.c_void_p()
+        rc = self._lib.bfhipBlockJacobi(self._h, C.byref(o), C.byref(h), C.byref(info))
+        if rc:
+            err = _capi.BfhipError(rc, self._lib.bfhipLastErrorMessage().decode())
+            err.info = info.as_dict()
+            raise err
+        return HipOperator(h.value), info.as_dict()
+
     def set_host_apply_budget(self, nbytes):
         """bfhipSetHostApplyBudget: device bytes the host-vector applies may use for vectors (0 = automatic)."""
         check(self._lib.bfhipSetHostApplyBudget(self._h, int(nbytes)))

@@ -427,6 +427,66 @@ int bfhipSolveGMRESRefine(BfhipOperator *op, BfhipOperator *opLow, const BfhipGm
                           const void *X0, size_t ldx0, size_t *numOuter, size_t *numInner, double *residual, double *history, void *X,
                           size_t ldx);
 
+/* ---- block-Jacobi preconditioner ------------------------------------------ */
+/* A preconditioner made on the device from the operator itself, for `solveM` of the GMRES entries above (the reference's
+ * production caller assembles the same kind: examples/multiple_scattering/multiple_scattering_context.c:544-606).
+ *
+ * The direct part A_dir of a SQUARE operator is the sum of the terms that map x to y within one stage of its compiled plan:
+ * pieces that read x and either write y or write a vector-arena slot that a reduce of the same stage sums into y.  Identity
+ * leaves count as identity entries.  The factors of a product never qualify (its first factor writes an intermediate, its
+ * last reads one), so product contributions inside a diagonal block are LEFT OUT: this is a near-field preconditioner.  On a
+ * fac_helm2 operand with leaf-aligned blocks nothing is left out (products couple only well-separated boxes), and the
+ * gathered block B_b = A_dir[D_b, D_b] equals A[D_b, D_b], the folded decorations (self value, KR correction, column
+ * weights) included.  The values are read from the operator's device plan tables and leaf arena, so operators from
+ * bfhipCompile, bfhipCompileDesc, the device builders and bfhipLoad all work, with no host values and no applies.
+ *
+ * Blocks D_b = [cuts[b], cuts[b + 1]) partition [0, n).  Automatic cuts: the direct pieces whose rectangle meets the diagonal
+ * are merged, row range with column range, into connected intervals (identity pieces cover only their diagonal entries);
+ * on a fac_helm2 operand these are exactly the leaf boxes of the quadtree.  A row no such piece covers is its own 1 x 1
+ * block (its direct diagonal entry is zero; it is taken as 1, so M = 1 there) and is counted in `uncoveredRows`; an uncovered
+ * row inside a caller's block gets the same 1 on its diagonal.  An interval longer than maxBlock is refused
+ * (INVALID_ARGUMENTS: pass cuts), never split.
+ *
+ * The result M = blockdiag(B_b^{-1}) (or blockdiag(B_b) with BFHIP_BJ_NO_INVERT) is an ordinary operator: a BlockDiag of dense
+ * leaves, applied, saved, loaded and described like any other.  The inverses are EXPLICIT (batched Gauss-Jordan with partial
+ * pivoting in double / complex double, ties to the smaller row), unlike the reference's LU solves (bfLuSolve): the
+ * preconditioner runs on the stage kernels, and its rounding differs from an LU solve's.  Repeated builds are bit-identical.
+ *
+ * Errors: INCOMPATIBLE_SHAPES (a non-square operator, a row shard included), INVALID_ARGUMENTS (NULL pointers, unknown
+ * flags, maxBlock > 256, cuts that are not strictly increasing from 0 to n or have a block over maxBlock, an automatic
+ * interval over maxBlock), TYPE_ERROR (an outDtype the operator's dtype cannot be demoted to), NOT_IMPLEMENTED
+ * (bfhipBlockJacobi on a BFHIP_FLAG_PLAN_ONLY operator, after every check above), RUNTIME_ERROR (a block with a zero or
+ * non-finite pivot: info.firstSingularBlock is set and no operator is made), MEMORY_ERROR.  Sharded operators are not
+ * supported; blocks are contiguous and at most 256 rows. */
+#define BFHIP_BJ_NO_INVERT 1u
+#define BFHIP_BJ_MAX_BLOCK 256u
+typedef struct BfhipBlockJacobiOptions {
+  uint32_t structSize;     /* = sizeof(BfhipBlockJacobiOptions) */
+  uint32_t flags;          /* BFHIP_BJ_NO_INVERT: M = blockdiag(B_b) itself */
+  uint32_t maxBlock;       /* 0 -> 128; <= 256 */
+  uint32_t outDtype;       /* 0 -> op's dtype; BFHIP_C64 from a complex128 op (inner preconditioner of the refinement), BFHIP_F32 from f64 */
+  const uint64_t *cuts;    /* [numBlocks + 1] or NULL = automatic */
+  uint64_t numBlocks;
+  int32_t device;          /* of the result; -1 = op's */
+  uint32_t maxRhs;         /* of the result, as BfhipOptions */
+} BfhipBlockJacobiOptions;
+typedef struct BfhipBlockJacobiInfo {
+  uint32_t structSize, reserved;   /* structSize = sizeof(BfhipBlockJacobiInfo) */
+  uint64_t numBlocks, maxBlockRows, uncoveredRows;
+  int64_t firstSingularBlock;      /* -1 if none */
+  double minPivotRel;              /* min over blocks of |pivot| / max |B_b| */
+  double gatherSeconds;            /* plan tables downloaded, block lists built, blocks gathered */
+  double invertSeconds;            /* the batched inversion (0 with BFHIP_BJ_NO_INVERT) */
+  double compileSeconds;           /* the result compiled and filled */
+} BfhipBlockJacobiInfo;
+/* The automatic cuts: cuts[0..numBlocks] (at most `cap` entries are written; *numBlocks is set whenever the partition
+ * exists).  maxBlock 0 -> 128.  Host-only on a BFHIP_FLAG_PLAN_ONLY operator (its plan's host mirrors); a device operator's
+ * plan tables are downloaded. */
+int bfhipBlockJacobiPartition(const BfhipOperator *op, uint32_t maxBlock, uint64_t *cuts, uint64_t cap, uint64_t *numBlocks);
+/* *pre = the preconditioner (freed with bfhipFree); `opt` may be NULL (automatic cuts, inverses, op's dtype and device);
+ * `info` may be NULL.  Synchronous; the workspace (sum of m_b^2 elements in double precision) is released before returning. */
+int bfhipBlockJacobi(BfhipOperator *op, const BfhipBlockJacobiOptions *opt, BfhipOperator **pre, BfhipBlockJacobiInfo *info);
+
 /* ---- introspection ------------------------------------------------------- */
 int bfhipGetStats(const BfhipOperator *op, BfhipStats *stats);
 size_t bfhipGetNumRows(const BfhipOperator *op);
