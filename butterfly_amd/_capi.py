@@ -156,6 +156,27 @@ def recipe_array(recipes: dict) -> np.ndarray:
     return out
 
 
+class BfhipLstSqOptions(C.Structure):
+    _fields_ = [("structSize", C.c_uint32), ("reserved", C.c_uint32), ("qrMin", C.c_int64), ("gramMin", C.c_int64),
+                ("forceGlobal", C.c_int64)]
+
+
+JACOBI_PLAIN, JACOBI_GRAM, JACOBI_GLOBAL = 0, 1, 2
+LSTSQ_ROUTE_FIELDS = ("qr", "qrLdsClass", "qrStreaming", "jacobi", "w", "threads", "ldsClass", "resident")
+
+
+class BfhipLstSqRoute(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in LSTSQ_ROUTE_FIELDS]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n in LSTSQ_ROUTE_FIELDS}
+
+
+class BfhipLstSqInfo(C.Structure):
+    _fields_ = [("route", BfhipLstSqRoute), ("rank", C.c_uint32), ("qrRank", C.c_uint32), ("sweeps", C.c_uint32),
+                ("notConverged", C.c_uint32)]
+
+
 class Helm2Problem:
     """Keeps the arrays a BfhipHelm2Problem points to alive."""
 
@@ -519,6 +540,10 @@ def load():
     lib.bfhipBuildHelm2.restype = C.c_int
     lib.bfhipHelm2BuildLeaf.argtypes = [C.POINTER(BfhipHelm2Problem), C.c_uint64, C.c_int, vp]
     lib.bfhipHelm2BuildLeaf.restype = C.c_int
+    lib.bfhipLstSqTruncated.argtypes = [C.c_uint64, vp, vp, vp, vp, vp, C.POINTER(BfhipLstSqInfo), C.POINTER(BfhipLstSqOptions), C.c_int]
+    lib.bfhipLstSqTruncated.restype = C.c_int
+    lib.bfhipLstSqRoutes.argtypes = [C.c_uint64, vp, vp, C.POINTER(BfhipLstSqOptions), C.POINTER(BfhipLstSqRoute)]
+    lib.bfhipLstSqRoutes.restype = C.c_int
     lib.bfhipHelm2DenseApplyDevice.argtypes = [C.POINTER(BfhipHelm2Problem), C.c_int, vp, vp, vp]
     lib.bfhipHelm2DenseApplyDevice.restype = C.c_int
     lib.bfhipHelm2DenseApply.argtypes = [C.POINTER(BfhipHelm2Problem), C.c_int, vp, vp]

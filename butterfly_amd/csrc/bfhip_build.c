@@ -9,6 +9,7 @@
  * the packed arena the apply kernels read.  Nothing but the recipes and the
  * point coordinates crosses PCIe.
  */
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -151,17 +152,13 @@ typedef struct ReexpWs { uint64_t zeq, v, x, zor, t, scale, total; } ReexpWs;
 
 /* Problems with at least this many equivalent sources go through the QR preconditioner (bfQrcpKernel) before the
  * Jacobi kernel: those are the ones whose stacked matrix does not stay in LDS.  BFHIP_JACOBI_QR_MIN overrides the
- * default (0: every problem, a test hook; a huge value: none). */
-static uint32_t qrMinCols(void) {
-  char const *env = getenv("BFHIP_JACOBI_QR_MIN");
-  if (env && env[0]) return (uint32_t)strtoul(env, NULL, 10);
-  return 65;
-}
-static int usesQr(BfhipHelm2Recipe const *r, uint32_t qrMin) {
-  return r->equiv.count >= qrMin && bfdevQrcpFits(r->tgt.count, r->equiv.count);
+ * default (0: every problem, a test hook; a huge value: none); the route as a whole is bfLstSqRoute (bfhip_internal.h). */
+static uint64_t qrMinCols(void) { return (uint64_t)bfLstSqResolve(NULL).qrMin; }
+static int usesQr(BfhipHelm2Recipe const *r, uint64_t qrMin) {
+  return r->equiv.count >= qrMin && bfQrcpLds(r->tgt.count, r->equiv.count) != 0;
 }
 
-static ReexpWs reexpWs(BfhipHelm2Recipe const *r, uint32_t qrMin) {
+static ReexpWs reexpWs(BfhipHelm2Recipe const *r, uint64_t qrMin) {
   uint64_t const mt = r->tgt.count, me = r->equiv.count, n = r->src.count;
   ReexpWs w;
   w.zeq = 0;
@@ -199,7 +196,86 @@ static int batchBufsReserve(BatchBufs *b, uint64_t storeElems, uint64_t wsElems)
 }
 
 /* leaf-store and workspace elements of a batch */
-static void batchSizes(BfhipHelm2Problem const *prob, uint64_t const *idx, uint64_t count, uint32_t qrMin, uint64_t *storeElems, uint64_t *wsElems);
+static void batchSizes(BfhipHelm2Problem const *prob, uint64_t const *idx, uint64_t count, uint64_t qrMin, uint64_t *storeElems, uint64_t *wsElems);
+
+/* The truncated-SVD least-squares solve X = pinv_k(A) B of a batch of problems, on device workspace: A (mt x me) and B
+ * (mt x n) are overwritten, V (me x me), Xq (me x me: QR route only), T (me x n), scale (me doubles), out = X (me x n,
+ * ld me).  info (device [3] or NULL): sweeps, not converged, singular values kept.  One QR launch per LDS class, the Jacobi
+ * launches, two batched GEMM launches:
+ *   plain:  A V = W (orthogonal columns, norms sigma):  T = diag(1/sigma^2) W^H B,  X = V T;
+ *   QR:     A P = Q R in place, B <- Q^H B, and the Jacobi kernel gets Xq = (R[0:r] P^T)^H (me x r) instead of A:
+ *           Xq V1 = W  =>  X = W diag(1/sigma^2) V1^H (Q^H B)[0:r]  (bfhip_build.hip).
+ * qrOut (host [count] or NULL): the QR stage's rank of each problem (me when the problem skips it), with BF_QR_NONFINITE
+ * when A was not finite; routes (host [count] or NULL): the route each problem took. */
+typedef struct BfLsJob {
+  void *a, *b, *v, *xq, *t, *out;
+  double *scale;
+  uint32_t *info;
+  uint32_t mt, me, n, dim;
+} BfLsJob;
+
+static int lstsqSolve(BfLsJob const *jobs, uint64_t count, BfLstSqOpts const *opts, BfhipBuildStats *st, uint32_t *qrOut,
+                      BfLstSqRoute *routes, int profile) {
+  int rc = 0;
+  BfLstSqOpts const o = bfLstSqResolve(opts);
+  BfSvdProb *probs = malloc((count + 1) * sizeof *probs);
+  BfGemmJob *g1 = malloc((count + 1) * sizeof *g1), *g2 = malloc((count + 1) * sizeof *g2);
+  BfQrProb *qr = malloc((count + 1) * sizeof *qr);
+  uint64_t *qrOf = malloc((count + 1) * sizeof *qrOf);          /* least-squares problem of the k-th QR problem */
+  uint32_t *qrRank = malloc((count + 1) * sizeof *qrRank);
+  uint64_t nq = 0;
+  double tp = profile ? nowSeconds() : 0;
+#define BF_PHASE(name) do { if (profile) { double const t = nowSeconds(); fprintf(stderr, "[build] %-12s %.3f s\n", name, t - tp); tp = t; } } while (0)
+  if (!probs || !g1 || !g2 || !qr || !qrOf || !qrRank) { rc = bfhipFail(BFABI_ERROR_MEMORY_ERROR, "host OOM (least squares)"); goto done; }
+  for (uint64_t i = 0; i < count; ++i) {
+    BfLsJob const *J = &jobs[i];
+    memset(&probs[i], 0, sizeof probs[i]);
+    probs[i].a = J->a; probs[i].v = J->v; probs[i].scale = J->scale; probs[i].info = J->info;
+    probs[i].mt = J->mt; probs[i].me = J->me; probs[i].dim = J->dim;
+    if (qrOut) qrOut[i] = J->me;
+    if (J->me >= o.qrMin && bfQrcpLds(J->mt, J->me)) {
+      qr[nq].a = J->a; qr[nq].b = J->b; qr[nq].x = J->xq;
+      qr[nq].mt = J->mt; qr[nq].me = J->me; qr[nq].n = J->n; qr[nq].dim = J->dim;
+      qrOf[nq++] = i;
+    }
+    /* T = diag(1/sigma^2) (U Sigma)^H B */
+    memset(&g1[i], 0, sizeof g1[i]);
+    g1[i].a = J->a; g1[i].b = J->b; g1[i].c = J->t; g1[i].scale = J->scale;
+    g1[i].M = J->me; g1[i].N = J->n; g1[i].K = J->mt; g1[i].lda = J->mt; g1[i].ldb = J->mt; g1[i].ldc = J->me; g1[i].transA = 1;
+    /* X = V T */
+    memset(&g2[i], 0, sizeof g2[i]);
+    g2[i].a = J->v; g2[i].b = J->t; g2[i].c = J->out; g2[i].scale = NULL;
+    g2[i].M = J->me; g2[i].N = J->n; g2[i].K = J->me; g2[i].lda = J->me; g2[i].ldb = J->me; g2[i].ldc = J->me; g2[i].transA = 0;
+    if (routes) bfLstSqRoute(J->mt, J->me, J->me, &o, &routes[i]);
+  }
+  if ((rc = bfdevBuildQrcp(qr, nq, qrRank))) goto done;
+  BF_PHASE("qr");
+  for (uint64_t k = 0; k < nq; ++k) {
+    uint64_t const q = qrOf[k];
+    uint32_t const me = qr[k].me, nonFinite = qrRank[k] & BF_QR_NONFINITE, rk = nonFinite ? 0 : qrRank[k];
+    probs[q].a = qr[k].x; probs[q].mt = me; probs[q].me = rk;                     /* V1: rk x rk in the v block */
+    g1[q].a = probs[q].v; g1[q].M = rk; g1[q].K = rk; g1[q].lda = rk;             /* T[0:rk] = diag(1/sigma^2) V1^H (Q^H B)[0:rk] */
+    g2[q].a = qr[k].x; g2[q].K = rk; g2[q].lda = me;                              /* X = W T[0:rk] */
+    if (qrOut) qrOut[q] = qrRank[k];
+    if (routes) bfLstSqRoute(jobs[q].mt, me, rk, &o, &routes[q]);
+    st->qrProblems += 1; st->qrColumns += me; st->qrRank += rk;
+    /* a matrix that is not finite has no answer: counted like an SVD that did not converge (the build then fails unless
+     * BFHIP_ALLOW_UNCONVERGED_SVD=1); rank 0 of a finite matrix (zero, or below the threshold together) is the reference's
+     * answer X = 0.  With K = 0 the second GEMM writes an exactly zero leaf instead of leaving what the reused store held. */
+    if (nonFinite) st->notConverged += 1;
+  }
+  BfSvdStats ss = {st->maxSweeps, 0, 0, 0};
+  if ((rc = bfdevBuildJacobi(probs, count, &o, &ss))) goto done;
+  st->maxSweeps = ss.maxSweeps; st->notConverged += ss.notConverged; st->truncated += ss.truncated; st->sumSweeps += ss.sumSweeps;
+  BF_PHASE("jacobi");
+  if ((rc = bfdevBuildGemm(g1, count))) goto done;
+  if ((rc = bfdevBuildGemm(g2, count))) goto done;
+  BF_PHASE("gemm");
+#undef BF_PHASE
+done:
+  free(probs); free(g1); free(g2); free(qr); free(qrOf); free(qrRank);
+  return rc;
+}
 
 /* Compute recipes idx[0..count) on the current device.  *dStore receives a
  * device buffer holding the leaves column-major at storeOff[i] (elements). */
@@ -212,14 +288,9 @@ static int buildBatch(BfhipHelm2Problem const *prob, uint64_t const *idx, uint64
   uint64_t *wsOff = malloc((count + 1) * sizeof *wsOff);
   BfEvalMat *mats = malloc(2 * count * sizeof *mats);
   uint64_t *prefix = malloc((2 * count + 1) * sizeof *prefix);
-  BfSvdProb *probs = malloc((count + 1) * sizeof *probs);
-  BfGemmJob *g1 = malloc((count + 1) * sizeof *g1), *g2 = malloc((count + 1) * sizeof *g2);
-  BfQrProb *qr = malloc((count + 1) * sizeof *qr);
-  uint64_t *qrOf = malloc((count + 1) * sizeof *qrOf);          /* least-squares problem of the k-th QR problem */
-  uint32_t *qrRank = malloc((count + 1) * sizeof *qrRank);
-  uint32_t const qrMin = qrMinCols();
-  uint64_t nq = 0;
-  if (!wsOff || !mats || !prefix || !probs || !g1 || !g2 || !qr || !qrOf || !qrRank) {
+  BfLsJob *jobs = malloc((count + 1) * sizeof *jobs);
+  uint64_t const qrMin = qrMinCols();
+  if (!wsOff || !mats || !prefix || !jobs) {
     rc = bfhipFail(BFABI_ERROR_MEMORY_ERROR, "host OOM (builder batch)");
     goto done;
   }
@@ -260,64 +331,28 @@ static int buildBatch(BfhipHelm2Problem const *prob, uint64_t const *idx, uint64
     mats[nm].pot = proxyPot; mats[nm].decorate = 1;
     prefix[nm + 1] = prefix[nm] + ((uint64_t)mt * n + BF_EVAL_TILE - 1) / BF_EVAL_TILE;
     ++nm;
-    probs[np].a = base + w.zeq * 16; probs[np].v = base + w.v * 16; probs[np].scale = (double *)(base + w.scale * 16);
-    probs[np].mt = mt; probs[np].me = me; probs[np].dim = mt > me ? mt : me; probs[np].pad = 0;
-    if (usesQr(r, qrMin)) {
-      qr[nq].a = probs[np].a; qr[nq].b = base + w.zor * 16; qr[nq].x = base + w.x * 16;
-      qr[nq].mt = mt; qr[nq].me = me; qr[nq].n = n; qr[nq].dim = probs[np].dim;
-      qrOf[nq++] = np;
-    }
-    /* T = diag(1/sigma^2) (U Sigma)^H Z_orig */
-    memset(&g1[np], 0, sizeof g1[np]);
-    g1[np].a = probs[np].a; g1[np].b = base + w.zor * 16; g1[np].c = base + w.t * 16; g1[np].scale = probs[np].scale;
-    g1[np].M = me; g1[np].N = n; g1[np].K = mt; g1[np].lda = mt; g1[np].ldb = mt; g1[np].ldc = me; g1[np].transA = 1;
-    /* X = V T */
-    memset(&g2[np], 0, sizeof g2[np]);
-    g2[np].a = probs[np].v; g2[np].b = base + w.t * 16; g2[np].c = store + storeOff[i] * 16; g2[np].scale = NULL;
-    g2[np].M = me; g2[np].N = n; g2[np].K = me; g2[np].lda = me; g2[np].ldb = me; g2[np].ldc = me; g2[np].transA = 0;
-    ++np;
+    BfLsJob *J = &jobs[np++];
+    J->a = base + w.zeq * 16; J->b = base + w.zor * 16; J->v = base + w.v * 16; J->xq = base + w.x * 16; J->t = base + w.t * 16;
+    J->out = store + storeOff[i] * 16; J->scale = (double *)(base + w.scale * 16); J->info = NULL;
+    J->mt = mt; J->me = me; J->n = n; J->dim = mt > me ? mt : me;
     st->reexpLeaves += 1;
     st->kernelEvals += (uint64_t)mt * me + (uint64_t)mt * n;
   }
   char const *penv = getenv("BFHIP_JACOBI_PROFILE");
   int const profile = penv && penv[0] == '1';
-  double tp = tAlloc;
-#define BF_PHASE(name) do { if (profile) { double const t = nowSeconds(); fprintf(stderr, "[build] %-12s %.3f s\n", name, t - tp); tp = t; } } while (0)
-  BF_PHASE("alloc + lists");
+  if (profile) fprintf(stderr, "[build] %-12s %.3f s\n", "alloc + lists", nowSeconds() - tAlloc);
+  double const tEval = nowSeconds();
   if ((rc = bfdevBuildEval(mats, prefix, nm, env))) goto done;
-  BF_PHASE("kernel eval");
-  /* QR-preconditioned problems: A P = Q R in place, Z_orig <- Q^H Z_orig, and the Jacobi kernel gets X = (R[0:r] P^T)^H
-   * (me x r) instead of A:  X V1 = W  =>  pinv(A) Z_orig = W diag(1/sigma^2) V1^H (Q^H Z_orig)[0:r]  (bfhip_build.hip) */
-  if ((rc = bfdevBuildQrcp(qr, nq, qrRank))) goto done;
-  BF_PHASE("qr");
-  for (uint64_t k = 0; k < nq; ++k) {
-    uint64_t const q = qrOf[k];
-    uint32_t const me = qr[k].me, rk = qrRank[k];
-    probs[q].a = qr[k].x; probs[q].mt = me; probs[q].me = rk;                     /* V1: rk x rk in the v block */
-    g1[q].a = probs[q].v; g1[q].M = rk; g1[q].K = rk; g1[q].lda = rk;             /* T[0:rk] = diag(1/sigma^2) V1^H (Q^H Z_orig)[0:rk] */
-    g2[q].a = qr[k].x; g2[q].K = rk; g2[q].lda = me;                              /* X = W T[0:rk] */
-    st->qrProblems += 1; st->qrColumns += me; st->qrRank += rk;
-    /* rank 0: the matrix is zero or not finite (the pivot loop stops on `!(best >= threshold)`) -- nothing for the Jacobi kernel to flag.
-     * Count it like an SVD that did not converge (the build then fails unless BFHIP_ALLOW_UNCONVERGED_SVD=1); with K = 0 the second
-     * GEMM writes an exactly zero leaf instead of leaving what the reused store held from the batch before. */
-    if (!rk) st->notConverged += 1;
-  }
-  BfSvdStats ss = {st->maxSweeps, 0, 0, 0};
-  if ((rc = bfdevBuildJacobi(probs, np, &ss))) goto done;
-  st->maxSweeps = ss.maxSweeps; st->notConverged += ss.notConverged; st->truncated += ss.truncated; st->sumSweeps += ss.sumSweeps;
-  BF_PHASE("jacobi");
-  if ((rc = bfdevBuildGemm(g1, np))) goto done;
-  if ((rc = bfdevBuildGemm(g2, np))) goto done;
-  BF_PHASE("gemm");
-#undef BF_PHASE
+  if (profile) fprintf(stderr, "[build] %-12s %.3f s\n", "kernel eval", nowSeconds() - tEval);
+  if ((rc = lstsqSolve(jobs, np, NULL, st, NULL, NULL, profile))) goto done;
   st->numBatches += 1;
 done:
   if (rc) *dStore = NULL;
-  free(wsOff); free(mats); free(prefix); free(probs); free(g1); free(g2); free(qr); free(qrOf); free(qrRank);
+  free(wsOff); free(mats); free(prefix); free(jobs);
   return rc;
 }
 
-static void batchSizes(BfhipHelm2Problem const *prob, uint64_t const *idx, uint64_t count, uint32_t qrMin, uint64_t *storeElems, uint64_t *wsElems) {
+static void batchSizes(BfhipHelm2Problem const *prob, uint64_t const *idx, uint64_t count, uint64_t qrMin, uint64_t *storeElems, uint64_t *wsElems) {
   uint64_t se = 0, we = 0;
   for (uint64_t i = 0; i < count; ++i) {
     BfhipHelm2Recipe const *r = &prob->recipes[idx[i]];
@@ -586,5 +621,129 @@ int bfhipHelm2DenseApply(BfhipHelm2Problem const *prob, int device, void const *
   if (!rc) rc = bfdevMemcpyD2H(Y, dY, (size_t)m * 16);
   bfdevFree(dX); bfdevFree(dY);
   if (prev >= 0) bfdevSetDevice(prev);
+  return rc;
+}
+
+/* ---- the least-squares solve on caller matrices (include/bfhip_build.h) ---- */
+static BfLstSqOpts lstsqOpts(BfhipLstSqOptions const *opts) {
+  BfLstSqOpts o = {-1, -1, -1};
+  if (opts) { o.qrMin = opts->qrMin; o.gramMin = opts->gramMin; o.forceGlobal = opts->forceGlobal; }
+  return bfLstSqResolve(&o);
+}
+
+static void publicRoute(BfLstSqRoute const *r, BfhipLstSqRoute *p) {
+  p->qr = r->qr; p->qrLdsClass = r->qrLdsClass; p->qrStreaming = r->qrStreaming; p->jacobi = r->jacobi;
+  p->w = r->w; p->threads = r->threads; p->ldsClass = r->ldsClass; p->resident = r->resident;
+}
+
+static int checkLstSq(uint64_t count, uint32_t const *shapes, BfhipLstSqOptions const *opts) {
+  if (count && !shapes) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL shapes");
+  if (opts && opts->structSize < sizeof(BfhipLstSqOptions)) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "BfhipLstSqOptions.structSize too small");
+  for (uint64_t i = 0; i < count; ++i)
+    if (!shapes[3 * i] || !shapes[3 * i + 1] || !shapes[3 * i + 2])
+      return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "least-squares problem %llu: empty shape %u x %u, %u right-hand sides", (unsigned long long)i,
+                       shapes[3 * i], shapes[3 * i + 1], shapes[3 * i + 2]);
+  return 0;
+}
+
+int bfhipLstSqRoutes(uint64_t count, uint32_t const *shapes, uint32_t const *ranks, BfhipLstSqOptions const *opts, BfhipLstSqRoute *routes) {
+  int rc = checkLstSq(count, shapes, opts);
+  if (rc) return rc;
+  if (count && !routes) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL routes");
+  BfLstSqOpts const o = lstsqOpts(opts);
+  for (uint64_t i = 0; i < count; ++i) {
+    uint32_t const mt = shapes[3 * i], me = shapes[3 * i + 1];
+    BfLstSqRoute r;
+    bfLstSqRoute(mt, me, ranks ? (ranks[i] < me ? ranks[i] : me) : me, &o, &r);
+    publicRoute(&r, &routes[i]);
+  }
+  return 0;
+}
+
+static int allFinite(double const *v, uint64_t count) {
+  for (uint64_t i = 0; i < count; ++i)
+    if (!isfinite(v[i])) return 0;
+  return 1;
+}
+
+static int cmpDescending(void const *pa, void const *pb) {
+  double const a = *(double const *)pa, b = *(double const *)pb;
+  return a > b ? -1 : a < b ? 1 : 0;
+}
+
+int bfhipLstSqTruncated(uint64_t count, uint32_t const *shapes, void const *A, void const *B, void *X, double *sigma, BfhipLstSqInfo *info,
+                        BfhipLstSqOptions const *opts, int device) {
+  int rc = checkLstSq(count, shapes, opts);
+  if (rc) return rc;
+  if (!count) return 0;
+  if (!A || !B || !X) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL A / B / X");
+  BfLstSqOpts const o = lstsqOpts(opts);
+  /* element offsets of every problem's blocks (complex elements; scale and info in their own units) */
+  uint64_t *off = calloc(8 * (count + 1), sizeof *off);
+  BfLsJob *jobs = malloc(count * sizeof *jobs);
+  uint32_t *qrOut = malloc(count * sizeof *qrOut);
+  BfLstSqRoute *routes = malloc(count * sizeof *routes);
+  uint32_t *hInfo = malloc(3 * count * sizeof *hInfo);
+  if (!off || !jobs || !qrOut || !routes || !hInfo) {
+    free(off); free(jobs); free(qrOut); free(routes); free(hInfo);
+    return bfhipFail(BFABI_ERROR_MEMORY_ERROR, "host OOM (least squares)");
+  }
+  enum { OA, OB, OX, OV, OQ, OT, OS, OI };
+  for (uint64_t i = 0; i < count; ++i) {
+    uint64_t const mt = shapes[3 * i], me = shapes[3 * i + 1], n = shapes[3 * i + 2];
+    uint64_t *c = off + 8 * i, *nx = off + 8 * (i + 1);
+    nx[OA] = c[OA] + mt * me; nx[OB] = c[OB] + mt * n; nx[OX] = c[OX] + me * n; nx[OV] = c[OV] + me * me;
+    nx[OQ] = c[OQ] + ((int64_t)me >= o.qrMin && bfQrcpLds((uint32_t)mt, (uint32_t)me) ? me * me : 0);
+    nx[OT] = c[OT] + me * n; nx[OS] = c[OS] + me; nx[OI] = c[OI] + 3;
+  }
+  uint64_t const *tot = off + 8 * count;
+  void *dA = NULL, *dB = NULL, *dX = NULL, *dV = NULL, *dQ = NULL, *dT = NULL, *dS = NULL, *dI = NULL;
+  int prev = -1;
+  bfdevGetDevice(&prev);
+  if ((rc = bfdevSetDevice(device))) goto done;
+  if ((rc = bfdevMalloc(&dA, tot[OA] * 16)) || (rc = bfdevMalloc(&dB, tot[OB] * 16)) || (rc = bfdevMalloc(&dX, tot[OX] * 16)) ||
+      (rc = bfdevMalloc(&dV, tot[OV] * 16)) || (rc = bfdevMalloc(&dQ, (tot[OQ] ? tot[OQ] : 1) * 16)) || (rc = bfdevMalloc(&dT, tot[OT] * 16)) ||
+      (rc = bfdevMalloc(&dS, tot[OS] * 8)) || (rc = bfdevMalloc(&dI, tot[OI] * 4)))
+    goto done;
+  if ((rc = bfdevMemcpyH2D(dA, A, tot[OA] * 16)) || (rc = bfdevMemcpyH2D(dB, B, tot[OB] * 16)) || (rc = bfdevMemset(dI, 0, tot[OI] * 4)) ||
+      (rc = bfdevMemset(dS, 0, tot[OS] * 8)))
+    goto done;
+  for (uint64_t i = 0; i < count; ++i) {
+    uint64_t const *c = off + 8 * i;
+    BfLsJob *J = &jobs[i];
+    J->a = (char *)dA + c[OA] * 16; J->b = (char *)dB + c[OB] * 16; J->out = (char *)dX + c[OX] * 16; J->v = (char *)dV + c[OV] * 16;
+    J->xq = (char *)dQ + c[OQ] * 16; J->t = (char *)dT + c[OT] * 16; J->scale = (double *)dS + c[OS]; J->info = (uint32_t *)dI + c[OI];
+    J->mt = shapes[3 * i]; J->me = shapes[3 * i + 1]; J->n = shapes[3 * i + 2]; J->dim = J->mt > J->me ? J->mt : J->me;
+  }
+  BfhipBuildStats st;
+  memset(&st, 0, sizeof st);
+  if ((rc = lstsqSolve(jobs, count, &o, &st, qrOut, routes, 0))) goto done;
+  if ((rc = bfdevMemcpyD2H(X, dX, tot[OX] * 16)) || (rc = bfdevMemcpyD2H(hInfo, dI, tot[OI] * 4))) goto done;
+  if (sigma) {
+    if ((rc = bfdevMemcpyD2H(sigma, dS, tot[OS] * 8))) goto done;
+    /* scale[j] = 1 / sigma_j^2 for the kept ones, 0 else -> kept sigma, descending, zero padded */
+    for (uint64_t i = 0; i < count; ++i) {
+      double *sg = sigma + off[8 * i + OS];
+      uint32_t const me = shapes[3 * i + 1];
+      for (uint32_t j = 0; j < me; ++j) sg[j] = sg[j] > 0.0 ? sqrt(1.0 / sg[j]) : 0.0;
+      qsort(sg, me, sizeof *sg, cmpDescending);
+    }
+  }
+  if (info) {
+    double const *b = B;
+    for (uint64_t i = 0; i < count; ++i) {
+      BfhipLstSqInfo *f = &info[i];
+      uint32_t const *h = hInfo + 3 * i;
+      publicRoute(&routes[i], &f->route);
+      f->sweeps = h[0]; f->rank = h[2];
+      f->qrRank = qrOut[i] & ~BF_QR_NONFINITE;
+      /* B enters only the GEMMs: a NaN there reaches X unless the rank is 0, so it is looked for here */
+      f->notConverged = h[1] || (qrOut[i] & BF_QR_NONFINITE) || !allFinite(b + 2 * off[8 * i + OB], 2 * (off[8 * (i + 1) + OB] - off[8 * i + OB]));
+    }
+  }
+done:
+  bfdevFree(dA); bfdevFree(dB); bfdevFree(dX); bfdevFree(dV); bfdevFree(dQ); bfdevFree(dT); bfdevFree(dS); bfdevFree(dI);
+  if (prev >= 0) bfdevSetDevice(prev);
+  free(off); free(jobs); free(qrOut); free(routes); free(hInfo);
   return rc;
 }

@@ -232,7 +232,6 @@ int bfdevBuildEval(BfEvalMat const *hostMats, uint64_t const *hostTilePrefix, ui
 // and never leaves LDS until it has converged.
 // ---------------------------------------------------------------------------
 #define BF_JACOBI_MAX_SWEEPS 40
-#define BF_JACOBI_LDS_MAX (144u << 10)
 
 template <int W> __device__ __forceinline__ double bfGroupSum(double v) {
 #pragma unroll
@@ -263,12 +262,16 @@ __device__ void bfJacobiFinish(BfSvdProb const &P, BfSvdStats *stats, int sweep,
     if (l == 0) P.scale[j] = s2;
   }
   __syncthreads();
+  // a NaN or an infinity anywhere in A ends in a column norm that is not finite (a rotation carries it along, a frozen
+  // column keeps it): such a problem has no answer and counts as not converged, whatever the sweeps said
   if (tid == 0) {
     double mx = 0;
-    for (uint32_t j = 0; j < me; ++j) mx = fmax(mx, P.scale[j]);
-    *sigMaxShared = sqrt(mx);
+    bool finite = true;
+    for (uint32_t j = 0; j < me; ++j) { mx = fmax(mx, P.scale[j]); finite = finite && isfinite(P.scale[j]); }
+    *sigMaxShared = finite ? sqrt(mx) : -1.0;
   }
   __syncthreads();
+  if (*sigMaxShared < 0.0) converged = false;
   double const eps = 2.220446049250313e-16;
   double const tol = (double)P.dim * eps * *sigMaxShared + eps;
   unsigned long long dropped = 0;
@@ -284,6 +287,39 @@ __device__ void bfJacobiFinish(BfSvdProb const &P, BfSvdStats *stats, int sweep,
     atomicMax(&stats->maxSweeps, (unsigned long long)(sweep + (converged ? 1 : 0)));
     atomicAdd(&stats->sumSweeps, (unsigned long long)(sweep + (converged ? 1 : 0)));
     if (!converged) atomicAdd(&stats->notConverged, 1ull);
+  }
+  if (P.info) {
+    __syncthreads();
+    if (tid == 0) {
+      uint32_t kept = 0;
+      for (uint32_t j = 0; j < me; ++j) kept += P.scale[j] != 0.0;
+      P.info[0] = (uint32_t)(sweep + (converged ? 1 : 0)); P.info[1] = converged ? 0u : 1u; P.info[2] = kept;
+    }
+  }
+}
+
+// The columns a sweep leaves alone.  A column below the threshold (dead2, squared) is noise, but many of them together can
+// carry a singular value well above it: only a set whose squared norms SUM to less than dead2 may be frozen -- the
+// Frobenius norm of what is then dropped bounds its 2-norm.  Every column below the threshold when their sum allows it
+// (rotations of a pair one of whose columns fell below it during the sweep are then skipped as well: *angleDead2 = dead2);
+// else, in column order, those that still fit under the sum, and no pair of live columns is skipped for its norms
+// (*angleDead2 = 0).  frozen(j) is written for every j < me.  Thread 0 only.
+template <typename F>
+__device__ void bfJacobiFreeze(double const *s2, uint32_t me, double dead2, double *angleDead2, F frozen) {
+  double small = 0;
+  for (uint32_t j = 0; j < me; ++j)
+    if (s2[j] < dead2) small += s2[j];
+  if (small < dead2) {
+    *angleDead2 = dead2;
+    for (uint32_t j = 0; j < me; ++j) frozen(j, !(s2[j] >= dead2));
+    return;
+  }
+  *angleDead2 = 0.0;
+  double acc = 0;
+  for (uint32_t j = 0; j < me; ++j) {
+    bool const f = s2[j] < dead2 && acc + s2[j] < dead2;
+    if (f) acc += s2[j];
+    frozen(j, f);
   }
 }
 
@@ -321,8 +357,6 @@ __device__ __forceinline__ bool bfJacobiAngle(double alpha, double beta, double 
   return true;
 }
 
-#define BF_JACOBI_MAX_COLS 2304          /* 2 (rows + cols) 16 B <= the LDS tile  =>  cols <= 2300 */
-
 template <int W>
 __global__ __launch_bounds__(1024) void bfJacobiKernel(BfSvdProb const *probs, uint32_t const *list, BfSvdStats *stats, uint32_t ldsBytes) {
   extern __shared__ __attribute__((aligned(16))) unsigned char bfJacobiLds[];
@@ -331,7 +365,8 @@ __global__ __launch_bounds__(1024) void bfJacobiKernel(BfSvdProb const *probs, u
   __shared__ double sigMax;
   __shared__ unsigned long long maxNormBits;
   __shared__ uint32_t numLive;
-  __shared__ uint16_t live[BF_JACOBI_MAX_COLS];     // the columns still above the threshold, in column order
+  __shared__ double angleDead2;
+  __shared__ uint16_t live[BF_JACOBI_MAX_COLS];     // the columns a sweep rotates (bfJacobiFreeze), in column order
   BfSvdProb const P = probs[list[blockIdx.x]];
   uint32_t const mt = P.mt, me = P.me;
   if (me == 0) return;                              // rank 0 after the QR preconditioner: nothing to orthogonalise
@@ -392,7 +427,7 @@ __global__ __launch_bounds__(1024) void bfJacobiKernel(BfSvdProb const *probs, u
     alpha = bfGroupSum<W>(alpha); beta = bfGroupSum<W>(beta);
     gr = bfGroupSum<W>(gr); gi = bfGroupSum<W>(gi);
     double c, sn, er, ei;
-    if (!bfJacobiAngle(alpha, beta, gr, gi, tol2, dead2, c, sn, er, ei)) return;
+    if (!bfJacobiAngle(alpha, beta, gr, gi, tol2, angleDead2, c, sn, er, ei)) return;
     for (uint32_t r = l; r < R; r += W) {
       double2 const x = sp[r], y = sq[r];
       double2 const yt = make_double2(er * y.x - ei * y.y, er * y.y + ei * y.x);
@@ -426,8 +461,7 @@ __global__ __launch_bounds__(1024) void bfJacobiKernel(BfSvdProb const *probs, u
     __syncthreads();
     if (tid == 0) {
       uint32_t n = 0;
-      for (uint32_t j = 0; j < me; ++j)
-        if (P.scale[j] >= dead2) live[n++] = (uint16_t)j;
+      bfJacobiFreeze(P.scale, me, dead2, &angleDead2, [&](uint32_t j, bool f) { if (!f) live[n++] = (uint16_t)j; });
       numLive = n;
       rotated = 0;
     }
@@ -508,7 +542,6 @@ __global__ __launch_bounds__(1024) void bfJacobiKernel(BfSvdProb const *probs, u
 #define BF_GRAM_THREADS 512
 #define BF_GRAM_RC 32
 #define BF_GRAM_LD 33
-#define BF_GRAM_MAX_COLS 4096
 #define BF_GRAM_NONE 0xffffu
 #define BF_GRAM_INNER 1                  /* sweeps of the inner solve per visit of a block pair (2: 10.2 instead of 10.5 outer sweeps on
                                           * average, but the solve -- then by one wavefront -- was half of a visit's time: 4.66 against 3.76 s per batch) */
@@ -525,6 +558,7 @@ __global__ __launch_bounds__(BF_GRAM_THREADS) void bfJacobiGramKernel(BfSvdProb 
   __shared__ double sigMax;
   __shared__ unsigned long long maxNormBits;
   __shared__ uint32_t numLive;
+  __shared__ double angleDead2;
   BfSvdProb const P = probs[list[blockIdx.x]];
   uint32_t const mt = P.mt, me = P.me;
   if (me == 0) return;
@@ -549,8 +583,7 @@ __global__ __launch_bounds__(BF_GRAM_THREADS) void bfJacobiGramKernel(BfSvdProb 
     __syncthreads();
     if (tid == 0) {
       uint32_t n = 0;
-      for (uint32_t j = 0; j < me; ++j)
-        if (P.scale[j] >= dead2) live[n++] = (uint16_t)j;
+      bfJacobiFreeze(P.scale, me, dead2, &angleDead2, [&](uint32_t j, bool f) { if (!f) live[n++] = (uint16_t)j; });
       numLive = n;
       rotated = 0;
     }
@@ -636,7 +669,7 @@ __global__ __launch_bounds__(BF_GRAM_THREADS) void bfJacobiGramKernel(BfSvdProb 
               if (worker) {
                 bfRoundRobin(BF_GRAM_P, s, kk, p, q);
                 double2 const gpq = G[p * BF_GRAM_LD + q];
-                rot = bfJacobiAngle(G[p * BF_GRAM_LD + p].x, G[q * BF_GRAM_LD + q].x, gpq.x, gpq.y, tol2, dead2, c, sn, er, ei);
+                rot = bfJacobiAngle(G[p * BF_GRAM_LD + p].x, G[q * BF_GRAM_LD + q].x, gpq.x, gpq.y, tol2, angleDead2, c, sn, er, ei);
               }
               __syncthreads();                                       // every rotation of the step has read its inputs
               if (rot) {
@@ -719,6 +752,7 @@ __global__ __launch_bounds__(1024) void bfJacobiGlobalKernel(BfSvdProb const *pr
   __shared__ int rotated;
   __shared__ double sigMax;
   __shared__ unsigned long long maxNormBits;
+  __shared__ double angleDead2;
   BfSvdProb const P = probs[list[blockIdx.x]];
   uint32_t const mt = P.mt, me = P.me;
   double2 *A = (double2 *)P.a, *V = (double2 *)P.v;
@@ -733,13 +767,26 @@ __global__ __launch_bounds__(1024) void bfJacobiGlobalKernel(BfSvdProb const *pr
   bool converged = false;
   __syncthreads();
   for (; sweep < BF_JACOBI_MAX_SWEEPS; ++sweep) {
-    if (tid == 0) rotated = 0;
+    // the frozen columns of this sweep: P.scale[j] < 0 (scratch until bfJacobiFinish)
+    for (uint32_t j = g; j < me; j += groups) {
+      double2 const *aj = A + (uint64_t)j * mt;
+      double s2 = 0;
+      for (uint32_t r = l; r < mt; r += W) { double2 const a = aj[r]; s2 = fma(a.x, a.x, fma(a.y, a.y, s2)); }
+      s2 = bfGroupSum<W>(s2);
+      if (l == 0) P.scale[j] = s2;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      rotated = 0;
+      bfJacobiFreeze(P.scale, me, dead2, &angleDead2, [&](uint32_t j, bool f) { if (f) P.scale[j] = -1.0; });
+    }
     __syncthreads();
     for (uint32_t s = 0; s + 1 < M; ++s) {
       for (uint32_t kk = g; kk < M / 2; kk += groups) {
         uint32_t p, q;
         bfRoundRobin(M, s, kk, p, q);
         if (q >= me) continue;                       // the dummy column of an odd me
+        if (P.scale[p] < 0.0 || P.scale[q] < 0.0) continue;
         double2 *ap = A + (uint64_t)p * mt, *aq = A + (uint64_t)q * mt;
         double alpha = 0, beta = 0, gr = 0, gi = 0;
         for (uint32_t r = l; r < mt; r += W) {
@@ -752,7 +799,7 @@ __global__ __launch_bounds__(1024) void bfJacobiGlobalKernel(BfSvdProb const *pr
         alpha = bfGroupSum<W>(alpha); beta = bfGroupSum<W>(beta);
         gr = bfGroupSum<W>(gr); gi = bfGroupSum<W>(gi);
         double c, sn, er, ei;
-        if (!bfJacobiAngle(alpha, beta, gr, gi, tol2, dead2, c, sn, er, ei)) continue;
+        if (!bfJacobiAngle(alpha, beta, gr, gi, tol2, angleDead2, c, sn, er, ei)) continue;
         double2 *vp = V + (uint64_t)p * me, *vq = V + (uint64_t)q * me;
         for (uint32_t r = l; r < mt + me; r += W) {
           double2 *xp = r < mt ? ap + r : vp + (r - mt), *yp = r < mt ? aq + r : vq + (r - mt);
@@ -775,8 +822,8 @@ __global__ __launch_bounds__(1024) void bfJacobiGlobalKernel(BfSvdProb const *pr
 // ---------------------------------------------------------------------------
 // Preconditioner of the Jacobi SVD for the problems that do not fit LDS (Drmac & Veselic's
 // scheme, first stage): Householder QR with column pivoting  A P = Q R,  stopped at the first step
-// whose largest remaining column is below the threshold under which the Jacobi kernel never
-// rotates a column (r steps).  The right-hand side B rides along as extra, never pivoted
+// whose trailing columns together (their squared norms summed) are below the threshold under which the Jacobi
+// kernel freezes columns (r steps): the Frobenius norm of the trailing block bounds the 2-norm of what is dropped.  The right-hand side B rides along as extra, never pivoted
 // columns and leaves as Q^H B.  What the Jacobi kernel then orthogonalises is
 //   X = (R[0:r, :] P^T)^H      (me x r, rows in the ORIGINAL column order of A),
 // whose columns are already graded and few: X V1 = W (orthogonal columns, norms sigma)  gives
@@ -795,39 +842,46 @@ __global__ __launch_bounds__(512) void bfQrcpKernel(BfQrProb const *probs, uint3
   double2 *u = (double2 *)bfQrLds;                       // [mt]
   double *cn = (double *)(u + mt);                       // [me] squared norms of rows j.. of the columns
   uint32_t *perm = (uint32_t *)(cn + me);                // [me]
-  __shared__ double redVal[16];
+  __shared__ double redVal[16], redSum[16];
   __shared__ uint32_t redIdx[16];
-  __shared__ double sCoef, sDead2;
+  __shared__ double sCoef, sDead2, sTotal;
+  __shared__ int sNonFinite;
   __shared__ uint32_t sPivot;
   uint32_t const nthreads = blockDim.x, tid = threadIdx.x;
   uint32_t const groups = nthreads / W, g = tid / W, l = tid % W;
 
-  // largest cn[c], c >= from (lowest index among equals) -> sPivot; every thread gets the value
+  // largest cn[c], c >= from (lowest index among equals) -> sPivot; every thread gets the value.  The sum of those cn[c]
+  // -> sTotal (fixed order: lane strides, a butterfly, the groups in turn)
   auto argmax = [&](uint32_t from) -> double {
-    double bv = -1.0; uint32_t bi = 0xffffffffu;
-    for (uint32_t c = from + tid; c < me; c += nthreads) { double const v = cn[c]; if (v > bv) { bv = v; bi = c; } }
+    double bv = -1.0, sum = 0.0; uint32_t bi = 0xffffffffu;
+    for (uint32_t c = from + tid; c < me; c += nthreads) { double const v = cn[c]; sum += v; if (v > bv) { bv = v; bi = c; } }
 #pragma unroll
     for (int m = 1; m < W; m <<= 1) {
       double const ov = __shfl_xor(bv, m, W); uint32_t const oi = __shfl_xor(bi, m, W);
       if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
     }
-    if (l == 0) { redVal[g] = bv; redIdx[g] = bi; }
+    sum = bfGroupSum<W>(sum);
+    if (l == 0) { redVal[g] = bv; redIdx[g] = bi; redSum[g] = sum; }
     __syncthreads();
     if (tid == 0) {
-      for (uint32_t k = 1; k < groups; ++k)
+      for (uint32_t k = 1; k < groups; ++k) {
         if (redVal[k] > bv || (redVal[k] == bv && redIdx[k] < bi)) { bv = redVal[k]; bi = redIdx[k]; }
-      redVal[0] = bv; sPivot = bi;
+        sum += redSum[k];
+      }
+      redVal[0] = bv; sPivot = bi; sTotal = sum;
     }
     __syncthreads();
     return redVal[0];
   };
 
+  if (tid == 0) sNonFinite = 0;
+  __syncthreads();
   for (uint32_t c = g; c < me; c += groups) {
     double2 const *ac = A + (uint64_t)c * mt;
     double s2 = 0;
     for (uint32_t r = l; r < mt; r += W) { double2 const a = ac[r]; s2 = fma(a.x, a.x, fma(a.y, a.y, s2)); }
     s2 = bfGroupSum<W>(s2);
-    if (l == 0) { cn[c] = s2; perm[c] = c; }
+    if (l == 0) { cn[c] = s2; perm[c] = c; if (!isfinite(s2)) sNonFinite = 1; }
   }
   __syncthreads();
   {
@@ -836,11 +890,11 @@ __global__ __launch_bounds__(512) void bfQrcpKernel(BfQrProb const *probs, uint3
     if (tid == 0) sDead2 = deadRel * deadRel * mx;
     __syncthreads();
   }
-  uint32_t const steps = mt < me ? mt : me;
+  uint32_t const steps = sNonFinite ? 0 : mt < me ? mt : me;      // not finite: nothing to factor, the problem is flagged
   uint32_t j = 0;
   for (; j < steps; ++j) {
     double const best = argmax(j);
-    if (!(best >= sDead2) || best <= 0.0) break;       // everything left is below the threshold (or not a number)
+    if (!(sTotal >= sDead2) || best <= 0.0) break;     // what is left is below the threshold together
     uint32_t const p = sPivot;
     if (p != j) {
       double2 *aj = A + (uint64_t)j * mt, *ap = A + (uint64_t)p * mt;
@@ -908,7 +962,7 @@ __global__ __launch_bounds__(512) void bfQrcpKernel(BfQrProb const *probs, uint3
     __syncthreads();
   }
   uint32_t const r = j;
-  if (tid == 0) ranks[blockIdx.x] = r;
+  if (tid == 0) ranks[blockIdx.x] = r | (sNonFinite ? BF_QR_NONFINITE : 0u);
   // X[perm[c] + i me] = conj(R[i][c]), i <= c; zero below the diagonal of R
   for (uint32_t c = g; c < me; c += groups) {
     double2 const *rc = A + (uint64_t)c * mt;
@@ -921,13 +975,7 @@ __global__ __launch_bounds__(512) void bfQrcpKernel(BfQrProb const *probs, uint3
   }
 }
 
-// LDS a problem of the QR kernel needs; 0: does not fit (the caller keeps such a problem on the plain path)
-static uint32_t qrcpLds(uint32_t mt, uint32_t me) {
-  uint64_t const need = (uint64_t)mt * 16 + (uint64_t)me * 12 + 64;
-  return need <= (150u << 10) ? (uint32_t)need : 0;
-}
-
-int bfdevQrcpFits(uint32_t mt, uint32_t me) { return qrcpLds(mt, me) != 0; }
+int bfdevQrcpFits(uint32_t mt, uint32_t me) { return bfQrcpLds(mt, me) != 0; }
 
 typedef struct QrOrder { double cost; uint32_t idx; int cls; } QrOrder;
 static int qrOrderCmp(void const *pa, void const *pb) {
@@ -940,8 +988,7 @@ static int qrOrderCmp(void const *pa, void const *pb) {
 // one launch per LDS class (several small problems then share a CU)
 int bfdevBuildQrcp(BfQrProb const *hostProbs, uint64_t numProbs, uint32_t *hostRanks) {
   if (!numProbs) return 0;
-  enum { NC = 6 };                                       /* <= 8, 16, 32, 64, 128, 150 KiB */
-  static uint32_t const cap[NC] = {8u << 10, 16u << 10, 32u << 10, 64u << 10, 128u << 10, 150u << 10};
+  enum { NC = BF_QR_LDS_CLASSES };                       /* <= 8, 16, 32, 64, 128, 150 KiB (bfLstSqRoute) */
   uint32_t *order = (uint32_t *)malloc(numProbs * sizeof(uint32_t));
   BfQrProb *sorted = (BfQrProb *)malloc(numProbs * sizeof(BfQrProb));
   uint32_t *ranks = (uint32_t *)malloc(numProbs * sizeof(uint32_t));
@@ -950,10 +997,9 @@ int bfdevBuildQrcp(BfQrProb const *hostProbs, uint64_t numProbs, uint32_t *hostR
   QrOrder *ord = (QrOrder *)malloc(numProbs * sizeof(QrOrder));
   if (!rc && !ord) rc = bfhipFail(BFABI_ERROR_MEMORY_ERROR, "host OOM");
   for (uint64_t i = 0; i < numProbs && !rc; ++i) {
-    uint32_t const need = qrcpLds(hostProbs[i].mt, hostProbs[i].me);
+    uint32_t const need = bfQrcpLds(hostProbs[i].mt, hostProbs[i].me);
     if (!need) { rc = bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "QR preconditioner: problem %llu does not fit LDS", (unsigned long long)i); break; }
-    int c = 0;
-    while (cap[c] < need) ++c;
+    int const c = (int)bfQrcpLdsClass(need);
     ord[i].cls = c; ord[i].idx = (uint32_t)i;
     ord[i].cost = (double)hostProbs[i].mt * hostProbs[i].me * (hostProbs[i].me + hostProbs[i].n);
     count[c + 1] += 1;
@@ -969,12 +1015,12 @@ int bfdevBuildQrcp(BfQrProb const *hostProbs, uint64_t numProbs, uint32_t *hostR
   uint32_t *dR = NULL;
   if (!rc) rc = uploadArrayB(&dP, sorted, numProbs, "qr problems");
   if (!rc) rc = hipFailB(hipMalloc((void **)&dR, numProbs * sizeof(uint32_t)), "qr ranks");
-  if (!rc) rc = hipFailB(hipFuncSetAttribute((void const *)bfQrcpKernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cap[NC - 1]), "hipFuncSetAttribute(QR LDS)");
+  if (!rc) rc = hipFailB(hipFuncSetAttribute((void const *)bfQrcpKernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bfQrcpLdsCap(NC - 1)), "hipFuncSetAttribute(QR LDS)");
   for (int c = NC - 1; c >= 0 && !rc; --c) {              /* the big ones first */
     uint64_t const nc = count[c + 1] - count[c];
     if (!nc) continue;
     uint32_t const threads = c >= 2 ? 512 : 256;          /* LDS class ~ rows: short columns need few lane groups */
-    hipLaunchKernelGGL(bfQrcpKernel, dim3((uint32_t)nc), dim3(threads), cap[c], 0, dP + count[c], dR + count[c]);
+    hipLaunchKernelGGL(bfQrcpKernel, dim3((uint32_t)nc), dim3(threads), bfQrcpLdsCap(c), 0, dP + count[c], dR + count[c]);
     rc = hipFailB(hipGetLastError(), "QR preconditioner launch");
   }
   if (!rc) rc = hipFailB(hipDeviceSynchronize(), "QR preconditioner");
@@ -985,32 +1031,11 @@ int bfdevBuildQrcp(BfQrProb const *hostProbs, uint64_t numProbs, uint32_t *hostR
   return rc;
 }
 
-// Launch classes.  Workgroup: 256 threads for <= 64 columns, 1024 above.  LDS: the smallest of
-// 16/32/64/144 KiB that holds the whole stacked matrix (several small problems then share a
-// CU), else 144 KiB and block sweeps.  Lane-group width W: the largest power of two that still
-// gives each of the b column pairs of an inner step its own group, at most the column length.
+// Launch classes (bfJacobiRoute, bfhip_internal.h).  Workgroup: 256 threads for <= 64 columns, 1024 above.  LDS: the
+// smallest of 16/32/64/144 KiB that holds the whole stacked matrix (several small problems then share a CU), else 144 KiB
+// and block sweeps.  Lane-group width W: the largest power of two that still gives each of the b column pairs of an inner
+// step its own group, at most the column length.
 static uint32_t const kJacobiLds[4] = {16u << 10, 32u << 10, 64u << 10, BF_JACOBI_LDS_MAX};
-
-static int jacobiClass(BfSvdProb const *p, int forceGlobal, int *wlog, int *big, int *ldsClass) {
-  uint64_t const R = (uint64_t)p->mt + p->me, Rp = R | 1u;
-  if (2 * Rp * 16 > BF_JACOBI_LDS_MAX || p->me > BF_JACOBI_MAX_COLS || forceGlobal) { *ldsClass = -1; *big = 1; *wlog = 4; return 0; }   /* global-memory fallback */
-  uint64_t const meEven = p->me + (p->me & 1u);
-  int lc = 3;
-  for (int c = 0; c < 3; ++c)
-    if (meEven * Rp * 16 <= kJacobiLds[c]) { lc = c; break; }
-  uint32_t C = (uint32_t)((kJacobiLds[lc] / 16u) / Rp);
-  C = C < 2 ? 2 : C & ~1u;
-  uint32_t const b = C / 2 < (p->me + 1) / 2 ? C / 2 : (p->me + 1) / 2;
-  *ldsClass = lc;
-  *big = p->me > 64;
-  uint32_t const threads = *big ? 1024 : 256;
-  uint32_t w = 64;
-  while (w > 4 && (threads / w < b || w / 2 >= p->mt)) w >>= 1;
-  int l = 0;
-  while ((4u << l) < w) ++l;
-  *wlog = l;                                       // W = 4 << l, l = 0..4
-  return 0;
-}
 
 template <int W> static int jacobiLaunch(uint32_t count, uint32_t threads, uint32_t lds, BfSvdProb const *dP, uint32_t const *dL, BfSvdStats *dS) {
   int rc = hipFailB(hipFuncSetAttribute((void const *)bfJacobiKernel<W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BF_JACOBI_LDS_MAX),
@@ -1027,40 +1052,38 @@ static int jacobiCostDescending(void const *pa, void const *pb) {
   return a->idx < b->idx ? -1 : 1;
 }
 
-int bfdevBuildJacobi(BfSvdProb const *hostProbs, uint64_t numProbs, BfSvdStats *stats) {
+int bfdevBuildJacobi(BfSvdProb const *hostProbs, uint64_t numProbs, BfLstSqOpts const *opts, BfSvdStats *stats) {
   if (!numProbs) return 0;
   enum { NW = 5, NL = 4, NCLS = 2 * NW * NL };
   uint32_t *lists[NCLS] = {0};
   uint64_t counts[NCLS] = {0};
   uint8_t *cls = (uint8_t *)malloc(numProbs);
   int rc = cls ? 0 : bfhipFail(BFABI_ERROR_MEMORY_ERROR, "host OOM");
-  // BFHIP_JACOBI_GLOBAL=1 sends every problem through the fallback kernel (test hook for a path that
-  // otherwise needs problems of > 2300 columns)
-  char const *env = getenv("BFHIP_JACOBI_GLOBAL");
-  int const forceGlobal = env && env[0] == '1';
+  // the route of every problem (bfJacobiRoute): the block form on Gram matrices (bfJacobiGramKernel) for rows + columns >=
+  // gramMin (512 by default: fewer than nine stacked columns of a block would fit the LDS tile; N = 262144 build with the
+  // limit at 384 / 512 / 768 / 1024: 21.5 / 22.0 / 22.0 - 23.6 / 27.5 s) and for those too long for the tile at all when they
+  // have <= 4096 columns; the global-memory fallback beyond that (or for every problem: forceGlobal, a test hook for a path
+  // that otherwise needs problems of > 2300 columns); else one launch class per (W, threads, LDS tile)
+  BfLstSqOpts const o = bfLstSqResolve(opts);
   uint32_t *globalList = (uint32_t *)malloc(numProbs * sizeof(uint32_t));
   uint64_t numGlobal = 0;
   if (!globalList) rc = bfhipFail(BFABI_ERROR_MEMORY_ERROR, "host OOM");
-  // Problems of rows + columns >= 512 (fewer than nine stacked columns of a block would fit the LDS tile) run the block form
-  // on Gram matrices (bfJacobiGramKernel), as do those too long for the tile at all when they have <= 4096 columns.
-  // (N = 262144 build with the limit at 384 / 512 / 768 / 1024: 21.5 / 22.0 / 22.0 - 23.6 / 27.5 s.)
-  // BFHIP_JACOBI_GRAM_MIN moves the limit (0: every problem -- a test hook; a huge value: none).
-  char const *genv = getenv("BFHIP_JACOBI_GRAM_MIN");
-  uint64_t const gramMin = genv && genv[0] ? strtoull(genv, NULL, 10) : 512;
   JacobiOrder *gramList = (JacobiOrder *)malloc((numProbs ? numProbs : 1) * sizeof(JacobiOrder));
   uint64_t numGram = 0;
   if (!gramList) rc = bfhipFail(BFABI_ERROR_MEMORY_ERROR, "host OOM");
   for (uint64_t i = 0; i < numProbs && !rc; ++i) {
-    int wlog, big, lc;
-    rc = jacobiClass(&hostProbs[i], forceGlobal, &wlog, &big, &lc);
-    if (!forceGlobal && hostProbs[i].me <= BF_GRAM_MAX_COLS && (lc < 0 || (uint64_t)hostProbs[i].mt + hostProbs[i].me >= gramMin)) {
+    BfLstSqRoute r;
+    bfJacobiRoute(hostProbs[i].mt, hostProbs[i].me, &o, &r);
+    if (r.jacobi == BF_JACOBI_GRAM) {
       cls[i] = 0xff;
       gramList[numGram].idx = (uint32_t)i;
       gramList[numGram++].cost = (double)hostProbs[i].me * hostProbs[i].me * (hostProbs[i].mt + hostProbs[i].me);
       continue;
     }
-    if (lc < 0) { cls[i] = 0xff; globalList[numGlobal++] = (uint32_t)i; continue; }
-    cls[i] = (uint8_t)((wlog * 2 + big) * NL + lc);
+    if (r.jacobi == BF_JACOBI_GLOBAL) { cls[i] = 0xff; globalList[numGlobal++] = (uint32_t)i; continue; }
+    int wlog = 0;
+    while ((4u << wlog) < r.w) ++wlog;                   // W = 4 << wlog, wlog = 0..4
+    cls[i] = (uint8_t)((wlog * 2 + (r.threads == 1024)) * NL + (int)r.ldsClass);
     counts[cls[i]] += 1;
   }
   for (int c = 0; c < NCLS && !rc; ++c) {

@@ -7,6 +7,7 @@
 
 #include <stddef.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include "../../include/bfhip.h"
 
 #ifdef __cplusplus
@@ -509,14 +510,97 @@ typedef struct BfSvdProb {
   uint32_t mt, me;
   uint32_t dim, pad;     /* the max(rows, cols) of the truncation rule (src/mat_dense_complex.c:1800-1812): that of the ORIGINAL
                             matrix when (a) is the QR-preconditioned one */
+  uint32_t *info;        /* device [3] or NULL: sweeps, not converged (0/1), singular values kept */
+  void *pad2;
 } BfSvdProb;
 typedef struct BfSvdStats { unsigned long long maxSweeps, notConverged, truncated, sumSweeps; } BfSvdStats;
-int bfdevBuildJacobi(BfSvdProb const *hostProbs, uint64_t numProbs, BfSvdStats *stats);
+
+/* ---- routing of a least-squares problem (host-only; bfhipLstSqRoutes reports it without a device) ----
+ * Sizes the Jacobi kernels are built for: columns of the plain kernel's live list, columns of the block (Gram) form, the
+ * largest LDS tile, and the tiles of the four LDS classes. */
+#define BF_JACOBI_MAX_COLS 2304          /* 2 (rows + cols) 16 B <= the LDS tile  =>  cols <= 2300 */
+#define BF_GRAM_MAX_COLS 4096
+#define BF_JACOBI_LDS_MAX (144u << 10)
+#define BF_QR_LDS_CLASSES 6
+enum { BF_JACOBI_PLAIN = 0, BF_JACOBI_GRAM = 1, BF_JACOBI_GLOBAL = 2 };
+/* the route's switches: < 0 takes the default (the BFHIP_JACOBI_QR_MIN / _GRAM_MIN / _GLOBAL environment hooks, else 65 /
+ * 512 / 0); qrMin: problems with at least this many columns get the QR preconditioner (0: all); gramMin: problems with
+ * rows + columns >= gramMin go to the Gram form; forceGlobal: 1 sends every Jacobi problem to the global-memory kernel */
+typedef struct BfLstSqOpts { int64_t qrMin, gramMin, forceGlobal; } BfLstSqOpts;
+typedef struct BfLstSqRoute {
+  uint32_t qr;           /* 1: bfQrcpKernel first */
+  uint32_t qrLdsClass;   /* 0..5: 8, 16, 32, 64, 128, 150 KiB */
+  uint32_t qrStreaming;  /* 1: columns longer than 1024 rows, streamed (else held in registers) */
+  uint32_t jacobi;       /* BF_JACOBI_* */
+  uint32_t w, threads;   /* plain kernel: lane-group width and workgroup size */
+  uint32_t ldsClass;     /* plain kernel: 0..3, 16, 32, 64, 144 KiB */
+  uint32_t resident;     /* plain kernel: the whole stacked matrix stays in LDS (else block sweeps) */
+} BfLstSqRoute;
+static inline int64_t bfLstSqEnvInt(char const *name, int64_t dflt) {
+  char const *e = getenv(name);
+  return e && e[0] ? (int64_t)strtoull(e, NULL, 10) : dflt;
+}
+static inline BfLstSqOpts bfLstSqResolve(BfLstSqOpts const *o) {
+  BfLstSqOpts r;
+  r.qrMin = o && o->qrMin >= 0 ? o->qrMin : bfLstSqEnvInt("BFHIP_JACOBI_QR_MIN", 65);
+  r.gramMin = o && o->gramMin >= 0 ? o->gramMin : bfLstSqEnvInt("BFHIP_JACOBI_GRAM_MIN", 512);
+  if (o && o->forceGlobal >= 0) r.forceGlobal = o->forceGlobal != 0;
+  else { char const *e = getenv("BFHIP_JACOBI_GLOBAL"); r.forceGlobal = e && e[0] == '1'; }
+  return r;
+}
+/* LDS the QR kernel needs for an mt x me problem (0: does not fit), and its class */
+static inline uint32_t bfQrcpLds(uint32_t mt, uint32_t me) {
+  uint64_t const need = (uint64_t)mt * 16 + (uint64_t)me * 12 + 64;
+  return need <= (150u << 10) ? (uint32_t)need : 0;
+}
+static inline uint32_t bfQrcpLdsCap(uint32_t cls) {
+  static uint32_t const cap[BF_QR_LDS_CLASSES] = {8u << 10, 16u << 10, 32u << 10, 64u << 10, 128u << 10, 150u << 10};
+  return cap[cls];
+}
+static inline uint32_t bfQrcpLdsClass(uint32_t need) {
+  uint32_t c = 0;
+  while (c + 1 < BF_QR_LDS_CLASSES && bfQrcpLdsCap(c) < need) ++c;
+  return c;
+}
+/* the Jacobi stage of an mt x me problem (after the QR stage: me x rank) */
+static inline void bfJacobiRoute(uint32_t mt, uint32_t me, BfLstSqOpts const *o, BfLstSqRoute *r) {
+  static uint32_t const lds[4] = {16u << 10, 32u << 10, 64u << 10, BF_JACOBI_LDS_MAX};
+  uint64_t const R = (uint64_t)mt + me, Rp = R | 1u;
+  r->w = 64; r->threads = 1024; r->ldsClass = 0; r->resident = 0;
+  int const fits = !(2 * Rp * 16 > BF_JACOBI_LDS_MAX || me > BF_JACOBI_MAX_COLS);
+  if (!o->forceGlobal && me <= BF_GRAM_MAX_COLS && (!fits || R >= (uint64_t)o->gramMin)) { r->jacobi = BF_JACOBI_GRAM; r->threads = 512; return; }
+  if (!fits || o->forceGlobal) { r->jacobi = BF_JACOBI_GLOBAL; return; }
+  r->jacobi = BF_JACOBI_PLAIN;
+  uint64_t const meEven = me + (me & 1u);
+  uint32_t lc = 3;
+  for (uint32_t c = 0; c < 3; ++c)
+    if (meEven * Rp * 16 <= lds[c]) { lc = c; break; }
+  uint32_t C = (uint32_t)((lds[lc] / 16u) / Rp);           /* stacked columns the tile holds (bfJacobiKernel) */
+  C = C < 2 ? 2 : C & ~1u;
+  uint32_t const b = C / 2 < (me + 1) / 2 ? C / 2 : (me + 1) / 2;
+  r->ldsClass = lc;
+  r->threads = me > 64 ? 1024 : 256;
+  uint32_t w = 64;
+  while (w > 4 && (r->threads / w < b || w / 2 >= mt)) w >>= 1;
+  r->w = w;
+  r->resident = b ? (me + b - 1) / b <= 2 : 1;
+}
+/* the whole route of an mt x me least-squares problem; `rank`: what the QR stage leaves for the Jacobi stage (if it runs) */
+static inline void bfLstSqRoute(uint32_t mt, uint32_t me, uint32_t rank, BfLstSqOpts const *o, BfLstSqRoute *r) {
+  uint32_t const need = bfQrcpLds(mt, me);
+  r->qr = me >= o->qrMin && need != 0;
+  r->qrLdsClass = r->qr ? bfQrcpLdsClass(need) : 0;
+  r->qrStreaming = r->qr && mt > 1024;
+  if (r->qr) bfJacobiRoute(me, rank, o, r);
+  else bfJacobiRoute(mt, me, o, r);
+}
+int bfdevBuildJacobi(BfSvdProb const *hostProbs, uint64_t numProbs, BfLstSqOpts const *opts, BfSvdStats *stats);
 
 /* QR with column pivoting ahead of the Jacobi SVD (bfQrcpKernel): a (mt x me, ld mt) is overwritten (R in its upper
  * triangle), b (mt x n, ld mt) becomes Q^H b, x (me x me workspace) receives the me x rank matrix the Jacobi kernel
- * then works on (ld me); hostRanks[i] = the number of steps taken before the largest remaining column fell below
- * dim * eps * (largest column of a). */
+ * then works on (ld me); hostRanks[i] = the number of steps taken before the trailing columns' total squared norm fell
+ * below (dim * eps)^2 x the largest squared column of a, with BF_QR_NONFINITE set when a holds a NaN or an infinity. */
+#define BF_QR_NONFINITE 0x80000000u
 typedef struct BfQrProb {
   void *a, *b, *x;
   uint32_t mt, me, n, dim;

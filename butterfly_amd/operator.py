@@ -547,3 +547,60 @@ def helm2_dense_apply(points, wavenumber, x, device=-1, **problem):
     check(lib.bfhipHelm2DenseApplyDevice(prob.byref(), x.device.index, C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()),
                                          C.c_void_p(s.cuda_stream)))
     return y
+
+
+def _lstsq_options(qr_min=None, gram_min=None, force_global=None):
+    o = _capi.BfhipLstSqOptions()
+    o.structSize = C.sizeof(_capi.BfhipLstSqOptions)
+    o.qrMin = -1 if qr_min is None else int(qr_min)
+    o.gramMin = -1 if gram_min is None else int(gram_min)
+    o.forceGlobal = -1 if force_global is None else int(bool(force_global))
+    return o
+
+
+def _lstsq_shapes(shapes):
+    sh = np.ascontiguousarray(np.asarray(shapes, dtype=np.uint32).reshape(-1, 3))
+    if np.any(sh == 0):
+        raise ValueError("every dimension of a least-squares problem must be >= 1")
+    return sh
+
+
+def lstsq_routes(shapes, ranks=None, qr_min=None, gram_min=None, force_global=None):
+    """The routes bfhipLstSqTruncated takes for problems of the given (mt, me, n) shapes, without a device
+    (bfhipLstSqRoutes); `ranks`: what the QR stage is assumed to leave (default: me).  A list of dicts."""
+    sh = _lstsq_shapes(shapes)
+    rk = None if ranks is None else np.ascontiguousarray(ranks, dtype=np.uint32)
+    out = (_capi.BfhipLstSqRoute * max(len(sh), 1))()
+    opts = _lstsq_options(qr_min, gram_min, force_global)
+    check(_capi.load().bfhipLstSqRoutes(len(sh), sh.ctypes.data, None if rk is None else rk.ctypes.data, C.byref(opts), out))
+    return [out[i].as_dict() for i in range(len(sh))]
+
+
+def lstsq_truncated(problems, device=-1, qr_min=None, gram_min=None, force_global=None):
+    """X = pinv_k(A) B for each (A, B) of `problems` on the device, by the builder's own solve (bfhipLstSqTruncated:
+    QR with column pivoting, one-sided Jacobi SVD, the reference's truncation rule).  Returns a list of
+    (X, sigma, info): sigma the kept singular values, descending; info a dict with rank, qrRank, sweeps,
+    notConverged and the route taken."""
+    As = [np.asarray(a, dtype=np.complex128) for a, _ in problems]
+    Bs = [np.asarray(b, dtype=np.complex128) for _, b in problems]
+    if any(a.ndim != 2 or b.ndim != 2 or a.shape[0] != b.shape[0] for a, b in zip(As, Bs)):
+        raise ValueError("each problem is (A: mt x me, B: mt x n)")
+    sh = _lstsq_shapes([(a.shape[0], a.shape[1], b.shape[1]) for a, b in zip(As, Bs)])
+    abuf = np.concatenate([a.ravel(order="F") for a in As]) if As else np.zeros(0, np.complex128)
+    bbuf = np.concatenate([b.ravel(order="F") for b in Bs]) if Bs else np.zeros(0, np.complex128)
+    xbuf = np.empty(int(np.sum(sh[:, 1].astype(np.uint64) * sh[:, 2])), dtype=np.complex128)
+    sbuf = np.empty(int(np.sum(sh[:, 1].astype(np.uint64))), dtype=np.float64)
+    info = (_capi.BfhipLstSqInfo * max(len(sh), 1))()
+    opts = _lstsq_options(qr_min, gram_min, force_global)
+    check(_capi.load().bfhipLstSqTruncated(len(sh), sh.ctypes.data, abuf.ctypes.data, bbuf.ctypes.data, xbuf.ctypes.data,
+                                           sbuf.ctypes.data, info, C.byref(opts), device))
+    out, xo, so = [], 0, 0
+    for i, (mt, me, n) in enumerate(sh.tolist()):
+        X = xbuf[xo:xo + me * n].reshape((me, n), order="F").copy()
+        f = info[i]
+        rank = int(f.rank)
+        out.append((X, sbuf[so:so + rank].copy(), {"rank": rank, "qrRank": int(f.qrRank), "sweeps": int(f.sweeps),
+                                                   "notConverged": int(f.notConverged), "route": f.route.as_dict()}))
+        xo += me * n
+        so += me
+    return out

@@ -21,14 +21,14 @@
  * at r == 0; a re-expansion leaf is X = pinv_trunc(Z_equiv) Z_orig with the
  * reference's truncation rule (singular values below max(m,n) eps s_max + eps
  * dropped), computed by a one-sided Jacobi SVD (QR-preconditioned with column pivoting from 65 equivalent sources up)
- * instead of LAPACK zgesvd.  Where the two criteria differ: the QR stage stops on COLUMN NORMS (the largest remaining column
- * of the pivoted factorization below max(m,n) eps x the largest column of Z_equiv -- the threshold under which the Jacobi kernel
+ * instead of LAPACK zgesvd.  Where the two criteria differ: the QR stage stops on COLUMN NORMS (the trailing columns
+ * of the pivoted factorization, their squared norms summed, below max(m,n) eps x the largest column of Z_equiv -- the threshold under which the Jacobi kernel
  * freezes a column), the reference truncates on SINGULAR VALUES (sigma < max(m,n) eps sigma_max + eps).  The stop is at the noise
  * floor, far below the rule's threshold on these matrices, and the rule itself is then applied to the singular values of what the
  * QR kept; a direction whose singular value lies within a factor ~sqrt(columns) of the threshold can still be dropped by the QR
  * stage where zgesvd would have kept it -- such directions are rounding noise in either computation (BFHIP_JACOBI_QR_MIN=<huge>
- * turns the stage off).  A least-squares matrix that is zero or not finite (QR rank 0) is counted in
- * BfhipBuildStats.notConverged: the build fails unless BFHIP_ALLOW_UNCONVERGED_SVD=1, and the leaf is then exactly zero.
+ * turns the stage off).  A least-squares matrix that is not finite is counted in
+ * BfhipBuildStats.notConverged: the build fails unless BFHIP_ALLOW_UNCONVERGED_SVD=1; a zero one gives a zero leaf.
  * Element-wise agreement with the CPU path is therefore at the level of the
  * truncation (the dropped directions), while Z_equiv X, and hence every
  * apply result, agrees to ~1e-12; see tests/test_gpu_build.py.
@@ -219,6 +219,44 @@ int bfhipFacHelm2MakeMultilevel2(const double *points, const double *normals, co
 /* One leaf, computed on the device and returned to the host row-major
  * (rows x cols complex128) -- unit-level parity checks of the builder. */
 int bfhipHelm2BuildLeaf(const BfhipHelm2Problem *prob, uint64_t recipeIndex, int device, void *out);
+
+/* ---- the builder's least-squares solve on caller matrices ------------------------------------------------
+ * X = pinv_k(A) B for a batch of problems, computed exactly as a re-expansion leaf is (QR with column pivoting ->
+ * one-sided Jacobi SVD -> two GEMMs, the reference's truncation rule: singular values below max(mt, me) eps sigma_max +
+ * eps dropped).  Problem i is mt x me (A), mt x n (B), me x n (X); all complex128, column-major, each array the problems'
+ * blocks back to back in problem order.  shapes: [3 count] (mt, me, n), every one >= 1; wide problems (mt < me) are
+ * allowed.  sigma: NULL, or [sum of me] -- problem i's kept singular values, descending, then zeros.  info: NULL, or
+ * [count].  A NaN or an infinity in A or B sets info.notConverged (X is then no answer).  Host memory throughout. */
+typedef struct BfhipLstSqOptions {
+  uint32_t structSize;   /* = sizeof(BfhipLstSqOptions) */
+  uint32_t reserved;
+  int64_t qrMin;         /* problems with >= qrMin columns take the QR stage first (0: all); < 0: BFHIP_JACOBI_QR_MIN, else 65 */
+  int64_t gramMin;       /* Jacobi problems with rows + columns >= gramMin take the Gram form; < 0: BFHIP_JACOBI_GRAM_MIN, else 512 */
+  int64_t forceGlobal;   /* 1: every Jacobi problem takes the global-memory kernel; < 0: BFHIP_JACOBI_GLOBAL=1, else 0 */
+} BfhipLstSqOptions;
+enum { BFHIP_JACOBI_PLAIN = 0, BFHIP_JACOBI_GRAM = 1, BFHIP_JACOBI_GLOBAL = 2 };
+typedef struct BfhipLstSqRoute {
+  uint32_t qr;           /* 1: QR with column pivoting first (the Jacobi stage then sees me x qrRank) */
+  uint32_t qrLdsClass;   /* QR: 0..5 = 8, 16, 32, 64, 128, 150 KiB of LDS */
+  uint32_t qrStreaming;  /* QR: 1 when columns of > 1024 rows are streamed (else held in registers) */
+  uint32_t jacobi;       /* BFHIP_JACOBI_* */
+  uint32_t w, threads;   /* plain Jacobi kernel: lane-group width (4..64) and workgroup size (256 / 1024) */
+  uint32_t ldsClass;     /* plain Jacobi kernel: 0..3 = 16, 32, 64, 144 KiB tile */
+  uint32_t resident;     /* plain Jacobi kernel: 1 = the stacked matrix stays in LDS, 0 = block sweeps */
+} BfhipLstSqRoute;
+typedef struct BfhipLstSqInfo {
+  BfhipLstSqRoute route; /* the route taken (with the QR stage's actual rank) */
+  uint32_t rank;         /* singular values kept */
+  uint32_t qrRank;       /* columns the QR stage left (me without it) */
+  uint32_t sweeps;       /* Jacobi sweeps */
+  uint32_t notConverged; /* 1: the sweep cap was hit, or A or B is not finite */
+} BfhipLstSqInfo;
+int bfhipLstSqTruncated(uint64_t count, const uint32_t *shapes, const void *A, const void *B, void *X, double *sigma,
+                        BfhipLstSqInfo *info, const BfhipLstSqOptions *opts, int device);
+/* The routes bfhipLstSqTruncated would take, without a device; ranks: NULL, or [count] the rank the QR stage is assumed
+ * to leave (NULL: me). */
+int bfhipLstSqRoutes(uint64_t count, const uint32_t *shapes, const uint32_t *ranks, const BfhipLstSqOptions *opts,
+                     BfhipLstSqRoute *routes);
 
 /* y = G x with the N x N single-layer kernel matrix evaluated on the fly
  * (never stored): the reference examples' acceptance check at sizes where
