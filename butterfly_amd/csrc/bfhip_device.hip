@@ -965,17 +965,57 @@ __device__ __forceinline__ void bfRowRange(uint64_t n, uint32_t nb, uint64_t &r0
   if (r0 > n) r0 = n;
 }
 
-// W = B - AX0 (AX0 may be null); partialOut[q*nb + bx] = sum |W|^2 over the block's rows
+// fixed-order tree over the 256 threads: .x summed, .y the maximum
+__device__ __forceinline__ double2 bfBlockReduceSumMax(double2 v, double2 *sh) {
+  sh[threadIdx.x] = v;
+  __syncthreads();
+  for (int s = BF_GM_THREADS / 2; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) { sh[threadIdx.x].x += sh[threadIdx.x + s].x; sh[threadIdx.x].y = fmax(sh[threadIdx.x].y, sh[threadIdx.x + s].y); }
+    __syncthreads();
+  }
+  double2 r = sh[0];
+  __syncthreads();
+  return r;
+}
+
+// W = B - AX0 (AX0 may be null); partialOut[q*nb + bx] = (sum |W|^2, largest |component| of W) over the block's rows
 __global__ __launch_bounds__(BF_GM_THREADS) void bfGmresResidualKernel(double2 const *B, double2 const *AX0, double2 *W,
                                                                       double2 *partialOut, uint64_t n, uint32_t nrhs, uint32_t nb) {
   __shared__ double2 sh[BF_GM_THREADS];
   uint32_t const q = blockIdx.y;
   uint64_t r0, r1;
   bfRowRange(n, nb, r0, r1);
-  double acc = 0.0;
+  double acc = 0.0, big = 0.0;
   for (uint64_t r = r0 + threadIdx.x; r < r1; r += BF_GM_THREADS) {
     double2 v = B[r * nrhs + q];
     if (AX0) { double2 y = AX0[r * nrhs + q]; v.x -= y.x; v.y -= y.y; }
+    W[r * nrhs + q] = v;
+    acc += v.x * v.x + v.y * v.y;
+    big = fmax(big, fmax(fabs(v.x), fabs(v.y)));
+  }
+  double2 t = bfBlockReduceSumMax(make_double2(acc, big), sh);
+  if (threadIdx.x == 0) partialOut[(uint64_t)q * nb + blockIdx.x] = t;
+}
+
+// Per column q: e = the binary exponent of the largest |component| (the .y of bfGmresResidualKernel's partials; 0 for a zero or
+// non-finite column); W *= 2^-e exactly (ldexp), so that the largest component lies in [1/2, 1) and the sum of squares can
+// neither underflow nor overflow; expOut[q] = e; partialOut = per-block |W|^2 of the scaled column.
+__global__ __launch_bounds__(BF_GM_THREADS) void bfGmresScaleKernel(double2 *W, double2 const *partialIn, double *expOut, double2 *partialOut,
+                                                                   uint64_t n, uint32_t nrhs, uint32_t nb) {
+  __shared__ double2 sh[BF_GM_THREADS];
+  uint32_t const q = blockIdx.y;
+  double big = 0.0;
+  for (uint32_t b = threadIdx.x; b < nb; b += BF_GM_THREADS) big = fmax(big, partialIn[(uint64_t)q * nb + b].y);
+  big = bfBlockReduceSumMax(make_double2(0.0, big), sh).y;
+  int e = 0;
+  if (big > 0.0 && isfinite(big)) frexp(big, &e);
+  if (blockIdx.x == 0 && threadIdx.x == 0) expOut[q] = (double)e;
+  uint64_t r0, r1;
+  bfRowRange(n, nb, r0, r1);
+  double acc = 0.0;
+  for (uint64_t r = r0 + threadIdx.x; r < r1; r += BF_GM_THREADS) {
+    double2 v = W[r * nrhs + q];
+    v = make_double2(ldexp(v.x, -e), ldexp(v.y, -e));
     W[r * nrhs + q] = v;
     acc += v.x * v.x + v.y * v.y;
   }
@@ -1039,11 +1079,13 @@ __global__ __launch_bounds__(BF_GM_THREADS) void bfGmresFinishKernel(double2 con
   double2 const s = bfSumPartials(partialIn, q, nb, sh);
   double const nrm = sqrt(s.x);
   if (blockIdx.x == 0 && threadIdx.x == 0) hOut[q] = make_double2(nrm, 0.0);
+  // a zero column (zero residual, or an exhausted Krylov space) gives V = 0, not 0/0: the host stops that column there
+  bool const live = nrm > 0.0;
   uint64_t r0, r1;
   bfRowRange(n, nb, r0, r1);
   for (uint64_t r = r0 + threadIdx.x; r < r1; r += BF_GM_THREADS) {
     double2 w = W[r * nrhs + q];
-    Vout[r * nrhs + q] = make_double2(w.x / nrm, w.y / nrm);
+    Vout[r * nrhs + q] = live ? make_double2(w.x / nrm, w.y / nrm) : make_double2(0.0, 0.0);
   }
 }
 
@@ -1056,6 +1098,7 @@ __global__ __launch_bounds__(BF_GM_THREADS) void bfGmresUpdateKernel(double2 con
   double2 x = X0 ? X0[e] : make_double2(0.0, 0.0);
   for (uint32_t i = 0; i < j; ++i) {
     double2 v = V[(uint64_t)i * total + e], c = y[(uint64_t)i * nrhs + q];
+    if (c.x == 0.0 && c.y == 0.0) continue;      // a column that stopped early: x0 is kept bit for bit
     x.x += v.x * c.x - v.y * c.y;
     x.y += v.x * c.y + v.y * c.x;
   }
@@ -1418,9 +1461,13 @@ int bfdevLaunchReduce(BfReduceArgs const *a, uint32_t count, void *stream) {
   return 0;
 }
 
-int bfdevGmresResidual(void const *B, void const *AX0, void *W, void *partialOut, uint64_t n, uint32_t nrhs, uint32_t nb, void *stream) {
+int bfdevGmresResidual(void const *B, void const *AX0, void *W, void *partialOut, uint64_t n, uint32_t nrhs, uint32_t nb, void *expOut,
+                       void *partialScaled, void *stream) {
   hipLaunchKernelGGL(bfGmresResidualKernel, dim3(nb, nrhs), dim3(BF_GM_THREADS), 0, (hipStream_t)stream, (double2 const *)B, (double2 const *)AX0, (double2 *)W, (double2 *)partialOut, n, nrhs, nb);
-  return hipFail(hipGetLastError(), "gmres residual launch");
+  int rc = hipFail(hipGetLastError(), "gmres residual launch");
+  if (rc || !expOut) return rc;
+  hipLaunchKernelGGL(bfGmresScaleKernel, dim3(nb, nrhs), dim3(BF_GM_THREADS), 0, (hipStream_t)stream, (double2 *)W, (double2 const *)partialOut, (double *)expOut, (double2 *)partialScaled, n, nrhs, nb);
+  return hipFail(hipGetLastError(), "gmres scale launch");
 }
 int bfdevGmresDot(void const *Vi, void const *W, void *partialOut, uint64_t n, uint32_t nrhs, uint32_t nb, void *stream) {
   hipLaunchKernelGGL(bfGmresDotKernel, dim3(nb, nrhs), dim3(BF_GM_THREADS), 0, (hipStream_t)stream, (double2 const *)Vi, (double2 const *)W, (double2 *)partialOut, n, nrhs, nb);

@@ -18,15 +18,31 @@
  * own order (one fused kernel per basis vector), which follows oracle/linalg_ref.py
  * iteration for iteration.
  *
- * Reference quirk kept for parity: when the residual test passes at iteration
- * j the loop breaks before j is incremented, so the solution uses j (not j+1)
- * basis vectors and numIter reports j (src/linalg.c:235-243,245-287).
+ * Where this solver departs from the reference ("GMRES semantics"):
+ *  - when the residual test passes at iteration j, the solution is built from
+ *    V_0..V_j -- the vectors the estimate |s_{j+1}| describes -- and numIter
+ *    reports j + 1, the number of Arnoldi steps (as maxNumIter does when the
+ *    test never passes).  The reference breaks before j is incremented and
+ *    builds the solution from j vectors (src/linalg.c:235-243,245-287): with b
+ *    an eigenvector of A it returns x0 and reports convergence;
+ *  - each residual column is scaled by a power of two 2^-e_p (its largest
+ *    component in [1/2, 1)) before its norm is taken, and the solution
+ *    coefficients are scaled back by 2^e_p: the sums of squares cannot
+ *    underflow or overflow (the reference's dznrm2 is scaled too), and a
+ *    right-hand side scaled by 2^k gives the same iterations and X scaled by
+ *    2^k bit for bit;
+ *  - a column whose residual is zero, or whose Krylov space is exhausted
+ *    (H[j+1, j] = 0 exactly), stops there: its next basis vector is 0, not
+ *    0/0, and its back substitution uses only its own vectors.  When every
+ *    column has stopped the solve ends, whatever tol is.
  */
 #include "bfhip_internal.h"
 #include "../../include/bfhip_abi.h"
 
 #include <complex.h>
+#include <limits.h>
 #include <math.h>
+#include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -138,10 +154,10 @@ int bfGmresResolveOrth(uint32_t orthogonalization) {
 
 void bfGmresWorkRelease(BfGmresWork *w) {
   bfdevFree(w->dV); bfdevFree(w->dW); bfdevFree(w->dPartA); bfdevFree(w->dPartB); bfdevFree(w->dH); bfdevFree(w->dY); bfdevFree(w->dAX0);
-  bfdevFree(w->dPartAll); bfdevFree(w->dH1); bfdevFree(w->dH2); bfdevFree(w->dPre);
+  bfdevFree(w->dPartAll); bfdevFree(w->dH1); bfdevFree(w->dH2); bfdevFree(w->dPre); bfdevFree(w->dExp);
   bfdevEventDestroy(w->evCol[0]); bfdevEventDestroy(w->evCol[1]);
   bfdevHostFreePinned(w->hHpinned);
-  free(w->H); free(w->S); free(w->Jc); free(w->Js); free(w->y); free(w->rnorm);
+  free(w->H); free(w->S); free(w->Jc); free(w->Js); free(w->y); free(w->rnorm); free(w->expo); free(w->len);
   memset(w, 0, sizeof *w);
 }
 
@@ -161,6 +177,7 @@ int bfGmresWorkInit(BfGmresWork *w, uint64_t n, size_t m, size_t nrhs, int orth,
   CHECK(bfdevMalloc(&w->dPartB, (size_t)nb * nrhs * 16));
   CHECK(bfdevMalloc(&w->dH, (m + 2) * nrhs * 16));
   CHECK(bfdevMalloc(&w->dY, (m + 1) * nrhs * 16));
+  CHECK(bfdevMalloc(&w->dExp, nrhs * sizeof(double)));
   if (!w->useMgs) {
     CHECK(bfdevMalloc(&w->dPartAll, (size_t)nb * nrhs * (m + 1) * 16));
     CHECK(bfdevMalloc(&w->dH1, (m + 1) * nrhs * 16));
@@ -177,7 +194,9 @@ int bfGmresWorkInit(BfGmresWork *w, uint64_t n, size_t m, size_t nrhs, int orth,
   w->Js = malloc(m * nrhs * sizeof(cplx));
   w->y = malloc((m + 1) * nrhs * sizeof(cplx));
   w->rnorm = malloc(nrhs * sizeof(double));
-  if (!w->H || !w->S || !w->Jc || !w->Js || !w->y || !w->rnorm) { rc = bfhipFail(BFABI_ERROR_MEMORY_ERROR, "host OOM"); goto fail; }
+  w->expo = malloc(nrhs * sizeof(double));
+  w->len = malloc(nrhs * sizeof(size_t));
+  if (!w->H || !w->S || !w->Jc || !w->Js || !w->y || !w->rnorm || !w->expo || !w->len) { rc = bfhipFail(BFABI_ERROR_MEMORY_ERROR, "host OOM"); goto fail; }
   return 0;
 fail:
   bfGmresWorkRelease(w);
@@ -200,8 +219,9 @@ int bfGmresRun(BfGmresWork *w, BfGmresApplyFn apply, void *ctx, BfGmresApplyFn p
   cplx *const hH = w->hHpinned;
   cplx *const hHslot[2] = {hH, hH + (m + 2) * nrhs};   /* "column j is in host memory", two in flight */
   cplx *const H = w->H, *const S = w->S, *const Jc = w->Jc, *const Js = w->Js, *const y = w->y;
-  double *const rnorm = w->rnorm;
-  size_t j = 0;
+  double *const rnorm = w->rnorm, *const expo = w->expo;
+  size_t *const len = w->len;
+  size_t j = 0, used = 0;
   int converged = 0;
   double lastResidual = INFINITY;
   memset(H, 0, (m + 2) * m * nrhs * sizeof(cplx));
@@ -213,17 +233,29 @@ int bfGmresRun(BfGmresWork *w, BfGmresApplyFn apply, void *ctx, BfGmresApplyFn p
   if (precond) {
     /* R = M^{-1} (B - A X0) (:127-135): the difference goes to a scratch vector, the preconditioner writes W,
      * and the norm partials are taken from W */
-    CHECK(bfdevGmresResidual(dB, dAX0, dPre, dPartA, n, (uint32_t)nrhs, nb, stream));
+    CHECK(bfdevGmresResidual(dB, dAX0, dPre, dPartA, n, (uint32_t)nrhs, nb, NULL, NULL, stream));
     CHECK(precond(pctx, dPre, nrhs, dW, stream));
-    CHECK(bfdevGmresResidual(dW, NULL, dW, dPartA, n, (uint32_t)nrhs, nb, stream));
+    CHECK(bfdevGmresResidual(dW, NULL, dW, dPartA, n, (uint32_t)nrhs, nb, w->dExp, dPartB, stream));
   } else
-  CHECK(bfdevGmresResidual(dB, dAX0, dW, dPartA, n, (uint32_t)nrhs, nb, stream));
-  /* V[0] = R / ||R|| per column; S[0] = ||R|| (:139-151) */
-  CHECK(bfdevGmresFinish(dW, dPartA, dV, dH, n, (uint32_t)nrhs, nb, stream));
+  CHECK(bfdevGmresResidual(dB, dAX0, dW, dPartA, n, (uint32_t)nrhs, nb, w->dExp, dPartB, stream));
+  /* (the residual launcher scaled R_p by 2^-e_p, exactly) V[0] = R / ||R|| per column; S[0] = ||R|| 2^-e_p (:139-151) */
+  CHECK(bfdevGmresFinish(dW, dPartB, dV, dH, n, (uint32_t)nrhs, nb, stream));
   CHECK(bfdevMemcpyD2HAsync(hH, dH, nrhs * 16, stream));
+  CHECK(bfdevMemcpyD2HAsync(hH + nrhs, w->dExp, nrhs * sizeof(double), stream));
   CHECK(bfdevSync(stream));
+  /* beta = max_p ||r_p|| (:142), held as betaS 2^E with E = the largest exponent of a nonzero column: the residual test
+   * max_p |s_{j+1,p}| 2^(e_p - E) / betaS then neither overflows nor underflows where it matters */
+  int E = INT_MIN;
+  for (size_t p = 0; p < nrhs; ++p) {
+    rnorm[p] = creal(hH[p]);
+    expo[p] = ((double const *)(hH + nrhs))[p];
+    S[p] = rnorm[p];
+    len[p] = rnorm[p] > 0 ? SIZE_MAX : 0;       /* a zero residual column stops before it starts: its X is x0 */
+    if (rnorm[p] > 0 && (int)expo[p] > E) E = (int)expo[p];
+  }
   double beta = 0;
-  for (size_t p = 0; p < nrhs; ++p) { rnorm[p] = creal(hH[p]); S[p] = rnorm[p]; if (rnorm[p] > beta) beta = rnorm[p]; }
+  for (size_t p = 0; p < nrhs; ++p)
+    if (rnorm[p] > 0) { double const b = ldexp(rnorm[p], (int)expo[p] - E); if (b > beta) beta = b; }
   if (!(beta > 0)) {
     /* zero residual: x0 already solves the system; the reference would divide by zero here */
     if (dX0) CHECK(bfdevMemcpyD2DAsync(dX, dX0, vecBytes, stream));
@@ -278,34 +310,46 @@ int bfGmresRun(BfGmresWork *w, BfGmresApplyFn apply, void *ctx, BfGmresApplyFn p
     cplx const *hCol = hHslot[j & 1];
 
     double resmax = 0;
+    int running = 0;
     for (size_t p = 0; p < nrhs; ++p) {
+      if (len[p] != SIZE_MAX) continue;            /* stopped: its later columns of H are zero and unused */
       cplx *col = H + (j * (m + 2)) * nrhs;        /* column j, entries i = 0..j+1 at col[i*nrhs + p] */
       for (size_t i = 0; i < j + 2; ++i) col[i * nrhs + p] = hCol[i * nrhs + p];
+      if (!(cabs(col[(j + 1) * nrhs + p]) > 0)) len[p] = j + 1;   /* exact breakdown: K_{j+1} is invariant, the solve exact */
+      else running = 1;
       for (size_t i = 0; i < j; ++i)               /* earlier rotations (:206-212) */
         applyGivens(&col[i * nrhs + p], &col[(i + 1) * nrhs + p], Jc[i * nrhs + p], Js[i * nrhs + p]);
       givens(col[j * nrhs + p], col[(j + 1) * nrhs + p], &Jc[j * nrhs + p], &Js[j * nrhs + p]);   /* (:214-219) */
       applyGivens(&col[j * nrhs + p], &col[(j + 1) * nrhs + p], Jc[j * nrhs + p], Js[j * nrhs + p]);
       applyGivens(&S[j * nrhs + p], &S[(j + 1) * nrhs + p], Jc[j * nrhs + p], Js[j * nrhs + p]);  /* (:222-228) */
-      double r = cabs(S[(j + 1) * nrhs + p]);
+      double r = ldexp(cabs(S[(j + 1) * nrhs + p]), (int)expo[p] - E);
       if (r > resmax) resmax = r;
     }
     lastResidual = resmax / beta;                  /* (:230-231) */
-    if (lastResidual < tol) { converged = 1; break; }   /* j is NOT incremented (:235-241) */
+    /* the estimate describes the iterate from V_0..V_j: it is the one returned, after j + 1 Arnoldi steps */
+    if (lastResidual < tol || !running) { converged = 1; break; }
   }
 #undef ENQUEUE
-  if (!converged) j = m;
+  used = converged ? j + 1 : m;
 
-  /* back substitution per RHS on the j x j triangle (:245-285) */
+  /* back substitution per RHS on its own k x k triangle, k = min(len_p, used) (:245-285); y = 0 past k, then y *= 2^e_p */
   for (size_t p = 0; p < nrhs; ++p) {
-    for (size_t r = j; r-- > 0;) {
+    size_t const k = len[p] < used ? len[p] : used;
+    for (size_t r = k; r < used; ++r) y[r * nrhs + p] = 0;
+    for (size_t r = k; r-- > 0;) {
       cplx acc = S[r * nrhs + p];
-      for (size_t c = r + 1; c < j; ++c) acc -= H[(c * (m + 2) + r) * nrhs + p] * y[c * nrhs + p];
+      for (size_t c = r + 1; c < k; ++c) acc -= H[(c * (m + 2) + r) * nrhs + p] * y[c * nrhs + p];
       y[r * nrhs + p] = acc / H[(r * (m + 2) + r) * nrhs + p];
     }
+    for (size_t r = 0; r < k; ++r) {
+      cplx const v = y[r * nrhs + p];
+      y[r * nrhs + p] = CMPLX(ldexp(creal(v), (int)expo[p]), ldexp(cimag(v), (int)expo[p]));
+    }
   }
-  CHECK(bfdevMemcpyH2DAsync(dY, y, j * nrhs * 16, stream));
-  CHECK(bfdevGmresUpdate(dX0, dV, dY, (uint32_t)j, dX, n, (uint32_t)nrhs, stream));
+  CHECK(bfdevMemcpyH2DAsync(dY, y, used * nrhs * 16, stream));
+  CHECK(bfdevGmresUpdate(dX0, dV, dY, (uint32_t)used, dX, n, (uint32_t)nrhs, stream));
   CHECK(bfdevSync(stream));
+  j = used;
 
 finish:
   if (numIter) *numIter = j;

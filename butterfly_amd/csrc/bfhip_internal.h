@@ -248,10 +248,11 @@ typedef struct BfGmresWork {
   size_t m, nrhs;
   uint32_t nb;
   int useMgs, hasPrecond, hasX0;
-  void *dV, *dW, *dPartA, *dPartB, *dH, *dY, *dAX0, *dPartAll, *dH1, *dH2, *dPre, *hHpinned;
+  void *dV, *dW, *dPartA, *dPartB, *dH, *dY, *dAX0, *dPartAll, *dH1, *dH2, *dPre, *dExp, *hHpinned;
   void *evCol[2];
   void *H, *S, *Jc, *Js, *y;   /* double _Complex host arrays */
-  double *rnorm;
+  double *rnorm, *expo;        /* per column: ||r_p|| 2^-e_p and e_p (the residual's power-of-two scale) */
+  size_t *len;                 /* per column: Krylov vectors its solution uses once it has stopped (SIZE_MAX while it runs) */
 } BfGmresWork;
 int bfGmresWorkInit(BfGmresWork *w, uint64_t n, size_t m, size_t nrhs, int orth, int hasPrecond, int hasX0);
 void bfGmresWorkRelease(BfGmresWork *w);   /* idempotent; a zeroed struct is released as a no-op */
@@ -442,7 +443,11 @@ int bfdevScalePermute(void *dst, void const *src, void const *scale, int power, 
  * Vectors are n x nrhs row-major; reductions are per RHS column, two-stage and
  * in fixed order (per-block partials, then a tree over the partials), so a
  * solve is bit-reproducible.  `nb` = number of row blocks = partials per RHS. */
-int bfdevGmresResidual(void const *B, void const *AX0, void *W, void *partialOut, uint64_t n, uint32_t nrhs, uint32_t nb, void *stream);
+/* W = B - AX0 (AX0 may be NULL); partialOut = per-block (|W|^2, largest |component|).  With expOut (nrhs doubles) it then scales
+ * each column: e = binary exponent of its largest component (0 for a zero column), W *= 2^-e exactly, expOut[q] = e, and
+ * partialScaled = per-block |W|^2 of the scaled column */
+int bfdevGmresResidual(void const *B, void const *AX0, void *W, void *partialOut, uint64_t n, uint32_t nrhs, uint32_t nb, void *expOut,
+                       void *partialScaled, void *stream);
 int bfdevGmresDot(void const *Vi, void const *W, void *partialOut, uint64_t n, uint32_t nrhs, uint32_t nb, void *stream);
 /* h = sum(partialIn); hOut[q] = h; W -= h * Vi; then partialOut = conj(Vnext).W (Vnext != NULL) or |W|^2 */
 int bfdevGmresMgsStep(void const *Vi, void const *Vnext, void *W, void const *partialIn, void *partialOut, void *hOut,
@@ -453,9 +458,9 @@ int bfdevGmresDots(void const *V, void const *W, void *partial, uint64_t n, uint
 int bfdevGmresDotsFinish(void const *partial, void const *hPrev, void *h, void *hSum, uint32_t nrhs, uint32_t nb, uint32_t numVec, void *stream);
 /* W -= sum_i h_i V_i; partialOut (may be NULL) = per-block |W|^2 */
 int bfdevGmresProject(void const *V, void *W, void const *h, void *partialOut, uint64_t n, uint32_t nrhs, uint32_t nb, uint32_t numVec, void *stream);
-/* nrm = sqrt(sum(partialIn)); hOut[q] = nrm; Vout = W / nrm */
+/* nrm = sqrt(sum(partialIn)); hOut[q] = nrm; Vout = W / nrm, or 0 where nrm is 0 */
 int bfdevGmresFinish(void const *W, void const *partialIn, void *Vout, void *hOut, uint64_t n, uint32_t nrhs, uint32_t nb, void *stream);
-/* X = X0 + sum_{i<j} V_i * y[i] ; V = (j) vectors of n*nrhs, y = [j][nrhs] */
+/* X = X0 + sum_{i<j} V_i * y[i] ; V = (j) vectors of n*nrhs, y = [j][nrhs]; a zero y[i] adds nothing (not even +0) */
 int bfdevGmresUpdate(void const *X0, void const *V, void const *y, uint32_t j, void *X, uint64_t n, uint32_t nrhs, void *stream);
 /* mixed-precision refinement (bfhip_refine.c drives them; streaming kernels, not stage kernels: no BfhipKernelId).
  * count = complex elements.  Demote rounds each component to nearest. */

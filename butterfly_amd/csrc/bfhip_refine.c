@@ -104,7 +104,7 @@ typedef struct BfRefine {
 static int trueResidual(BfRefine *R, void const *dXc, double *res, void *stream) {
   int rc = 0;
   if (dXc) rc = bfhipApplyDevice(R->op, dXc, R->nrhs, R->dR, stream);
-  if (!rc) rc = bfdevGmresResidual(R->dB, dXc ? R->dR : NULL, R->dR, R->dPart, R->n, (uint32_t)R->nrhs, R->nb, stream);
+  if (!rc) rc = bfdevGmresResidual(R->dB, dXc ? R->dR : NULL, R->dR, R->dPart, R->n, (uint32_t)R->nrhs, R->nb, NULL, NULL, stream);
   if (!rc) rc = bfdevRefineScale(R->dR, R->dPart, R->dRhat, R->dScale, R->n, (uint32_t)R->nrhs, R->nb, stream);
   if (!rc) rc = bfdevMemcpyD2HAsync(R->hScale, R->dScale, R->nrhs * sizeof(double), stream);
   if (!rc) rc = bfdevSync(stream);

@@ -485,7 +485,8 @@ def sharded_solve_gmres(step, b, x0=None, tol=1e-12, max_num_iter=100):
     GPU (O(j N) per iteration, nothing next to the apply) and the only communication of an iteration
     is the apply's one collective.  Same algorithm and quirks as the single-GPU bfhipSolveGMRES
     (unrestarted, Gram-Schmidt as two batched classical passes, residual = max_p |s_{j+1,p}| / max_p ||r_p||,
-    a converged solve uses j basis vectors).  b: [n] or [n, nrhs] complex tensor on the apply's device.
+    a solve that converges at iteration j uses the j + 1 basis vectors its estimate describes and reports j + 1,
+    a zero column gives a zero basis vector, not 0/0).  b: [n] or [n, nrhs] complex tensor on the apply's device.
     Returns (x, num_iter, residual)."""
     import torch
     one_d = b.dim() == 1
@@ -497,12 +498,15 @@ def sharded_solve_gmres(step, b, x0=None, tol=1e-12, max_num_iter=100):
     R = B - call(X0)
     rnorm = torch.linalg.vector_norm(R, dim=0)
     beta = float(rnorm.max())
+    if not beta > 0:                                 # x0 solves the system
+        X = X0.clone()
+        return (X[:, 0] if one_d else X), 0, 0.0
     # the Krylov basis as ONE tensor [max_num_iter + 1, n, nrhs]: an iteration's projections are two batched
     # contractions per Gram-Schmidt pass (CGS2: classical Gram-Schmidt, run twice -- as stable as the
     # reference's modified Gram-Schmidt, src/linalg.c:174-184, but one host synchronisation per iteration
     # instead of one per basis vector)
     V = torch.empty((max_num_iter + 1, n, nrhs), dtype=B.dtype, device=B.device)
-    V[0] = R / rnorm
+    V[0] = torch.where(rnorm > 0, R / torch.where(rnorm > 0, rnorm, torch.ones_like(rnorm)), torch.zeros_like(R))
     S = [[complex(rnorm[p]) if i == 0 else 0j for i in range(max_num_iter + 1)] for p in range(nrhs)]
     H, J = [], {}
     residual, converged, j = float("inf"), False, 0
@@ -514,7 +518,7 @@ def sharded_solve_gmres(step, b, x0=None, tol=1e-12, max_num_iter=100):
         h2 = torch.einsum("inp,np->ip", Vj.conj(), W)
         W -= torch.einsum("inp,ip->np", Vj, h2)
         wnorm = torch.linalg.vector_norm(W, dim=0)
-        V[j + 1] = W / wnorm
+        V[j + 1] = torch.where(wnorm > 0, W / torch.where(wnorm > 0, wnorm, torch.ones_like(wnorm)), torch.zeros_like(W))
         hcol = torch.cat([h1 + h2, wnorm[None].to(h1.dtype)], dim=0).tolist()     # the iteration's one host sync
         Hj = [[complex(hcol[i][p]) for i in range(j + 2)] for p in range(nrhs)]
         for p in range(nrhs):
@@ -526,17 +530,16 @@ def sharded_solve_gmres(step, b, x0=None, tol=1e-12, max_num_iter=100):
             _rot(S[p], j, *J[(j, p)])
         H.append(Hj)
         residual = max(abs(S[p][j + 1]) for p in range(nrhs)) / beta
-        if residual < tol:                           # :235-241: breaks before j is incremented
+        if residual < tol:                           # :235-241; the iterate the estimate describes uses V_0..V_j
             converged = True
             break
-    if not converged:
-        j = max_num_iter
+    j = j + 1 if converged else max_num_iter
     X = X0.clone()
     for p in range(nrhs):                            # back substitution and update (:245-285)
         y = [0j] * j
         for r in range(j - 1, -1, -1):
             acc = S[p][r] - sum(H[c][p][r] * y[c] for c in range(r + 1, j))
-            y[r] = acc / H[r][p][r]
+            y[r] = acc / H[r][p][r] if H[r][p][r] != 0 else 0j     # a column that stopped (zero residual or breakdown)
         for i in range(j):
             X[:, p] += V[i][:, p] * y[i]
     return (X[:, 0] if one_d else X), j, residual

@@ -274,9 +274,14 @@ int bfhipExtractWorkspaceBytes(const BfhipOperator *op, size_t numRows, size_t n
  * rotations, convergence when max_p |s_{j+1,p}| / max_p ||r_p|| < tol.  The
  * Krylov basis, the work vector, x0 and b stay on the device; only the new
  * Hessenberg column crosses PCIe per iteration.  X0 may be NULL (zeros).
- * `numIter` receives the reference's iteration count (the number of basis
- * vectors the solution is built from), `residual` the last relative residual;
- * either may be NULL.  Complex square operators only; the left preconditioner
+ * `numIter` receives the number of Arnoldi steps, which is the number of
+ * basis vectors the solution is built from: j + 1 when the test passes at
+ * iteration j (the reference stops one vector short and reports j), maxNumIter
+ * when it never does.  `residual` receives the last relative residual; either
+ * may be NULL.  Each residual column is scaled by a power of two before its
+ * norm is taken, so right-hand sides of any magnitude are solved (b scaled by
+ * 2^k gives X scaled by 2^k exactly); a column with a zero residual returns
+ * its x0, and a column whose Krylov space is exhausted stops there.  Complex square operators only; the left preconditioner
  * (the reference's M) is the *Precond* entry below.  Host-pointer form: B, X0, X are
  * row-major n x nrhs with leading dimensions in elements. */
 int bfhipSolveGMRES(BfhipOperator *op, const void *B, size_t ldb, size_t nrhs, const void *X0, size_t ldx0,

@@ -12,8 +12,9 @@ from oracle import linalg_ref
 
 INNER_TOL_DEFAULT = 1e-6          # BfhipGmresRefineOptions.innerTol = 0
 # outer steps the restatement needs on bie.second_kind_case(2048, 128), three random columns (seed 7), tol 1e-12,
-# default inner tolerance (tests/test_gmres_refine_cpu.py checks it; the GPU tests allow one more)
-OUTER_STEPS_2048 = 3
+# default inner tolerance (tests/test_gmres_refine_cpu.py checks it; the GPU tests allow one more).  3 while the inner
+# GMRES kept the reference's quirk of building a converged solution from one basis vector fewer than its estimate describes
+OUTER_STEPS_2048 = 2
 
 
 def c64_model(plan_only_c64_op):

@@ -92,7 +92,7 @@ def test_inverses(first_kind, second_kind, case):
     pre.close(); op.close()
 
 
-def test_preconditioned_gmres_follows_the_restatement(second_kind):
+def test_preconditioned_gmres_follows_the_corrected_restatement(second_kind):
     import torch
     desc, root, vals, dense = second_kind
     A = bfref.from_desc(desc, vals, root=root)

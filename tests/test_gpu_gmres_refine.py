@@ -93,8 +93,8 @@ def test_stagnation_returns_the_best_iterate(system, helm2_cases):
 
 
 def test_preconditioners_complex128_and_complex64(system):
-    """The block-Jacobi inverse of test_gmres.py::test_left_preconditioned_gmres as the inner solveM, compiled as complex128
-    and as complex64.  At inner_tol = 1e-10 (the default 1e-6 takes three iterations per correction with or without it)."""
+    """The block-Jacobi inverse of test_gmres.py::test_left_preconditioned_gmres_follows_the_corrected_restatement as the
+    inner solveM, compiled as complex128 and as complex64.  At inner_tol = 1e-10 (the default 1e-6 takes three iterations per correction with or without it)."""
     from butterfly_amd import helm2_structure as hs
     from butterfly_amd.operator import HipOperator
     desc, root, vals, dense, A, op, low, b = system

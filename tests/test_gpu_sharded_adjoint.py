@@ -168,7 +168,7 @@ def test_rccl_sharded_cov_matvec_and_shim_real_operator():
     op.close()
 
 
-def test_rccl_sharded_gmres_one_rank_is_the_plain_solve():
+def test_rccl_sharded_gmres_one_rank_is_the_plain_solve_and_the_corrected_restatement():
     """bfhipShardedSolveGMRESDevice (1-rank RCCL, the operator cut into three row segments) takes the iterations of
     bfhipSolveGMRESOptsDevice on the same operator and returns the same solution bit for bit -- the recurrences are the same
     code around another matvec -- and follows the numpy restatement of bfSolveGMRES (oracle/linalg_ref.py) in the reference's
