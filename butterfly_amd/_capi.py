@@ -18,6 +18,8 @@ FLAG_FLOW = 8
 FLAG_ADJOINT_PACKED = 16
 FLAG_EXACT_COMPLEX = 32
 KERNEL_COUNT = 61          # BFHIP_KERNEL_COUNT (include/bfhip.h): kernel ids of the apply path
+KERNEL_EXT_BASE, KERNEL_EXT_END = 64, 67      # the extension range: kernels only an opted-in operator runs (bfhipSetRhsBlocks)
+KERNEL_C64_MFMA1, KERNEL_C64_MFMA2, KERNEL_C64_MFMA4 = 64, 65, 66
 
 
 def kernel_name(kernel_id):
@@ -425,6 +427,8 @@ def load():
     lib.bfhipOperatorDevice.restype = C.c_int
     lib.bfhipSetHostApplyBudget.argtypes = [vp, C.c_uint64]
     lib.bfhipSetHostApplyBudget.restype = C.c_int
+    lib.bfhipSetRhsBlocks.argtypes = [vp, C.c_uint32]
+    lib.bfhipSetRhsBlocks.restype = C.c_int
     u64p = C.POINTER(C.c_uint64)
     lib.bfhipExtractDevice.argtypes = [vp, u64p, C.c_size_t, u64p, C.c_size_t, vp, C.c_size_t, C.POINTER(BfhipExtractOptions), vp]
     lib.bfhipExtractDevice.restype = C.c_int

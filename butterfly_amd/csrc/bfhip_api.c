@@ -86,6 +86,7 @@ struct BfhipOperator {
   uint32_t flowNumItems, flowGrid, flowEpoch, flowQueueBase, flowMaxWriters;
   uint64_t flowNumBufs;
   uint8_t evFlow[64];               /* per event set: that apply ran as ONE launch (its time is recorded under stage 0) */
+  uint32_t rhsBlocks;               /* bfhipSetRhsBlocks: 0 = off, else the smallest nrhs whose forward stages run the complex64 block kernels */
   uint64_t hostApplyBudget;         /* device bytes the host-vector apply may use for vectors; 0 = free memory - BF_HOST_BUDGET_MARGIN */
   void *extract;                    /* workspace of the dense extraction (bfhip_extract.c), released by extractRelease */
   void (*extractRelease)(void *);
@@ -731,7 +732,7 @@ static void stageLaunchArgs(BfhipOperator const *op, BfPlan const *plan, BfStage
   a->x = NULL; a->y = NULL; a->temp = op->dTemp; a->zero = op->dZero; a->nrhs = nrhs; a->dtype = plan->dtype; a->maxRows = st->maxRows;
   a->transposed = plan->transposed;
   a->tickets = NULL;
-  a->exactComplex = (op->flags & BFHIP_FLAG_EXACT_COMPLEX) != 0; a->pad2 = 0;
+  a->exactComplex = (op->flags & BFHIP_FLAG_EXACT_COMPLEX) != 0; a->rhsBlocks = plan == &op->plan ? op->rhsBlocks : 0;      /* the adjoint's plans (shared or packed) keep their kernels */
   a->bundles = st->dBundleBegin; a->numBundles = st->numBundles;
 }
 
@@ -1093,6 +1094,17 @@ int bfhipSetHostApplyBudget(BfhipOperator *op, uint64_t bytes) {
   return 0;
 }
 
+/* Host-only: the setting travels to the stage selection in every BfLaunchArgs (stageLaunchArgs), nothing else reads it. */
+int bfhipSetRhsBlocks(BfhipOperator *op, uint32_t minRhs) {
+  if (!op) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL operator");
+  if (op->plan.dtype != BFHIP_C64)
+    return bfhipFail(BFABI_ERROR_NOT_IMPLEMENTED, "right-hand-side block kernels are a complex64 switch: complex128 operators already run block kernels "
+                     "(bfStageKernelC128Mfma*) at nrhs >= 2, and the real element types (F64, F32) are not covered");
+  if (minRhs == 1) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "minRhs must be 0 (off) or at least 2");
+  op->rhsBlocks = minRhs;
+  return 0;
+}
+
 /* A caller who knows the lifetime of its vectors (the Krylov basis of a solver, a right-hand side applied many times) registers
  * them once: bfhipApply / the shim's Mul then DMA straight from / to them instead of packing through the staging buffer. */
 int bfhipHostRegister(void *p, size_t bytes) {
@@ -1194,7 +1206,13 @@ static char const *const kernelNames[BFHIP_KERNEL_COUNT] = {
   "bfReduceKernel<C128>", "bfReduceKernel<F64>", "bfReduceKernel<F64, long>", "bfReduceKernel<F32>",
   "bfReduceKernel<F32, long>", "bfReduceKernel<C64>", "bfReduceKernel<C64, long>",
 };
-char const *bfhipKernelName(uint32_t id) { return id < BFHIP_KERNEL_COUNT ? kernelNames[id] : NULL; }
+static char const *const kernelNamesExt[BFHIP_KERNEL_EXT_END - BFHIP_KERNEL_EXT_BASE] = {
+  "bfStageKernelC64Mfma<1 tile>", "bfStageKernelC64Mfma<2 tiles>", "bfStageKernelC64Mfma<4 tiles>",
+};
+char const *bfhipKernelName(uint32_t id) {
+  if (id >= BFHIP_KERNEL_EXT_BASE && id < BFHIP_KERNEL_EXT_END) return kernelNamesExt[id - BFHIP_KERNEL_EXT_BASE];
+  return id < BFHIP_KERNEL_COUNT ? kernelNames[id] : NULL;
+}
 
 int bfhipPlanStageKernels(BfhipOperator const *op, uint64_t stage, uint32_t nrhs, uint32_t *ids, uint32_t cap, uint32_t *count) {
   if (!op || !count || (cap && !ids) || !nrhs) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "bad stage kernel request");

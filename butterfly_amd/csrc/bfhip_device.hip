@@ -132,6 +132,7 @@ __global__ __launch_bounds__(BF_C128_WG_WAVES * 64) BF_C128_ATTR void bfStageKer
 }
 
 #include "bfhip_stage_mfma.h"
+#include "bfhip_stage_mfma_c64.h"
 
 // One row-major piece of MR rows (see the row-major branch of bfStageKernelReal): lane owns 16-byte units u = lane,
 // lane + 64, ... of every row; UNR units are in flight at once, so (MR + 1) * UNR independent loads per lane.  All
@@ -1391,6 +1392,16 @@ int bfdevLaunchStage(BfLaunchArgs const *a, void *stream) {
       { int handled = 0; int const rcx = bfdevLaunchStageExperimental(a, &p, grid, stream, &handled); if (handled) return rcx; }     /* EXPERIMENTAL=1 builds only */
 #endif
       hipLaunchKernelGGL(bfStageKernelC128, dim3(grid), dim3(BF_C128_WG_WAVES * 64), 0, s, p);
+    }
+    else if (L[i].kernel >= BFHIP_KERNEL_EXT_BASE) {
+      /* complex64 with bfhipSetRhsBlocks: one wavefront per item, ordinary and small items alike */
+      dim3 const g((uint32_t)a->numItems), b(64);
+      switch (L[i].kernel) {
+        case BFHIP_KERNEL_C64_MFMA1: hipLaunchKernelGGL((bfStageKernelC64Mfma<1, 4>), g, b, 0, s, p); break;
+        case BFHIP_KERNEL_C64_MFMA2: hipLaunchKernelGGL((bfStageKernelC64Mfma<2, 3>), g, b, 0, s, p); break;
+        case BFHIP_KERNEL_C64_MFMA4: hipLaunchKernelGGL((bfStageKernelC64Mfma<4, 2>), g, b, 0, s, p); break;
+        default: return bfhipFail(BFABI_ERROR_RUNTIME_ERROR, "internal: kernel id %u is not a stage kernel", L[i].kernel);
+      }
     }
     else if (L[i].kernel <= BFHIP_KERNEL_C128_MFMA4_EXACT) {
       dim3 const g((uint32_t)((a->numItems + BF_MF_WG_WAVES - 1) / BF_MF_WG_WAVES)), b(64 * BF_MF_WG_WAVES);

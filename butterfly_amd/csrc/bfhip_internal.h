@@ -315,7 +315,7 @@ typedef struct BfLaunchArgs {
   int transposed;        /* pieces carry `ld`: lanes own columns of the forward pieces */
   void *tickets;         /* NULL, or BF_TICKET_POOLS x BF_TICKET_STRIDE uint32 owned by this stage, zero between launches (see BfStage.dTickets) */
   uint32_t exactComplex; /* BFHIP_FLAG_EXACT_COMPLEX: the matrix-core kernels form complex products with four real multiplications */
-  uint32_t pad2;
+  uint32_t rhsBlocks;    /* bfhipSetRhsBlocks: forward complex64 stages of nrhs >= rhsBlocks run the block kernels; 0 = off */
   void const *bundles;   /* forward complex128: BfStage.dBundleBegin (NULL: none) */
   uint64_t numBundles;
 } BfLaunchArgs;
@@ -372,6 +372,12 @@ static inline uint32_t bfSelectStageKernels(BfLaunchArgs const *a, BfKernelLaunc
     out[0].numRanges = 1; out[0].first[0] = 0; out[0].count[0] = a->numItems; out[0].coop[0] = 0;
     if (a->nrhs < BF_MFMA_MIN_RHS) out[0].kernel = BFHIP_KERNEL_C128;
     else out[0].kernel = (a->exactComplex ? BFHIP_KERNEL_C128_MFMA1_EXACT : BFHIP_KERNEL_C128_MFMA1) + (a->nrhs <= 16 ? 0u : a->nrhs <= 32 ? 1u : 2u);
+    return 1;
+  }
+  /* complex64 with the block kernels switched on: one launch over all items, ordinary and small alike */
+  if (a->dtype == BFHIP_C64 && a->rhsBlocks && a->nrhs >= a->rhsBlocks) {
+    out[0].numRanges = 1; out[0].first[0] = 0; out[0].count[0] = a->numItems; out[0].coop[0] = 0;
+    out[0].kernel = BFHIP_KERNEL_C64_MFMA1 + (a->nrhs <= 16 ? 0u : a->nrhs <= 32 ? 1u : 2u);
     return 1;
   }
   /* the real family: items [firstSmall, numItems) are small (four to a wavefront) */

@@ -230,6 +230,19 @@ int bfhipApplyTransposeDevice(BfhipOperator *op, const void *dX, size_t nrhs, vo
  * when a call of more than 64 right-hand sides would grow those buffers.  A call that fits runs in one piece as before. */
 int bfhipSetHostApplyBudget(BfhipOperator *op, uint64_t bytes);
 
+/* complex64 operators: forward stages of applies with nrhs >= minRhs run on the block kernels
+ * (bfStageKernelC64Mfma*): one launch over all items of the stage, every leaf element loaded once per pass of up to 64
+ * right-hand sides (the default kernels load it once per right-hand side), widened exactly to double, contracted on the
+ * FP64 matrix cores and rounded to complex64 once at the store -- the element type's contract and error bound are unchanged.
+ * 0 = off (the default: every apply runs exactly the kernels it runs today); otherwise minRhs >= 2 (2 is the recommended
+ * value: the block path reads the operand once where the default path reads it nrhs times).  Plan, arena, saved file and
+ * applies of nrhs < minRhs are untouched; transposed stages and reduces are unchanged.  Results of the block path are
+ * deterministic and may differ from the default path's in the last float bit (another summation order).
+ * Works on any complex64 operator (compiled, loaded, a complex64 block-Jacobi result, a row shard) and under
+ * BFHIP_FLAG_PLAN_ONLY.  Errors: INVALID_ARGUMENTS (NULL operator, minRhs == 1); NOT_IMPLEMENTED for any other element type
+ * (complex128 already has block kernels; the real types are not covered). */
+int bfhipSetRhsBlocks(BfhipOperator *op, uint32_t minRhs);
+
 /* ---- dense extraction ------------------------------------------------------ */
 /* Entries of the operator, Out[i * ldOut + j] = A[rows[i], cols[j]]: a block A[I, J] (a near-field block, a check against the
  * dense kernel) or, with rows = cols = NULL, the whole matrix (what the reference's bfMatToType densifies, src/mat_product.c:377-407).
@@ -607,7 +620,12 @@ typedef enum BfhipKernelId {
   BFHIP_KERNEL_REDUCE_F32_LONG, BFHIP_KERNEL_REDUCE_C64, BFHIP_KERNEL_REDUCE_C64_LONG,
   BFHIP_KERNEL_COUNT
 } BfhipKernelId;
-/* "bfStageKernelT<F64, wide, coop, nrhs=1>"-style name of a kernel id; NULL when id >= BFHIP_KERNEL_COUNT */
+/* Extension range: kernels that only an opted-in operator runs (bfhipSetRhsBlocks).  The ids above never move; ids
+ * [BFHIP_KERNEL_COUNT, BFHIP_KERNEL_EXT_BASE) are unused. */
+#define BFHIP_KERNEL_EXT_BASE 64u
+enum { BFHIP_KERNEL_C64_MFMA1 = 64, BFHIP_KERNEL_C64_MFMA2 = 65, BFHIP_KERNEL_C64_MFMA4 = 66, BFHIP_KERNEL_EXT_END = 67 };   /* forward complex64 block kernels: nrhs <= 16, <= 32, more */
+/* "bfStageKernelT<F64, wide, coop, nrhs=1>"-style name of a kernel id; NULL for an id that is neither below BFHIP_KERNEL_COUNT
+ * nor in [BFHIP_KERNEL_EXT_BASE, BFHIP_KERNEL_EXT_END) */
 const char *bfhipKernelName(uint32_t id);
 /* The kernels, in launch order, that applying stage `stage` (numbering as bfhipPlanGetStage) to `nrhs` right-hand sides
  * launches: the stage's own kernels, then one reduce kernel per reduce launch.  Works under BFHIP_FLAG_PLAN_ONLY (no device).

@@ -25,6 +25,8 @@ def main():
     ap.add_argument("--ncols", type=int, default=8192)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--skip-host", action="store_true")
+    ap.add_argument("--c64", action="store_true", help="a complex64 operand: the synthetic headline layout (seed 1234, k = n / 16) compiled with demote_to_f32")
+    ap.add_argument("--rhs-blocks", type=int, default=0, help="with --c64: bfhipSetRhsBlocks(min_rhs) on the operand (0 = off)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch
@@ -32,13 +34,20 @@ def main():
     from butterfly_amd.operator import HipOperator
     n = a.n
     pts = hs.circle_points(n)
-    desc, _, perm = hs.helm2_multilevel_structure(pts, a.k, recipes=True, exact_sift=True)
-    op, st = HipOperator.build_helm2(desc, pts[perm], a.k)
+    if not a.c64:
+        desc, _, perm = hs.helm2_multilevel_structure(pts, a.k, recipes=True, exact_sift=True)
+    if a.c64:
+        desc, perm = hs.native_multilevel_structure(pts, n / 16.0)
+        op = HipOperator.from_desc(desc, None, seed=1234, demote_to_f32=True, max_rhs=64, rhs_blocks=a.rhs_blocks)
+    else:
+        op, st = HipOperator.build_helm2(desc, pts[perm], a.k)
+    ct = torch.complex64 if a.c64 else torch.complex128
+    esz = 8 if a.c64 else 16
     cols = np.arange(a.ncols, dtype=np.uint64)
-    out = torch.empty((n, a.ncols), dtype=torch.complex128, device="cuda")
-    x = torch.zeros((n, 64), dtype=torch.complex128, device="cuda")
+    out = torch.empty((n, a.ncols), dtype=ct, device="cuda")
+    x = torch.zeros((n, 64), dtype=ct, device="cuda")
     x[torch.arange(64, device="cuda"), torch.arange(64, device="cuda")] = 1
-    y = torch.empty((n, 64), dtype=torch.complex128, device="cuda")
+    y = torch.empty((n, 64), dtype=ct, device="cuda")
     panels = (a.ncols + 63) // 64
 
     def timed(fn):
@@ -60,11 +69,12 @@ def main():
     rec = {"n": n, "k": a.k, "ncols": a.ncols, "panels": panels, "reps": a.reps,
            "apply64_s": t_apply, "extract_device_s": t_dev,
            "apply64_cols_per_s": a.ncols / t_apply, "extract_device_cols_per_s": a.ncols / t_dev,
-           "device_over_apply": t_apply / t_dev, "output_bytes": n * a.ncols * 16}
+           "device_over_apply": t_apply / t_dev, "output_bytes": n * a.ncols * esz,
+           "dtype": "c64" if a.c64 else "c128", "rhs_blocks": a.rhs_blocks}
     assert torch.equal(out[:, :64], op.extract(None, cols[:64]))
     del out
     torch.cuda.empty_cache()
-    if not a.skip_host:
+    if not a.skip_host and not a.c64:
         host = np.empty((n, a.ncols), dtype=np.complex128)
         host[:] = 0
         HipOperator.host_register(host)

@@ -47,6 +47,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--max-iter", type=int, default=200)
     ap.add_argument("--solvers", default="c128,refine", help="comma list of c128 / refine (one alone for a kernel trace)")
+    ap.add_argument("--rhs-blocks", type=int, default=0, help="bfhipSetRhsBlocks(min_rhs) on the complex64 inner operator (0 = off)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch
@@ -58,7 +59,7 @@ def main():
         t_build = time.perf_counter() - t0
         mr = max(a.nrhs)
         op = HipOperator.from_desc(desc, vals, root=root, max_rhs=mr)
-        low = HipOperator.from_desc(desc, vals, root=root, max_rhs=mr, demote_to_f32=True)
+        low = HipOperator.from_desc(desc, vals, root=root, max_rhs=mr, demote_to_f32=True, rhs_blocks=a.rhs_blocks)
         for nrhs in a.nrhs:
             g = torch.Generator(device="cpu").manual_seed(1234 + nrhs)
             b = torch.randn((n, nrhs), dtype=torch.complex128, generator=g).to("cuda:0")
