@@ -102,7 +102,6 @@ static void freeDevicePlanOf(BfPlan *plan) {
     BfStage *st = &plan->stages[s];
     bfdevFree(st->dItems); st->dItems = NULL;
     bfdevFree(st->dPieces); st->dPieces = NULL;
-    bfdevFree(st->dBundleBegin); st->dBundleBegin = NULL;
     bfdevFree(st->dTickets); st->dTickets = NULL;
     for (uint64_t r = 0; r < st->numReduce; ++r) {
       bfdevFree(st->reduce[r].dRowInterval); bfdevFree(st->reduce[r].dIvBegin); bfdevFree(st->reduce[r].dSrcBias);
@@ -311,7 +310,6 @@ static int uploadPlanMeta(BfhipOperator *op, BfPlan *plan) {
     BfStage *st = &plan->stages[s];
     rc = uploadArray(&st->dItems, st->items, st->numItems * sizeof(BfDevItem), &op->metaBytes);
     if (!rc) rc = uploadArray(&st->dPieces, st->pieces, st->numPieces * sizeof(BfDevPiece), &op->metaBytes);
-    if (!rc && st->bundleBegin) rc = uploadArray(&st->dBundleBegin, st->bundleBegin, (st->numBundles + 1) * 4, &op->metaBytes);      /* forward complex128 */
     for (uint64_t r = 0; r < st->numReduce && !rc; ++r) {
       BfReduce *rd = &st->reduce[r];
       rc = uploadArray(&rd->dRowInterval, rd->rowInterval, rd->numRows * 4, &op->metaBytes);
@@ -733,7 +731,6 @@ static void stageLaunchArgs(BfhipOperator const *op, BfPlan const *plan, BfStage
   a->transposed = plan->transposed;
   a->tickets = NULL;
   a->exactComplex = (op->flags & BFHIP_FLAG_EXACT_COMPLEX) != 0; a->rhsBlocks = plan == &op->plan ? op->rhsBlocks : 0;      /* the adjoint's plans (shared or packed) keep their kernels */
-  a->bundles = st->dBundleBegin; a->numBundles = st->numBundles;
 }
 
 static int runPlan(BfhipOperator *op, BfPlan *plan, void const *dX, size_t nrhs, void *dY, void *stream) {
@@ -1488,12 +1485,6 @@ static int loadPlan(FILE *fp, BfhipOperator *op, BfPlan *pl, FileHeader const *f
         }
         st->numCoopNarrow = bfPlanCountCoop(hItems, hPieces, st->numNarrow, pl->elemSize);
         st->numCoop = bfPlanCountCoop((BfDevItem const *)hItems + st->numNarrow, hPieces, st->numItems - st->numNarrow, pl->elemSize);
-      }
-      if (!rc && pl->dtype == BFHIP_C128 && !pl->transposed && st->numItems) {
-        uint32_t *bb = NULL;
-        rc = bfPlanBundles(hItems, hPieces, st->numItems, &bb, &st->numBundles);
-        if (!rc) rc = uploadArray(&st->dBundleBegin, bb, (st->numBundles + 1) * 4, &op->metaBytes);
-        free(bb);
       }
     }
     free(hItems); free(hPieces);

@@ -1370,8 +1370,6 @@ int bfdevLaunchStage(BfLaunchArgs const *a, void *stream) {
   p.numItems = (uint32_t)a->numItems;
   p.nrhs = a->nrhs;
   p.coopItems = 0;
-  p.numBundles = (uint32_t)a->numBundles;
-  p.bundles = (uint32_t const *)a->bundles;
   p.x = a->x;
   p.y = a->y;
   p.temp = a->temp;
@@ -1405,16 +1403,13 @@ int bfdevLaunchStage(BfLaunchArgs const *a, void *stream) {
     }
     else if (L[i].kernel <= BFHIP_KERNEL_C128_MFMA4_EXACT) {
       dim3 const g((uint32_t)((a->numItems + BF_MF_WG_WAVES - 1) / BF_MF_WG_WAVES)), b(64 * BF_MF_WG_WAVES);
-      /* more than 32 right-hand sides: one workgroup of four wavefronts per BUNDLE of items that read the same X rows */
-      if (a->nrhs > 32 && BF_MF_BUNDLES && (!a->bundles || !a->numBundles)) return bfhipFail(BFABI_ERROR_RUNTIME_ERROR, "internal: a forward complex128 stage without its bundle table");
-      dim3 const gB(BF_MF_BUNDLES ? (uint32_t)a->numBundles : g.x), bB(BF_MF_BUNDLES ? 256u : b.x);
       switch (L[i].kernel) {
         case BFHIP_KERNEL_C128_MFMA1_EXACT: hipLaunchKernelGGL(bfStageKernelC128Mfma1Exact, g, b, 0, s, p); break;   /* BFHIP_FLAG_EXACT_COMPLEX: four real products per complex one */
         case BFHIP_KERNEL_C128_MFMA2_EXACT: hipLaunchKernelGGL(bfStageKernelC128Mfma2Exact, g, b, 0, s, p); break;
-        case BFHIP_KERNEL_C128_MFMA4_EXACT: hipLaunchKernelGGL(bfStageKernelC128MfmaExact, gB, bB, 0, s, p); break;
+        case BFHIP_KERNEL_C128_MFMA4_EXACT: hipLaunchKernelGGL(bfStageKernelC128MfmaExact, g, b, 0, s, p); break;
         case BFHIP_KERNEL_C128_MFMA1: hipLaunchKernelGGL(bfStageKernelC128Mfma1, g, b, 0, s, p); break;               /* one RHS tile: 5 wavefronts per SIMD */
         case BFHIP_KERNEL_C128_MFMA2: hipLaunchKernelGGL(bfStageKernelC128Mfma2, g, b, 0, s, p); break;               /* two: 3 */
-        default: hipLaunchKernelGGL(bfStageKernelC128Mfma, gB, bB, 0, s, p); break;                                   /* up to four per pass: 2 */
+        default: hipLaunchKernelGGL(bfStageKernelC128Mfma, g, b, 0, s, p); break;                                     /* up to four per pass: 2 */
       }
     }
     else {

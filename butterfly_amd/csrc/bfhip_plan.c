@@ -560,8 +560,8 @@ static int cmpItemCost(void const *pa, void const *pb) {
  * list is ordered run by run (cmpItemBundle), big first by cost bucket: list neighbours run side by side on one XCD (the 64-RHS
  * kernel's workgroup mapping) and walk the same X panel at the same time, so that a row of it is fetched into that L2 once.  Round 4
  * ordered by the FIRST input only: groups that share their first block but not the others sat in between.  Same box, N = 262144, 64
- * RHS: 30.3 - 30.6 ms against 30.8 - 31.0.  (The runs are also what the A/B kernel of bfhip_stage_mfma.h, BF_MF_BUNDLES, takes as
- * workgroups.) */
+ * RHS: 30.3 - 30.6 ms against 30.8 - 31.0.  (The runs are also what the set-aside shared-X kernel of round 5 took as workgroups:
+ * DESIGN.md section 9, tools/mfma_setaside_loops.h.) */
 static int cmpItemSig(void const *pa, void const *pb) {
   ItemTmp const *a = pa, *b = pb;
   if (a->sig != b->sig) return a->sig < b->sig ? -1 : 1;
@@ -606,12 +606,13 @@ static int cmpU64(void const *pa, void const *pb) {
 }
 static uint64_t roundUp(uint64_t v, uint64_t m) { return (v + m - 1) / m * m; }
 
-/* Bundles of a forward complex128 stage, from its final item list: the workgroups of the 64-RHS matrix-core kernel, up to
+/* Bundles of a forward complex128 stage, from its final item list: what the set-aside shared-X kernel took as workgroups and what
+ * bfhipPlanGetStage reports of the list's X sharing (no kernel of the product reads the table), up to
  * BF_BUNDLE_ITEMS list neighbours each (bundleBegin[numBundles + 1]: first item, bit 31 = BF_BUNDLE_MIXED; the last entry = numItems).
  *   shared:  exactly BF_BUNDLE_ITEMS items of <= 32 rows and the same number of 16-row slabs whose pieces read the same input rows in
  *            the same order -- the wavefronts fetch every X tile once for all of them;
  *   mixed:   any other neighbours (taller items, zero fills, different inputs): four unrelated one-wavefront passes.
- * Derived from (items, pieces) alone, so that a loaded plan and a row shard get theirs the same way. */
+ * Derived from (items, pieces) alone. */
 static int sameBundleInputs(BfDevItem const *a, BfDevItem const *c, BfDevPiece const *pieces) {
   if (!a->numPieces || c->numPieces != a->numPieces || (a->mrFlags & 0xffffu) > 32u || (c->mrFlags & 0xffffu) > 32u ||
       ((c->mrFlags & 0xffffu) > 16u) != ((a->mrFlags & 0xffffu) > 16u)) return 0;
@@ -1009,7 +1010,7 @@ int bfPlanBuild(BfIr const *ir, BfPlanOptions const *po, BfPlan *plan) {
      * fills the GEMV kernel's lanes through column groups. */
     uint64_t numItems = 0;
 #ifndef BF_PLAN_BUNDLE_ORDER
-#define BF_PLAN_BUNDLE_ORDER 1     /* 1 = runs of equal inputs kept together (product); A/B builds: 0 = items by cost bucket and first input (round 4), 2 = full bundles first, leftovers after (for -DBF_MF_BUNDLES=1 kernels) */
+#define BF_PLAN_BUNDLE_ORDER 1     /* 1 = runs of equal inputs kept together (product); A/B builds: 0 = items by cost bucket and first input (round 4), 2 = full bundles first, leftovers after (what the set-aside shared-X kernel ran on: DESIGN.md section 9) */
 #endif
     int const bundled = BF_PLAN_BUNDLE_ORDER && po->groupByInput && !T && bfDtypeC128Layout(plan->dtype);
     for (uint64_t g = 0; g < numGroups; ++g) {

@@ -578,7 +578,8 @@ typedef struct BfhipStageView {
   const void *items;      /* BfDevItem[numItems]  (16 bytes each) */
   const void *pieces;     /* BfDevPiece[numPieces] (24 bytes each) */
   /* filled when structSize covers them: forward complex128 stages -- runs of up to 4 list neighbours that read the same input rows
-   * (one workgroup of the 64-RHS kernel each: its wavefronts fetch every X tile once); bundleBegin[numBundles + 1] */
+   * (bit 31 of an entry: unrelated neighbours); bundleBegin[numBundles + 1].  A description of the list's X sharing: no kernel reads
+   * it.  Operators without the planner's host tables (bfhipLoad) report numBundles = 0 and a NULL table */
   uint64_t numBundles;
   const uint32_t *bundleBegin;
 } BfhipStageView;

@@ -111,8 +111,9 @@ def test_hand_counted_waits_of_the_rhs_block_kernels_hold_in_the_compiled_code(t
     vmcnt(n) there one short; (b) it may read, copy or reuse a fragment register before the wait that retires its load (it did, in
     round 5: a v_mov between a ds_read and its s_waitcnt in some instantiations of the LDS-ring loop).  Audit of the compiled
     code (tests/asm_audit.py replays the in-order counters over the instruction stream): in every innermost MFMA loop of all six
-    kernels (three tile counts x Gauss / exact) and of the LDS-ring build the only vector-memory instructions are the expected
-    buffer_load_dwordx4, and inside those loops no instruction touches a register a pending load may still write."""
+    kernels (three tile counts x Gauss / exact) the only vector-memory instructions are the expected buffer_load_dwordx4, in those
+    of the LDS-ring loop that was set aside (tools/mfma_setaside_loops.h, as tools/mfma_loop_probe.hip instantiates it) that and
+    its `lds` form, and inside those loops no instruction touches a register a pending load may still write."""
     import shutil
     import subprocess
     import sys
@@ -127,20 +128,34 @@ def test_hand_counted_waits_of_the_rhs_block_kernels_hold_in_the_compiled_code(t
     if not os.path.exists(hipcc):
         import pytest
         pytest.skip("no hipcc")
-    for tag, defs in (("product", []), ("ring", ["-DBF_MF_DMA=1"])):
-        out = tmp_path / f"dev_{tag}.s"
-        subprocess.check_call([hipcc, "-O3", "-g", "-fPIC", "--offload-arch=gfx950", "-std=c++17", "-S", "--cuda-device-only", *defs, "-o", str(out),
-                               os.path.join(ROOT, "butterfly_amd", "csrc", "bfhip_device.hip")], stderr=subprocess.DEVNULL)
-        txt = open(out).read()
-        syms = re.findall(r"^(_Z\d+bfStageKernelC128Mfma\w*11StageParams):", txt, flags=re.M)
-        assert len(syms) == 6, syms
-        for sym in syms:
-            loops = asm_audit.loop_vmem(txt, sym)
-            assert loops, sym
-            for mfmas, vm in loops:
-                assert mfmas % 2 == 0 and vm and set(vm) <= {"buffer_load_dwordx4", "buffer_load_dwordx4 lds"}, (sym, mfmas, vm)
-            bad = asm_audit.audit(txt, sym)
-            assert not bad, (tag, sym, bad[:4])
+    flags = ["-O3", "-g", "-fPIC", "--offload-arch=gfx950", "-std=c++17", "-S", "--cuda-device-only"]
+    csrc = os.path.join(ROOT, "butterfly_amd", "csrc")
+    # the product: six kernels, register loops only
+    out = tmp_path / "dev_product.s"
+    subprocess.check_call([hipcc, *flags, "-o", str(out), os.path.join(csrc, "bfhip_device.hip")], stderr=subprocess.DEVNULL)
+    txt = open(out).read()
+    syms = re.findall(r"^(_Z\d+bfStageKernelC128Mfma\w*11StageParams):", txt, flags=re.M)
+    assert len(syms) == 6, syms
+    for sym in syms:
+        loops = asm_audit.loop_vmem(txt, sym)
+        assert loops, sym
+        for mfmas, vm in loops:
+            assert mfmas % 2 == 0 and vm and set(vm) <= {"buffer_load_dwordx4"}, (sym, mfmas, vm)
+        bad = asm_audit.audit(txt, sym)
+        assert not bad, ("product", sym, bad[:4])
+    # the LDS-ring loop, set aside beside its probe (tools/mfma_setaside_loops.h): every probeLoop<NT, MS, WPS, DMA = true>
+    out = tmp_path / "dev_ring.s"
+    subprocess.check_call([hipcc, *flags, "-I", csrc, "-o", str(out), os.path.join(ROOT, "tools", "mfma_loop_probe.hip")], stderr=subprocess.DEVNULL)
+    txt = open(out).read()
+    syms = re.findall(r"^(_Z9probeLoopILi\d+ELi\d+ELi\d+ELb1EE\w+):", txt, flags=re.M)
+    assert syms, "no probeLoop<..., DMA = true> in tools/mfma_loop_probe.hip"
+    for sym in syms:
+        loops = asm_audit.loop_vmem(txt, sym)
+        assert loops, sym
+        for mfmas, vm in loops:
+            assert mfmas % 2 == 0 and vm and set(vm) <= {"buffer_load_dwordx4", "buffer_load_dwordx4 lds"}, (sym, mfmas, vm)
+        bad = asm_audit.audit(txt, sym)
+        assert not bad, ("ring", sym, bad[:4])
 
 
 def test_builder_structs_match_the_header_and_arguments_are_checked(tmp_path):

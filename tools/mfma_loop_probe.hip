@@ -19,11 +19,12 @@
 #include "../butterfly_amd/csrc/bfhip_stage_c128.h"
 
 #include "../butterfly_amd/csrc/bfhip_stage_mfma.h"
+#include "mfma_setaside_loops.h"
 
 #define CHECK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "%s: %s\n", #x, hipGetErrorString(e_)); exit(1); } } while (0)
 
 #define PROBE_COLS 1792u
-// DMA: the loop that prefetches its fragments through the wavefront's LDS ring (bfMfmaSegmentDma) instead of bfMfmaSegment
+// DMA: the loop that prefetches its fragments through the wavefront's LDS ring (bfMfmaSegmentDma of mfma_setaside_loops.h) instead of bfMfmaSegment
 template <int NT, int MS, int WPS, bool DMA>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPS, WPS))) void probeLoop(double *out, char const *A, char const *X, uint64_t aStride, uint32_t aBytes,
                                                                                              uint32_t xRows, uint32_t reps, uint32_t cols, uint32_t aWaves) {

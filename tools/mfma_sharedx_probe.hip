@@ -19,6 +19,7 @@
 #include "../butterfly_amd/csrc/bfhip_stage_c128.h"
 
 #include "../butterfly_amd/csrc/bfhip_stage_mfma.h"
+#include "mfma_setaside_loops.h"
 
 #define CHECK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "%s: %s\n", #x, hipGetErrorString(e_)); exit(1); } } while (0)
 
@@ -56,7 +57,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPS, WPS)))
   sg.voffA = (lk * mr + li) * 16u;
   sg.cX = li * 16u;
   uint32_t const ring = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)ringMem);
-  for (uint32_t r = 0; r < reps; ++r) bfSxSegment<MS, true>(acc, sg, tab, lk, ring, lane, mine);      // the product's loop (bfhip_stage_mfma.h)
+  for (uint32_t r = 0; r < reps; ++r) bfSxSegment<MS, true>(acc, sg, tab, lk, ring, lane, mine);      // the shared-X loop, set aside (mfma_setaside_loops.h)
   double sum = 0;
 #pragma unroll
   for (int g = 0; g < 3; ++g)
