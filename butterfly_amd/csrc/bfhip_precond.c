@@ -491,7 +491,7 @@ int bfhipBlockJacobi(BfhipOperator *op, BfhipBlockJacobiOptions const *opt, Bfhi
     }
     minPivotRel = nb ? mpr : NAN;
     if (firstSingular >= 0) {
-      rc = bfhipFail(BFABI_ERROR_RUNTIME_ERROR, "diagonal block %lld (rows %llu..%llu) has a zero or non-finite pivot at step %u", (long long)firstSingular,
+      rc = bfhipFail(BFABI_ERROR_RUNTIME_ERROR, "diagonal block %lld (rows %llu..%llu) has a zero or non-finite pivot, pivot reciprocal or scaled pivot row at step %u", (long long)firstSingular,
                      (unsigned long long)cuts[firstSingular], (unsigned long long)cuts[firstSingular + 1], res[firstSingular].step);
       goto out;
     }

@@ -14,7 +14,8 @@
 //     below the diagonal, ties to the smaller row; rows k and p are swapped; the scaled pivot row goes to LDS (rowK, its
 //     k-th entry 1/pivot) with the eliminated column (colF); then every entry is updated, A(i, j) = [j != k] A(i, j) - colF(i)
 //     rowK(j) for i != k and A(k, j) = rowK(j).  At the end the columns are swapped back in reverse step order.  A zero or
-//     non-finite pivot stops the block and is reported (status, step); the host refuses the build.
+//     non-finite pivot stops the block and is reported (status, step); so does a pivot whose reciprocal is not finite (a
+//     subnormal pivot: 1 / 2^-1074 overflows) and a scaled pivot row with a non-finite entry.  The host refuses the build.
 //   * fill: writes a piece of the result's arena (its plan's column-major mrPad x ncols or row-major mr x ld layout, padding
 //     zero) from the working copy, rounding to the result's element type on the store.
 //
@@ -69,6 +70,8 @@ __device__ __forceinline__ double bjAbs1(double2 v) { return fabs(v.x) + fabs(v.
 __device__ __forceinline__ double bjAbs1(double v) { return fabs(v); }
 __device__ __forceinline__ double bjAbs(double2 v) { return hypot(v.x, v.y); }
 __device__ __forceinline__ double bjAbs(double v) { return fabs(v); }
+__device__ __forceinline__ bool bjFinite(double2 v) { return fabs(v.x) <= 1.79769313486231570815e308 && fabs(v.y) <= 1.79769313486231570815e308; }
+__device__ __forceinline__ bool bjFinite(double v) { return fabs(v) <= 1.79769313486231570815e308; }
 template <typename W> __device__ __forceinline__ W bjZero();
 template <> __device__ __forceinline__ double2 bjZero<double2>() { return make_double2(0.0, 0.0); }
 template <> __device__ __forceinline__ double bjZero<double>() { return 0.0; }
@@ -116,6 +119,7 @@ __global__ __launch_bounds__(BF_BJ_THREADS) void bfBjInvertKernel(W *__restrict_
   __shared__ double key[BF_BJ_THREADS];
   __shared__ uint32_t kidx[BF_BJ_THREADS];
   __shared__ uint32_t perm[BF_BJ_MAX_M];
+  __shared__ uint32_t rowBad;               // a scaled pivot row held a non-finite entry (set once, the block stops)
   BfBjBlock const B = blocks[blockIdx.x];
   W *A = ws + B.wsOff;
   uint32_t const m = B.m < BF_BJ_MAX_M ? B.m : BF_BJ_MAX_M, tid = threadIdx.x;
@@ -129,6 +133,7 @@ __global__ __launch_bounds__(BF_BJ_THREADS) void bfBjInvertKernel(W *__restrict_
     mx = (a != a) ? INFINITY : fmax(mx, a);
   }
   key[tid] = mx;
+  if (tid == 0) rowBad = 0;
   __syncthreads();
   for (uint32_t s = BF_BJ_THREADS / 2; s > 0; s >>= 1) {
     if (tid < s) key[tid] = fmax(key[tid], key[tid + s]);
@@ -160,19 +165,23 @@ __global__ __launch_bounds__(BF_BJ_THREADS) void bfBjInvertKernel(W *__restrict_
     uint32_t const p = kidx[0];
     W const piv = A[p * m + k];             // the same value in every thread: the break below is uniform
     double const pa = bjAbs(piv);
-    if (!(pa > 0.0) || !(pa <= 1.79769313486231570815e308)) { status = 1; stepBad = k; break; }
+    W const inv = bjRecip(piv);
+    // a zero or non-finite pivot, or a finite one whose reciprocal overflows (subnormal pivots)
+    if (!(pa > 0.0) || !(pa <= 1.79769313486231570815e308) || !bjFinite(inv)) { status = 1; stepBad = k; break; }
     minPiv = fmin(minPiv, pa);
     __syncthreads();                        // every thread has read row p's entry and kidx[0] before they change
     if (p != k)
       for (uint32_t c = tid; c < m; c += BF_BJ_THREADS) { W const t = A[k * m + c]; A[k * m + c] = A[p * m + c]; A[p * m + c] = t; }
     if (tid == 0) perm[k] = p;
     __syncthreads();
-    W const inv = bjRecip(piv);
     for (uint32_t c = tid; c < m; c += BF_BJ_THREADS) {
-      rowK[c] = c == k ? inv : bjMul(A[k * m + c], inv);
+      W const rk = c == k ? inv : bjMul(A[k * m + c], inv);
+      if (!bjFinite(rk)) rowBad = 1;        // every writer stores the same value
+      rowK[c] = rk;
       colF[c] = c == k ? bjZero<W>() : A[c * m + k];
     }
     __syncthreads();
+    if (rowBad) { status = 1; stepBad = k; break; }     // read after the barrier by every thread: uniform
     if (g < groups) {
       W const rk = rowK[j];
       for (uint32_t i = g; i < m; i += groups) {

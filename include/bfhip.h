@@ -474,8 +474,10 @@ int bfhipSolveGMRESRefine(BfhipOperator *op, BfhipOperator *opLow, const BfhipGm
  * flags, maxBlock > 256, cuts that are not strictly increasing from 0 to n or have a block over maxBlock, an automatic
  * interval over maxBlock), TYPE_ERROR (an outDtype the operator's dtype cannot be demoted to), NOT_IMPLEMENTED
  * (bfhipBlockJacobi on a BFHIP_FLAG_PLAN_ONLY operator, after every check above), RUNTIME_ERROR (a block with a zero or
- * non-finite pivot: info.firstSingularBlock is set and no operator is made), MEMORY_ERROR.  Sharded operators are not
- * supported; blocks are contiguous and at most 256 rows. */
+ * non-finite pivot, with a pivot whose reciprocal is not finite -- a subnormal pivot such as 2^-1074 -- or with a non-finite
+ * entry in a scaled pivot row; the inversion kernel tests each at the step it occurs and the message names block and step:
+ * info.firstSingularBlock is set and no operator is made), MEMORY_ERROR.  Sharded operators are not supported; blocks are
+ * contiguous and at most 256 rows. */
 #define BFHIP_BJ_NO_INVERT 1u
 #define BFHIP_BJ_MAX_BLOCK 256u
 typedef struct BfhipBlockJacobiOptions {

@@ -14,109 +14,10 @@ from butterfly_amd import _capi, helm2_structure as hs
 from butterfly_amd.operator import HipOperator
 from oracle import helm2_build as hb, linalg_ref
 import bie
+from bj_ref import direct_blocks, self_leaf_cuts
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N, K = 2048, 128
-
-BF_ITEM_OUT_Y = 1 << 16
-BF_PIECE_IN_X, BF_PIECE_IDENTITY, BF_PIECE_ROWMAJOR = 1, 2, 4
-
-
-def _view(ptr, count, dtype):
-    if count == 0:
-        return np.zeros(0, dtype=dtype)
-    return np.frombuffer((C.c_char * (count * dtype.itemsize)).from_address(ptr), dtype=dtype)
-
-
-def direct_blocks(op, cuts):
-    """Numpy restatement of the direct-part rule: the pieces that read x and write y, or write vector-arena rows a reduce of
-    the same stage sums into y; identity pieces are identity entries.  Returns [B_b] with B_b = A_dir[D_b, D_b]."""
-    lib = _capi.load()
-    info = _capi.BfhipPlanInfo()
-    info.structSize = C.sizeof(info)
-    _capi.check(lib.bfhipPlanGetInfo(op.handle, C.byref(info)))
-    dt = {0: np.complex128, 1: np.float64, 2: np.float32, 3: np.complex64}[info.dtype]
-    arena = np.zeros(int(info.arenaElems), dtype=dt)
-    _capi.check(lib.bfhipPlanPackArena(op.handle, arena.ctypes.data))
-    n, epl = int(info.numRows), int(info.epl)
-    adir = np.zeros((n, n), dtype=np.complex128 if np.iscomplexobj(arena) else np.float64)
-    for s in range(int(info.numStages)):
-        sv = _capi.BfhipStageView()
-        sv.structSize = C.sizeof(sv)
-        _capi.check(lib.bfhipPlanGetStage(op.handle, s, C.byref(sv)))
-        items = _view(sv.items, int(sv.numItems), _capi.ITEM_DTYPE)
-        pieces = _view(sv.pieces, int(sv.numPieces), _capi.PIECE_DTYPE)
-        tmap = {}          # vector-arena row -> y row, from this stage's y-reduces
-        for r in range(int(sv.numReduce)):
-            rv = _capi.BfhipReduceView()
-            rv.structSize = C.sizeof(rv)
-            _capi.check(lib.bfhipPlanGetReduce(op.handle, s, r, C.byref(rv)))
-            if not rv.destIsY:
-                continue
-            row_iv = _view(rv.rowInterval, int(rv.numRows), np.dtype("<u4"))
-            iv_begin = _view(rv.ivBegin, int(rv.numIntervals) + 1, np.dtype("<u4"))
-            bias = _view(rv.srcBias, int(rv.numSrc), np.dtype("<i8"))
-            for row in range(int(rv.numRows)):
-                iv = int(row_iv[row])
-                if iv == 0xFFFFFFFF:
-                    continue
-                for q in range(int(iv_begin[iv]), int(iv_begin[iv + 1])):
-                    tmap[int(bias[q]) + row] = row
-        for it in items:
-            mr = int(it["mrFlags"]) & 0xFFFF
-            mr_pad = (mr + epl - 1) // epl * epl
-            if int(it["mrFlags"]) & BF_ITEM_OUT_Y:
-                yrows = np.arange(int(it["outOff"]), int(it["outOff"]) + mr)
-            else:
-                yrows = np.array([tmap.get(int(it["outOff"]) + i, -1) for i in range(mr)])
-            keep = yrows >= 0
-            if not keep.any():
-                continue
-            for pc in pieces[int(it["pieceBegin"]):int(it["pieceBegin"]) + int(it["numPieces"])]:
-                fl = int(pc["flags"])
-                if not fl & BF_PIECE_IN_X:
-                    continue
-                io, nc, d0 = int(pc["inOff"]), int(pc["ncols"]), int(pc["dataOff"])
-                if fl & BF_PIECE_IDENTITY:
-                    rows = np.nonzero(keep)[0]
-                    np.add.at(adir, (yrows[rows], io + rows), 1.0)
-                    continue
-                if fl & BF_PIECE_ROWMAJOR:
-                    ld = int(pc["ld"])
-                    blk = arena[d0:d0 + mr * ld].reshape(mr, ld)[:, :nc]
-                else:
-                    blk = arena[d0:d0 + mr_pad * nc].reshape(nc, mr_pad).T[:mr]
-                adir[yrows[keep], io:io + nc] += blk[keep]
-    return [adir[a:b, a:b] for a, b in zip(cuts[:-1], cuts[1:])]
-
-
-def self_leaf_cuts(desc, root, n):
-    """The diagonal dense self-leaves, from the descriptor alone: dense leaves reached through BLOCK nodes (never a product)
-    that sit on the diagonal; identity leaves cover single rows.  Merged into intervals the way the rule merges pieces."""
-    reach = -np.ones(n, dtype=np.int64)
-
-    def walk(node, r0, c0):
-        kind = desc.kind[node]
-        if kind == hs.NODE_BLOCK:
-            for c, dr, dc in desc.children[node]:
-                walk(c, r0 + dr, c0 + dc)
-        elif kind == hs.NODE_DENSE and r0 == c0 and desc.rows[node] == desc.cols[node]:
-            reach[r0] = max(reach[r0], r0 + desc.rows[node])
-        elif kind == hs.NODE_IDENTITY and r0 == c0:
-            for i in range(desc.rows[node]):
-                reach[r0 + i] = max(reach[r0 + i], r0 + i + 1)
-    walk(root, 0, 0)
-    cuts, i = [0], 0
-    while i < n:
-        end = i + 1 if reach[i] < 0 else int(reach[i])
-        j = i + 1
-        while j < end:
-            end = max(end, int(reach[j]))
-            j += 1
-        cuts.append(end)
-        i = end
-    return np.array(cuts)
-
 
 @pytest.fixture(scope="module")
 def operands():
