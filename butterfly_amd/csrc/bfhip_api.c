@@ -1,11 +1,9 @@
-/* bfhip_api.c -- the C-ABI of include/bfhip.h: operator lifetime, compile
- * (IR -> plan -> HBM), apply, profiling, and the BfMat vtable shim that makes
- * the device operator a drop-in behind the reference's bfMatMul / bfMatMulVec
- * (reference src/mat.c:183-189; precedent for a foreign operator behind the
- * vtable: BfMatFunc, include/bf/mat_func.h:5-28, src/mat_func.c:59-82).
+/* bfhip_api.c -- the C-ABI of include/bfhip.h: errors, operator lifetime, compile (IR -> plan -> HBM), profiling and
+ * apply.  The other parts of the ABI that work on struct BfhipOperator (bfhip_operator.h) are bfhip_file.c (save / load),
+ * bfhip_shim.c (the BfMat vtable shim) and bfhip_inspect.c (plan inspection, kernel names).
  */
 #define _GNU_SOURCE
-#include "bfhip_internal.h"
+#include "bfhip_operator.h"
 #include "../../include/bfhip_abi.h"
 #include "../../include/bfhip_synth.h"
 
@@ -47,56 +45,6 @@ int bfhipSyntheticLeafBases(BfhipDesc const *desc, uint64_t *bases) {
 }
 
 /* ---- operator --------------------------------------------------------------- */
-struct BfhipOperator {
-  BfPlan plan;
-  BfPlan tplan;               /* plan of A^T over the same leaf arena (BFHIP_FLAG_ADJOINT) */
-  int hasTplan;
-  uint32_t srcDtype;          /* dtype of the operand as given (C128 / F64) */
-  int device;
-  uint32_t flags;
-  void *dArena;               /* leaf data */
-  void *dArenaT;              /* BFHIP_FLAG_ADJOINT_PACKED: the leaves of A^T packed for tplan, a FORWARD plan of the transposed expression */
-  void *dTemp;                /* vector arena: intermediates + partial slots, tempElems * maxRhs */
-  void *dZero;                /* 4 KiB of zeros */
-  uint32_t tempRhs;
-  uint64_t metaBytes;
-  uint64_t leafBytesAlgorithmic;
-  /* staging for the host-pointer apply */
-  void *dX, *dY;
-  void *hX, *hY;              /* pinned host mirrors of dX / dY */
-  void *evHost[4];            /* "piece i of the result is in hY" (created on first use) */
-  uint32_t xyRhs;
-  /* profiling */
-  void **evStart, **evStop;   /* [BF_EV_POOL][numStages]: one set per apply in flight, so timing an apply never waits for the one before */
-  double *stageMs;
-  uint64_t *stageLaunches;
-  uint32_t lastNrhs;
-  uint64_t evIssued, evHarvested;   /* applies whose events were recorded / read back */
-  uint64_t applyCount;              /* forward applies so far */
-  void *dCov;                       /* scratch of the covariance products (2 vectors of the longer side) */
-  uint32_t profEvery;               /* events around one apply in profEvery (0, 1: every apply) */
-  /* BFHIP_FLAG_PLAN_ONLY: the IR is kept (borrowed leaf pointers!) for bfhipPlanPackArena; irT: its transposed view when the
-   * adjoint plan has an arena of its own (BFHIP_FLAG_ADJOINT_PACKED), for bfhipPlanPackArenaT */
-  BfIr *ir, *irT;
-  int packedT;
-  uint64_t seed;
-  /* dependency-driven launch of the forward plan (complex128, one right-hand side): flat copies of the index tables */
-  int flow;
-  void *dFlowItems, *dFlowPieces, *dFlowItemOut, *dFlowWriters, *dFlowCounters;
-  uint32_t flowNumItems, flowGrid, flowEpoch, flowQueueBase, flowMaxWriters;
-  uint64_t flowNumBufs;
-  uint8_t evFlow[64];               /* per event set: that apply ran as ONE launch (its time is recorded under stage 0) */
-  uint32_t rhsBlocks;               /* bfhipSetRhsBlocks: 0 = off, else the smallest nrhs whose forward stages run the complex64 block kernels */
-  uint64_t hostApplyBudget;         /* device bytes the host-vector apply may use for vectors; 0 = free memory - BF_HOST_BUDGET_MARGIN */
-  void *extract;                    /* workspace of the dense extraction (bfhip_extract.c), released by extractRelease */
-  void (*extractRelease)(void *);
-};
-
-#define BF_ARENA_SLACK 256u
-#define BF_HOST_PIECE_ROWS 8192u    /* host vectors of more than 4 x this many rows cross PCIe in 4 pieces, copy and DMA overlapped */
-#define BF_EV_POOL 64u
-#define BF_HOST_BUDGET_MARGIN (512ull << 20)   /* automatic host-apply budget: what the device has free, less this */
-
 static void freeDevicePlanOf(BfPlan *plan) {
   for (uint64_t s = 0; s < plan->numStages && plan->stages; ++s) {
     BfStage *st = &plan->stages[s];
@@ -230,7 +178,7 @@ static int packPiece(BfPlan const *pl, BfIr const *ir, BfDevPiece const *pc, BfP
  * write everything (synthetic leaves included) to host memory; else upload
  * host-valued leaves through a staging buffer and synthesize the rest on the
  * device. */
-static int packLeavesPlan(BfPlan const *pl, void *dArena, BfIr const *ir, uint64_t seed, void *hostDst) {
+int packLeavesPlan(BfPlan const *pl, void *dArena, BfIr const *ir, uint64_t seed, void *hostDst) {
   size_t const es = pl->elemSize;
   int const cplx = bfDtypeComplex(pl->dtype);
   size_t const chunkBytes = (size_t)64 << 20;
@@ -429,6 +377,28 @@ static int ensureTemp(BfhipOperator *op, uint32_t nrhs) {
   return 0;
 }
 
+/* what compile and load end with: the vector arena for maxRhs right-hand sides (0: one), the zero buffer and, under
+ * BFHIP_FLAG_PROFILE, the per-stage timing arrays and the event pool */
+int finishOperator(BfhipOperator *op, uint32_t maxRhs) {
+  int rc;
+  if ((rc = ensureTemp(op, maxRhs ? maxRhs : 1))) return rc;
+  if ((rc = bfdevMalloc(&op->dZero, 4096))) return rc;
+  if ((rc = bfdevMemset(op->dZero, 0, 4096))) return rc;
+  if (op->flags & BFHIP_FLAG_PROFILE) {
+    uint64_t S = op->plan.numStages;
+    op->evStart = calloc(BF_EV_POOL * S, sizeof(void *));
+    op->evStop = calloc(BF_EV_POOL * S, sizeof(void *));
+    op->stageMs = calloc(S, sizeof(double));
+    op->stageLaunches = calloc(S, sizeof(uint64_t));
+    if (!op->evStart || !op->evStop || !op->stageMs || !op->stageLaunches) return bfhipFail(BFABI_ERROR_MEMORY_ERROR, "host OOM");
+    for (uint64_t s = 0; s < BF_EV_POOL * S && !rc; ++s) {
+      rc = bfdevEventCreate(&op->evStart[s]);
+      if (!rc) rc = bfdevEventCreate(&op->evStop[s]);
+    }
+  }
+  return rc;
+}
+
 /* The adjoint plan over the forward plan's packed leaves (BFHIP_FLAG_ADJOINT): index metadata only.  Needs the forward plan's
  * host mirrors.  Row-range / row-block shards: the transposed plan of the shard's own tasks (bfPlanBuild prunes the same way). */
 static int buildSharedTplan(BfhipOperator *op, BfIr const *ir, BfPlanOptions const *po) {
@@ -574,21 +544,7 @@ int bfhipCompileIrFill(BfIr *ir, BfhipOptions const *opts, BfFillFn fill, void *
   /* host mirrors of the bulky per-piece arrays are no longer needed */
   dropPlanMirrors(&op->plan);
   dropPlanMirrors(&op->tplan);
-  if ((rc = ensureTemp(op, o.maxRhs ? o.maxRhs : 1))) goto done;
-  if ((rc = bfdevMalloc(&op->dZero, 4096))) goto done;
-  if ((rc = bfdevMemset(op->dZero, 0, 4096))) goto done;
-  if (op->flags & BFHIP_FLAG_PROFILE) {
-    uint64_t S = op->plan.numStages;
-    op->evStart = calloc(BF_EV_POOL * S, sizeof(void *));
-    op->evStop = calloc(BF_EV_POOL * S, sizeof(void *));
-    op->stageMs = calloc(S, sizeof(double));
-    op->stageLaunches = calloc(S, sizeof(uint64_t));
-    if (!op->evStart || !op->evStop || !op->stageMs || !op->stageLaunches) { rc = bfhipFail(BFABI_ERROR_MEMORY_ERROR, "host OOM"); goto done; }
-    for (uint64_t s = 0; s < BF_EV_POOL * S && !rc; ++s) {
-      rc = bfdevEventCreate(&op->evStart[s]);
-      if (!rc) rc = bfdevEventCreate(&op->evStop[s]);
-    }
-  }
+  if ((rc = finishOperator(op, o.maxRhs))) goto done;
 done:
   bfIrFree(ir);
   bfIrFree(&irT);
@@ -725,7 +681,7 @@ int bfhipSetProfileSampling(BfhipOperator *op, uint32_t every) {
 
 /* ---- apply ------------------------------------------------------------------ */
 /* what bfdevLaunchStage gets for stage `st` of `plan` (x and y left NULL) */
-static void stageLaunchArgs(BfhipOperator const *op, BfPlan const *plan, BfStage const *st, uint32_t nrhs, BfLaunchArgs *a) {
+void stageLaunchArgs(BfhipOperator const *op, BfPlan const *plan, BfStage const *st, uint32_t nrhs, BfLaunchArgs *a) {
   a->arena = (plan == &op->tplan && op->dArenaT) ? op->dArenaT : op->dArena; a->items = st->dItems; a->pieces = st->dPieces; a->numItems = st->numItems; a->firstSmall = st->firstSmall; a->numCoop = st->numCoop; a->numNarrow = st->numNarrow; a->numCoopNarrow = st->numCoopNarrow; a->maxRowsRest = st->maxRowsRest;
   a->x = NULL; a->y = NULL; a->temp = op->dTemp; a->zero = op->dZero; a->nrhs = nrhs; a->dtype = plan->dtype; a->maxRows = st->maxRows;
   a->transposed = plan->transposed;
@@ -1060,7 +1016,7 @@ static int hostApplyWidth(BfhipOperator *op, int transpose, void const *X, void 
   return 0;
 }
 
-static int applyHost(BfhipOperator *op, int transpose, void const *X, size_t ldx, size_t nrhs, void *Y, size_t ldy) {
+int applyHost(BfhipOperator *op, int transpose, void const *X, size_t ldx, size_t nrhs, void *Y, size_t ldy) {
   if (!op || !X || !Y) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL argument");
   if (transpose && !op->hasTplan) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "operator was not compiled with BFHIP_FLAG_ADJOINT");
   if (nrhs == 0 || ldx < nrhs || ldy < nrhs) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "bad nrhs / leading dimension");
@@ -1132,770 +1088,3 @@ void const *bfhipOperatorArena(BfhipOperator const *op) { return op ? op->dArena
 size_t bfhipGetNumRows(BfhipOperator const *op) { return op ? op->plan.numRows : 0; }
 size_t bfhipGetNumCols(BfhipOperator const *op) { return op ? op->plan.numCols : 0; }
 size_t bfhipNumBytes(BfhipOperator const *op) { return op ? op->plan.leafElems * (op->srcDtype == BFHIP_C128 ? 16 : 8) : 0; }
-
-int bfhipGetStats(BfhipOperator const *op, BfhipStats *st) {
-  if (!op || !st || st->structSize < sizeof(BfhipStats)) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "bad stats struct");
-  BfPlan const *pl = &op->plan;
-  st->dtype = pl->dtype;
-  st->numRows = pl->numRows; st->numCols = pl->numCols; st->numStages = pl->numStages;
-  st->numLeaves = pl->numLeaves;
-  st->numItems = 0; st->numPieces = 0; st->vecElemsRead = 0; st->vecElemsWritten = 0;
-  for (uint64_t s = 0; s < pl->numStages; ++s) {
-    st->numItems += pl->stages[s].numItems;
-    st->numPieces += pl->stages[s].numPieces;
-    st->vecElemsRead += pl->stages[s].vecIn;
-    st->vecElemsWritten += pl->stages[s].vecOut;
-  }
-  st->leafElems = pl->leafElems;
-  st->leafBytes = pl->leafElems * pl->elemSize;
-  st->arenaBytes = pl->arenaElems * pl->elemSize + (op->dArenaT ? op->tplan.arenaElems * op->tplan.elemSize : 0);      /* both packed copies with BFHIP_FLAG_ADJOINT_PACKED */
-  st->tempElems = pl->tempElems;
-  st->metaBytes = op->metaBytes;
-  return 0;
-}
-
-/* ---- plan inspection (BFHIP_FLAG_PLAN_ONLY) --------------------------------- */
-static int needPlanOnly(BfhipOperator const *op) {
-  if (!op) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL operator");
-  if (!(op->flags & BFHIP_FLAG_PLAN_ONLY)) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "plan inspection needs BFHIP_FLAG_PLAN_ONLY");
-  return 0;
-}
-int bfhipPlanGetInfo(BfhipOperator const *op, BfhipPlanInfo *info) {
-  int rc = needPlanOnly(op);
-  if (rc) return rc;
-  if (!info || info->structSize < sizeof *info) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "bad info struct");
-  BfPlan const *pl = &op->plan;
-  info->dtype = pl->dtype; info->elemSize = pl->elemSize; info->epl = pl->epl; info->xcap = pl->xcap;
-  info->numRows = pl->numRows; info->numCols = pl->numCols; info->numStages = pl->numStages;
-  info->arenaElems = pl->arenaElems; info->tempElems = pl->tempElems;
-  info->numStagesT = op->hasTplan ? op->tplan.numStages : 0;
-  info->tempElemsT = op->hasTplan ? op->tplan.tempElems : 0;
-  info->reserved = op->packedT ? 1u : 0u;                     /* 1: the adjoint plan is a forward plan over its own arena ... */
-  info->arenaElemsT = op->packedT ? op->tplan.arenaElems : 0;      /* ... of this many elements */
-  return 0;
-}
-int bfhipPlanGetStage(BfhipOperator const *op, uint64_t stage, BfhipStageView *v) {
-  int rc = needPlanOnly(op);
-  if (rc) return rc;
-  BfPlan const *pl = &op->plan;
-  if (stage >= pl->numStages && op->hasTplan) { stage -= pl->numStages; pl = &op->tplan; }
-  if (!v || v->structSize < offsetof(BfhipStageView, numBundles) || stage >= pl->numStages) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "bad stage view request");
-  BfStage const *st = &pl->stages[stage];
-  v->numItems = st->numItems; v->numPieces = st->numPieces; v->numReduce = st->numReduce;
-  v->items = st->items; v->pieces = st->pieces;
-  if (v->structSize >= sizeof *v) { v->numBundles = st->numBundles; v->bundleBegin = st->bundleBegin; }
-  return 0;
-}
-static char const *const kernelNames[BFHIP_KERNEL_COUNT] = {
-  "bfStageKernelC128", "bfStageKernelC128Mfma1", "bfStageKernelC128Mfma2", "bfStageKernelC128Mfma",
-  "bfStageKernelC128Mfma1Exact", "bfStageKernelC128Mfma2Exact", "bfStageKernelC128MfmaExact",
-  "bfStageKernelReal<F64>", "bfStageKernelReal<F32>", "bfStageKernelReal<C64>",
-  "bfStageKernelRealBoth<F64>", "bfStageKernelRealBoth<F32>", "bfStageKernelRealBoth<C64>",
-  "bfStageKernelSmall<F64>", "bfStageKernelSmall<F32>", "bfStageKernelSmall<C64>",
-#define BF_T_NAMES(DT) "bfStageKernelT<" DT ", narrow, nrhs>1>", "bfStageKernelT<" DT ", narrow, nrhs=1>", \
-                       "bfStageKernelT<" DT ", narrow, coop, nrhs>1>", "bfStageKernelT<" DT ", narrow, coop, nrhs=1>", \
-                       "bfStageKernelT<" DT ", wide, nrhs>1>", "bfStageKernelT<" DT ", wide, nrhs=1>", \
-                       "bfStageKernelT<" DT ", wide, coop, nrhs>1>", "bfStageKernelT<" DT ", wide, coop, nrhs=1>"
-  BF_T_NAMES("C128"), BF_T_NAMES("F64"), BF_T_NAMES("F32"), BF_T_NAMES("C64"),
-#undef BF_T_NAMES
-  "bfStageKernelTBoth<F64, nrhs>1>", "bfStageKernelTBoth<F64, nrhs=1>", "bfStageKernelTBoth<F32, nrhs>1>",
-  "bfStageKernelTBoth<F32, nrhs=1>", "bfStageKernelTBoth<C64, nrhs>1>", "bfStageKernelTBoth<C64, nrhs=1>",
-  "bfReduceKernel<C128>", "bfReduceKernel<F64>", "bfReduceKernel<F64, long>", "bfReduceKernel<F32>",
-  "bfReduceKernel<F32, long>", "bfReduceKernel<C64>", "bfReduceKernel<C64, long>",
-};
-static char const *const kernelNamesExt[BFHIP_KERNEL_EXT_END - BFHIP_KERNEL_EXT_BASE] = {
-  "bfStageKernelC64Mfma<1 tile>", "bfStageKernelC64Mfma<2 tiles>", "bfStageKernelC64Mfma<4 tiles>",
-};
-char const *bfhipKernelName(uint32_t id) {
-  if (id >= BFHIP_KERNEL_EXT_BASE && id < BFHIP_KERNEL_EXT_END) return kernelNamesExt[id - BFHIP_KERNEL_EXT_BASE];
-  return id < BFHIP_KERNEL_COUNT ? kernelNames[id] : NULL;
-}
-
-int bfhipPlanStageKernels(BfhipOperator const *op, uint64_t stage, uint32_t nrhs, uint32_t *ids, uint32_t cap, uint32_t *count) {
-  if (!op || !count || (cap && !ids) || !nrhs) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "bad stage kernel request");
-  BfPlan const *pl = &op->plan;
-  if (stage >= pl->numStages && op->hasTplan) { stage -= pl->numStages; pl = &op->tplan; }
-  if (stage >= pl->numStages) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "bad stage kernel request");
-  BfStage const *st = &pl->stages[stage];
-  BfLaunchArgs a;
-  stageLaunchArgs(op, pl, st, nrhs, &a);
-  BfKernelLaunch L[2];
-  uint32_t const nl = bfSelectStageKernels(&a, L);
-  uint32_t n = 0;
-  for (uint32_t i = 0; i < nl; ++i, ++n) if (n < cap) ids[n] = L[i].kernel;
-  /* the reduce launches of runPlan: groups of 16, each split by bfdevLaunchReduce into batches of BF_REDUCE_BATCH; a batch
-   * of no rows launches nothing */
-  for (uint64_t r0 = 0; r0 < st->numReduce; r0 += 16) {
-    uint64_t const cnt = st->numReduce - r0 < 16 ? st->numReduce - r0 : 16;
-    for (uint64_t base = 0; base < cnt; base += BF_REDUCE_BATCH) {
-      uint64_t const bc = cnt - base < BF_REDUCE_BATCH ? cnt - base : BF_REDUCE_BATCH;
-      int longLists = 0, rows = 0;
-      for (uint64_t k = 0; k < bc; ++k) {
-        BfReduce const *rd = &st->reduce[r0 + base + k];
-        longLists = longLists || rd->maxSrc >= 64;
-        rows = rows || rd->numRows;
-      }
-      if (!rows) continue;
-      if (n < cap) ids[n] = bfSelectReduceKernel(pl->dtype, longLists);
-      ++n;
-    }
-  }
-  *count = n;
-  return 0;
-}
-int bfhipPlanGetReduce(BfhipOperator const *op, uint64_t stage, uint64_t index, BfhipReduceView *v) {
-  int rc = needPlanOnly(op);
-  if (rc) return rc;
-  BfPlan const *pl = &op->plan;
-  if (stage >= pl->numStages && op->hasTplan) { stage -= pl->numStages; pl = &op->tplan; }
-  if (!v || v->structSize < sizeof *v || stage >= pl->numStages || index >= pl->stages[stage].numReduce)
-    return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "bad reduce view request");
-  BfReduce const *rd = &pl->stages[stage].reduce[index];
-  v->destIsY = rd->destSpace == BF_SPACE_Y; v->destOff = rd->destOff; v->numRows = rd->numRows;
-  v->numIntervals = rd->numIntervals; v->numSrc = rd->numSrc;
-  v->rowInterval = rd->rowInterval; v->ivBegin = rd->ivBegin; v->srcBias = rd->srcBias;
-  return 0;
-}
-int bfhipPlanPackArena(BfhipOperator const *op, void *dst) {
-  int rc = needPlanOnly(op);
-  if (rc) return rc;
-  if (!dst) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL destination");
-  return packLeaves(op, op->ir, op->seed, dst);
-}
-/* the second arena of a BFHIP_FLAG_ADJOINT_PACKED plan (arenaElemsT elements): the leaves of the transposed expression */
-int bfhipPlanPackArenaT(BfhipOperator const *op, void *dst) {
-  int rc = needPlanOnly(op);
-  if (rc) return rc;
-  if (!dst) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL destination");
-  if (!op->packedT || !op->irT) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "operator was not compiled with BFHIP_FLAG_ADJOINT_PACKED");
-  return packLeavesPlan(&op->tplan, NULL, op->irT, op->seed, dst);
-}
-
-
-/* =============================================================================
- * Serialization: the flattened device layout is the
- * natural on-disk form of a compiled operator.  The reference's bfMatDump is
- * write-only and lacks a complex dense payload (src/mat.c:67-73,
- * src/mat_dense_complex.c:173-222); here Save / Load round-trip the operator
- * exactly (bit-identical applies) without the BfMat graph or a rebuild.
- * File: "BFHIPOP1" | header | per plan: per stage {counts, items, pieces,
- * reduces} | leaf arena bytes.  Little-endian, same-architecture format.
- * ============================================================================= */
-#define BFHIP_FILE_MAGIC "BFHIPOP1"
-
-typedef struct FileHeader {
-  char magic[8];
-  uint32_t version, dtype, srcDtype, elemSize, epl, xcap, hasTplan, reserved;
-  uint64_t numRows, numCols, arenaElems, leafElems, numLeaves, leafBytesAlgorithmic;
-} FileHeader;
-
-typedef struct FilePlanHeader { uint64_t numStages, tempElems, numRows, numCols; uint32_t maxItemRows, transposed; } FilePlanHeader;
-typedef struct FileStageHeader { uint64_t numItems, numPieces, leafElems, vecIn, vecOut, numReduce; uint32_t maxRows, reserved; } FileStageHeader;
-typedef struct FileReduceHeader { uint64_t destOff, numRows, numIntervals, numSrc; uint32_t destSpace, reserved; } FileReduceHeader;
-
-static int writeAll(FILE *fp, void const *p, size_t n) { return n == 0 || fwrite(p, 1, n, fp) == n ? 0 : bfhipFail(BFABI_ERROR_FILE_ERROR, "short write"); }
-static int readAll(FILE *fp, void *p, size_t n) { return n == 0 || fread(p, 1, n, fp) == n ? 0 : bfhipFail(BFABI_ERROR_FILE_ERROR, "short read / truncated file"); }
-
-static int writeDeviceArray(FILE *fp, void const *d, size_t bytes) {
-  if (!bytes) return 0;
-  size_t const chunk = (size_t)64 << 20;
-  void *h = malloc(bytes < chunk ? bytes : chunk);
-  if (!h) return bfhipFail(BFABI_ERROR_MEMORY_ERROR, "host OOM");
-  int rc = 0;
-  for (size_t off = 0; off < bytes && !rc; off += chunk) {
-    size_t n = bytes - off < chunk ? bytes - off : chunk;
-    rc = bfdevMemcpyD2H(h, (char const *)d + off, n);
-    if (!rc) rc = writeAll(fp, h, n);
-  }
-  free(h);
-  return rc;
-}
-static int readDeviceArray(FILE *fp, void **d, size_t bytes, uint64_t *meta) {
-  int rc = bfdevMalloc(d, bytes + BF_ARENA_SLACK);
-  if (rc || !bytes) return rc;
-  if (meta) *meta += bytes;
-  size_t const chunk = (size_t)64 << 20;
-  void *h = malloc(bytes < chunk ? bytes : chunk);
-  if (!h) return bfhipFail(BFABI_ERROR_MEMORY_ERROR, "host OOM");
-  for (size_t off = 0; off < bytes && !rc; off += chunk) {
-    size_t n = bytes - off < chunk ? bytes - off : chunk;
-    rc = readAll(fp, h, n);
-    if (!rc) rc = bfdevMemcpyH2D((char *)*d + off, h, n);
-  }
-  free(h);
-  return rc;
-}
-
-static int savePlan(FILE *fp, BfPlan const *pl) {
-  FilePlanHeader ph = {pl->numStages, pl->tempElems, pl->numRows, pl->numCols, pl->maxItemRows, (uint32_t)pl->transposed};
-  int rc = writeAll(fp, &ph, sizeof ph);
-  for (uint64_t s = 0; s < pl->numStages && !rc; ++s) {
-    BfStage const *st = &pl->stages[s];
-    FileStageHeader sh = {st->numItems, st->numPieces, st->leafElems, st->vecIn, st->vecOut, st->numReduce, st->maxRows, 0};
-    rc = writeAll(fp, &sh, sizeof sh);
-    if (!rc) rc = writeDeviceArray(fp, st->dItems, st->numItems * sizeof(BfDevItem));
-    if (!rc) rc = writeDeviceArray(fp, st->dPieces, st->numPieces * sizeof(BfDevPiece));
-    for (uint64_t r = 0; r < st->numReduce && !rc; ++r) {
-      BfReduce const *rd = &st->reduce[r];
-      FileReduceHeader rh = {rd->destOff, rd->numRows, rd->numIntervals, rd->numSrc, rd->destSpace, 0};
-      rc = writeAll(fp, &rh, sizeof rh);
-      if (!rc) rc = writeDeviceArray(fp, rd->dRowInterval, rd->numRows * 4);
-      if (!rc) rc = writeDeviceArray(fp, rd->dIvBegin, (rd->numIntervals + 1) * 4);
-      if (!rc) rc = writeDeviceArray(fp, rd->dSrcBias, rd->numSrc * 8);
-    }
-  }
-  return rc;
-}
-
-/* index tables are small (0.03 % of the operand): read whole, validate on the host, then upload */
-static int readMetaArray(FILE *fp, void **d, void **h, size_t bytes, uint64_t *meta) {
-  *h = NULL;
-  int rc = bfdevMalloc(d, bytes);
-  if (rc || !bytes) return rc;
-  if (meta) *meta += bytes;
-  *h = malloc(bytes);
-  if (!*h) return bfhipFail(BFABI_ERROR_MEMORY_ERROR, "host OOM");
-  if ((rc = readAll(fp, *h, bytes))) return rc;
-  return bfdevMemcpyH2D(*d, *h, bytes);
-}
-
-/* A file is untrusted input: every offset the kernels will dereference is checked against the
- * sizes in the header before the operator is accepted (a truncated or corrupt file must not turn
- * into device out-of-bounds accesses). */
-/* offset + extent <= len without wrapping: offsets and extents come straight from the file as 64-bit values,
- * and `off + ext > len` accepts off = 2^64 - 16 (the sum wraps to a small value) */
-static int fitsIn(uint64_t off, uint64_t ext, uint64_t len) { return off <= len && ext <= len - off; }
-/* a * b + c, saturating at UINT64_MAX */
-static uint64_t mulAddSat(uint64_t a, uint64_t b, uint64_t c) {
-  uint64_t r;
-  if (__builtin_mul_overflow(a, b, &r) || __builtin_add_overflow(r, c, &r)) return UINT64_MAX;
-  return r;
-}
-
-static int validateStage(BfPlan const *pl, uint64_t arenaElems, BfStage const *st, BfDevItem const *items, BfDevPiece const *pieces) {
-  uint64_t const inX = pl->numCols, outY = pl->numRows, temp = pl->tempElems;
-  for (uint64_t i = 0; i < st->numItems; ++i) {
-    BfDevItem const *it = &items[i];
-    uint32_t const mr = it->mrFlags & 0xffffu;
-    uint64_t const outLen = (it->mrFlags & BF_ITEM_OUT_Y) ? outY : temp;
-    if (!mr || mr > pl->maxItemRows || mr > st->maxRows || (it->mrFlags & ~(0xffffu | BF_ITEM_OUT_Y | BF_ITEM_ROWMAJOR | BF_ITEM_MERGED | BF_ITEM_SMALL | BF_ITEM_TNARROW)) ||
-        ((it->mrFlags & BF_ITEM_TNARROW) != 0) != (i < st->numNarrow) || ((it->mrFlags & BF_ITEM_TNARROW) && (!pl->transposed || mr > 16)) ||
-        ((it->mrFlags & BF_ITEM_SMALL) != 0) != (i >= st->firstSmall) ||
-        ((it->mrFlags & BF_ITEM_ROWMAJOR) && (pl->transposed || bfDtypeC128Layout(pl->dtype) || mr > 2 * pl->epl)) ||
-        (pl->transposed && mr > 64) ||       /* bfStageKernelT: at most 64 columns of A per item */
-        !fitsIn(it->outOff, mr, outLen) || !fitsIn(it->pieceBegin, it->numPieces, st->numPieces))
-      return bfhipFail(BFABI_ERROR_FILE_ERROR, "corrupt operator file: item %llu out of bounds", (unsigned long long)i);
-    uint32_t const mrPad = (mr + pl->epl - 1) / pl->epl * pl->epl;
-    if (it->mrFlags & (BF_ITEM_MERGED | BF_ITEM_SMALL)) {     /* the kernel reads the dense pieces as one block from the first one's offset */
-      int const sm = (it->mrFlags & BF_ITEM_SMALL) != 0;
-      uint64_t next = 0, dense = 0;
-      int const smRm = sm && (it->mrFlags & BF_ITEM_ROWMAJOR);      /* small items: row-major pieces, no contiguity promise */
-      int badm = pl->transposed || bfDtypeC128Layout(pl->dtype) || (!sm && (it->mrFlags & BF_ITEM_ROWMAJOR)) || it->numPieces > (sm ? BF_SMALL_PIECES : 64u) ||
-                 (sm && (mr > 2 * pl->epl || !(it->mrFlags & BF_ITEM_ROWMAJOR)));
-      for (uint32_t k = 0; k < it->numPieces && !badm; ++k) {
-        BfDevPiece const *pc = &pieces[it->pieceBegin + k];
-        if (pc->flags & BF_PIECE_IDENTITY) continue;
-        if (!smRm && dense && pc->dataOff != next) badm = 1;
-        next = mulAddSat(mrPad, pc->ncols, pc->dataOff); dense += pc->ncols;
-      }
-      if (badm || (!dense && !sm) || dense > (sm ? BF_SMALL_COLS : BF_MERGE_COLS))
-        return bfhipFail(BFABI_ERROR_FILE_ERROR, "corrupt operator file: merged item %llu is not one block", (unsigned long long)i);
-    }
-    for (uint32_t k = 0; k < it->numPieces; ++k) {
-      BfDevPiece const *pc = &pieces[it->pieceBegin + k];
-      uint64_t const inLen = (pc->flags & BF_PIECE_IN_X) ? inX : temp;
-      int bad = (pc->flags & ~(BF_PIECE_IN_X | BF_PIECE_IDENTITY | BF_PIECE_ROWMAJOR)) != 0;
-      int const rm = (pc->flags & BF_PIECE_ROWMAJOR) != 0;
-      if (!(pc->flags & BF_PIECE_IDENTITY) && !pl->transposed && rm != ((it->mrFlags & BF_ITEM_ROWMAJOR) != 0)) bad = 1;
-      if (pc->flags & BF_PIECE_IDENTITY) bad |= !fitsIn(pc->inOff, mr, inLen);
-      else if (pl->transposed && rm)      /* rows of a row-major forward piece: ncols rows, mr columns from dataOff */
-        bad |= !pc->ld || pc->ld % pl->epl || pc->dataOff % pl->epl || bfDtypeC128Layout(pl->dtype) || !pc->ncols ||
-               !fitsIn(pc->dataOff, mulAddSat(pc->ncols - 1, pc->ld, (mr + pl->epl - 1) / pl->epl * pl->epl), arenaElems) ||
-               !fitsIn(pc->inOff, pc->ncols, inLen);
-      else if (rm)
-        bad |= !pc->ncols || pc->ld % pl->epl || pc->ld < pc->ncols || pc->dataOff % pl->epl ||   /* x is read from global memory: no xcap */
-               !fitsIn(pc->dataOff, mulAddSat(mr, pc->ld, 0), arenaElems) || !fitsIn(pc->inOff, pc->ncols, inLen);
-      else if (pl->transposed)
-        bad |= !pc->ld || pc->ld % pl->epl || pc->ncols > pc->ld || pc->dataOff % pl->epl ||
-               !fitsIn(pc->dataOff, mulAddSat(mr - 1, pc->ld, (pc->ncols + pl->epl - 1) / pl->epl * pl->epl), arenaElems) ||
-               !fitsIn(pc->inOff, pc->ncols, inLen);
-      else
-        bad |= !pc->ncols || pc->ncols > pl->xcap || pc->dataOff % pl->epl ||
-               !fitsIn(pc->dataOff, mulAddSat(mrPad, pc->ncols, 0), arenaElems) || !fitsIn(pc->inOff, pc->ncols, inLen);
-      if (bad) return bfhipFail(BFABI_ERROR_FILE_ERROR, "corrupt operator file: piece %u of item %llu out of bounds", k, (unsigned long long)i);
-    }
-  }
-  return 0;
-}
-
-static int validateReduce(BfPlan const *pl, BfReduce const *rd, uint32_t const *rowInterval, uint32_t const *ivBegin, int64_t const *srcBias) {
-  uint64_t const destLen = rd->destSpace == BF_SPACE_Y ? pl->numRows : pl->tempElems;
-  if ((rd->destSpace != BF_SPACE_Y && rd->destSpace != BF_SPACE_TEMP) || !fitsIn(rd->destOff, rd->numRows, destLen) || rd->numIntervals > rd->numRows + 1)
-    return bfhipFail(BFABI_ERROR_FILE_ERROR, "corrupt operator file: reduce destination out of bounds");
-  if (ivBegin[0] != 0 || ivBegin[rd->numIntervals] > rd->numSrc) return bfhipFail(BFABI_ERROR_FILE_ERROR, "corrupt operator file: reduce interval table");
-  for (uint64_t i = 0; i < rd->numIntervals; ++i)
-    if (ivBegin[i + 1] < ivBegin[i]) return bfhipFail(BFABI_ERROR_FILE_ERROR, "corrupt operator file: reduce interval table not monotone");
-  for (uint64_t r = 0; r < rd->numRows; ++r) {
-    uint32_t const iv = rowInterval[r];
-    if (iv == BF_REDUCE_SKIP) continue;
-    if (iv >= rd->numIntervals) return bfhipFail(BFABI_ERROR_FILE_ERROR, "corrupt operator file: reduce row %llu", (unsigned long long)r);
-    for (uint32_t k = ivBegin[iv]; k < ivBegin[iv + 1]; ++k) {
-      int64_t src;
-      if (__builtin_add_overflow(srcBias[k], (int64_t)r, &src) || src < 0 || (uint64_t)src >= pl->tempElems) return bfhipFail(BFABI_ERROR_FILE_ERROR, "corrupt operator file: reduce source out of bounds");
-    }
-  }
-  return 0;
-}
-
-static int loadPlan(FILE *fp, BfhipOperator *op, BfPlan *pl, FileHeader const *fh, uint64_t arenaElems) {
-  FilePlanHeader ph;
-  int rc = readAll(fp, &ph, sizeof ph);
-  if (rc) return rc;
-  if (ph.numStages > (1u << 20) || ph.tempElems >= 0xffffffffu) return bfhipFail(BFABI_ERROR_FILE_ERROR, "corrupt plan header");
-  pl->dtype = fh->dtype; pl->elemSize = fh->elemSize; pl->epl = fh->epl; pl->xcap = fh->xcap;
-  pl->maxItemRows = ph.maxItemRows; pl->transposed = (int)ph.transposed;
-  pl->numRows = ph.numRows; pl->numCols = ph.numCols; pl->numStages = ph.numStages; pl->tempElems = ph.tempElems;
-  pl->arenaElems = pl->transposed ? 0 : arenaElems;
-  pl->leafElems = fh->leafElems; pl->numLeaves = fh->numLeaves;
-  if (pl->epl != 16 / pl->elemSize || pl->xcap != 256 || pl->maxItemRows > 64 * pl->epl || (pl->transposed && pl->maxItemRows > 128))
-    return bfhipFail(BFABI_ERROR_FILE_ERROR, "corrupt plan header (lane granule / piece width / item height)");
-  pl->stages = calloc(ph.numStages ? ph.numStages : 1, sizeof(BfStage));
-  if (!pl->stages) return bfhipFail(BFABI_ERROR_MEMORY_ERROR, "host OOM");
-  for (uint64_t s = 0; s < pl->numStages && !rc; ++s) {
-    BfStage *st = &pl->stages[s];
-    FileStageHeader sh;
-    if ((rc = readAll(fp, &sh, sizeof sh))) break;
-    if (sh.numItems > 0xffffffffu || sh.numPieces > 0xffffffffu || sh.numReduce > (1u << 20)) { rc = bfhipFail(BFABI_ERROR_FILE_ERROR, "corrupt stage header"); break; }
-    st->numItems = sh.numItems; st->numPieces = sh.numPieces; st->leafElems = sh.leafElems; st->vecIn = sh.vecIn; st->vecOut = sh.vecOut;
-    st->maxRows = sh.maxRows;
-    void *hItems = NULL, *hPieces = NULL;
-    rc = readMetaArray(fp, &st->dItems, &hItems, st->numItems * sizeof(BfDevItem), &op->metaBytes);
-    if (!rc) rc = readMetaArray(fp, &st->dPieces, &hPieces, st->numPieces * sizeof(BfDevPiece), &op->metaBytes);
-    if (!rc) {       /* small items are the tail of the list (validateStage checks that they are nowhere else) */
-      st->firstSmall = st->numItems;
-      while (st->firstSmall && (((BfDevItem const *)hItems)[st->firstSmall - 1].mrFlags & BF_ITEM_SMALL)) --st->firstSmall;
-      st->numNarrow = 0;
-      while (st->numNarrow < st->numItems && (((BfDevItem const *)hItems)[st->numNarrow].mrFlags & BF_ITEM_TNARROW)) ++st->numNarrow;
-      rc = validateStage(pl, arenaElems, st, hItems, hPieces);
-      if (!rc && pl->transposed) {
-        st->maxRowsRest = 0;
-        for (uint64_t i = st->numNarrow; i < st->numItems; ++i) {
-          uint32_t const mr = ((BfDevItem const *)hItems)[i].mrFlags & 0xffffu;
-          if (mr > st->maxRowsRest) st->maxRowsRest = mr;
-        }
-        st->numCoopNarrow = bfPlanCountCoop(hItems, hPieces, st->numNarrow, pl->elemSize);
-        st->numCoop = bfPlanCountCoop((BfDevItem const *)hItems + st->numNarrow, hPieces, st->numItems - st->numNarrow, pl->elemSize);
-      }
-    }
-    free(hItems); free(hPieces);
-    if (!rc && sh.numReduce) {
-      st->reduce = calloc(sh.numReduce, sizeof(BfReduce));
-      if (!st->reduce) rc = bfhipFail(BFABI_ERROR_MEMORY_ERROR, "host OOM");
-    }
-    for (uint64_t r = 0; r < sh.numReduce && !rc; ++r) {
-      BfReduce *rd = &st->reduce[r];
-      FileReduceHeader rh;
-      if ((rc = readAll(fp, &rh, sizeof rh))) break;
-      st->numReduce = r + 1;
-      rd->destOff = rh.destOff; rd->numRows = rh.numRows; rd->numIntervals = rh.numIntervals; rd->numSrc = rh.numSrc; rd->destSpace = rh.destSpace;
-      if (rd->numRows >= 0xffffffffu || rd->numIntervals >= 0xffffffffu || rd->numSrc >= 0xffffffffu) { rc = bfhipFail(BFABI_ERROR_FILE_ERROR, "corrupt reduce header"); break; }
-      void *hRow = NULL, *hIv = NULL, *hBias = NULL;
-      rc = readMetaArray(fp, &rd->dRowInterval, &hRow, rd->numRows * 4, &op->metaBytes);
-      if (!rc) rc = readMetaArray(fp, &rd->dIvBegin, &hIv, (rd->numIntervals + 1) * 4, &op->metaBytes);
-      if (!rc) rc = readMetaArray(fp, &rd->dSrcBias, &hBias, rd->numSrc * 8, &op->metaBytes);
-      if (!rc) rc = validateReduce(pl, rd, hRow, hIv, hBias);
-      if (!rc) {
-        uint32_t const *iv = hIv;
-        rd->maxSrc = 0;
-        for (uint64_t i = 0; i < rd->numIntervals; ++i) if (iv[i + 1] - iv[i] > rd->maxSrc) rd->maxSrc = iv[i + 1] - iv[i];
-      }
-      free(hRow); free(hIv); free(hBias);
-    }
-  }
-  return rc;
-}
-
-int bfhipSave(BfhipOperator *op, char const *path) {
-  if (!op || !path) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL argument");
-  if (op->flags & BFHIP_FLAG_PLAN_ONLY) return bfhipFail(BFABI_ERROR_RUNTIME_ERROR, "a plan-only operator has no device data to save");
-  int prev = -1;
-  bfdevGetDevice(&prev);
-  int rc = bfdevSetDevice(op->device);
-  if (rc) return rc;
-  if ((rc = bfdevSync(NULL))) return rc;
-  FILE *fp = fopen(path, "wb");
-  if (!fp) return bfhipFail(BFABI_ERROR_FILE_ERROR, "cannot open %s for writing", path);
-  FileHeader fh;
-  memset(&fh, 0, sizeof fh);
-  memcpy(fh.magic, BFHIP_FILE_MAGIC, 8);
-  fh.version = 1; fh.dtype = op->plan.dtype; fh.srcDtype = op->srcDtype; fh.elemSize = op->plan.elemSize; fh.epl = op->plan.epl;
-  fh.xcap = op->plan.xcap; fh.hasTplan = (uint32_t)op->hasTplan;
-  fh.reserved = op->dArenaT ? 1u : 0u;        /* bit 0: the adjoint plan is a forward plan of the transposed expression over a second arena (BFHIP_FLAG_ADJOINT_PACKED) */
-  fh.numRows = op->plan.numRows; fh.numCols = op->plan.numCols; fh.arenaElems = op->plan.arenaElems;
-  fh.leafElems = op->plan.leafElems; fh.numLeaves = op->plan.numLeaves; fh.leafBytesAlgorithmic = op->leafBytesAlgorithmic;
-  rc = writeAll(fp, &fh, sizeof fh);
-  uint64_t const arenaElemsT = op->dArenaT ? op->tplan.arenaElems : 0;
-  if (!rc && op->dArenaT) rc = writeAll(fp, &arenaElemsT, sizeof arenaElemsT);
-  if (!rc) rc = savePlan(fp, &op->plan);
-  if (!rc && op->hasTplan) rc = savePlan(fp, &op->tplan);
-  if (!rc) rc = writeDeviceArray(fp, op->dArena, (size_t)op->plan.arenaElems * op->plan.elemSize);
-  if (!rc && op->dArenaT) rc = writeDeviceArray(fp, op->dArenaT, (size_t)arenaElemsT * op->plan.elemSize);
-  if (fclose(fp) != 0 && !rc) rc = bfhipFail(BFABI_ERROR_FILE_ERROR, "error closing %s", path);
-  if (prev >= 0 && prev != op->device) bfdevSetDevice(prev);
-  return rc;
-}
-
-int bfhipLoad(char const *path, BfhipOptions const *opts, BfhipOperator **out) {
-  if (!path || !out) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL argument");
-  *out = NULL;
-  BfhipOptions o;
-  memset(&o, 0, sizeof o);
-  o.device = -1;
-  if (opts) {
-    if (opts->structSize < BFHIP_OPTIONS_SIZE_V1) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "BfhipOptions.structSize too small");
-    memcpy(&o, opts, opts->structSize < sizeof o ? opts->structSize : sizeof o);
-  }
-  if (o.flags & BFHIP_FLAG_PLAN_ONLY) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "cannot load as plan-only");
-  FILE *fp = fopen(path, "rb");
-  if (!fp) return bfhipFail(BFABI_ERROR_FILE_ERROR, "cannot open %s", path);
-  FileHeader fh;
-  int rc = readAll(fp, &fh, sizeof fh);
-  if (!rc && (memcmp(fh.magic, BFHIP_FILE_MAGIC, 8) != 0 || fh.version != 1 || fh.dtype > BFHIP_C64 ||
-              fh.elemSize != bfDtypeElemSize(fh.dtype) || (fh.dtype == BFHIP_C64 && fh.srcDtype != BFHIP_C128)))
-    rc = bfhipFail(BFABI_ERROR_FILE_ERROR, "%s is not a bfhip operator file (bad magic / version / dtype)", path);
-  if (rc) { fclose(fp); return rc; }
-  BfhipOperator *op = calloc(1, sizeof *op);
-  if (!op) { fclose(fp); return bfhipFail(BFABI_ERROR_MEMORY_ERROR, "host OOM"); }
-  int prevDev = -1;
-  bfdevGetDevice(&prevDev);
-  op->flags = o.flags & ~(uint32_t)(BFHIP_FLAG_ADJOINT | BFHIP_FLAG_ADJOINT_PACKED);
-  op->srcDtype = fh.srcDtype;
-  op->leafBytesAlgorithmic = fh.leafBytesAlgorithmic;
-  if ((rc = bfdevSetDevice(o.device))) goto done;
-  if ((rc = bfdevGetDevice(&op->device))) goto done;
-  uint64_t arenaElemsT = 0;
-  int const packedT = (fh.reserved & 1u) != 0;
-  if (fh.reserved & ~1u) { rc = bfhipFail(BFABI_ERROR_FILE_ERROR, "corrupt operator file (header flags)"); goto done; }
-  if (packedT && (!fh.hasTplan || (rc = readAll(fp, &arenaElemsT, sizeof arenaElemsT)))) { if (!rc) rc = bfhipFail(BFABI_ERROR_FILE_ERROR, "corrupt operator file (packed adjoint without a plan)"); goto done; }
-  if ((rc = loadPlan(fp, op, &op->plan, &fh, fh.arenaElems))) goto done;
-  if (fh.hasTplan) {
-    if ((rc = loadPlan(fp, op, &op->tplan, &fh, packedT ? arenaElemsT : fh.arenaElems))) goto done;
-    /* a packed adjoint plan is a FORWARD plan over its own arena, a shared one a transposed plan over the forward arena */
-    if ((op->tplan.transposed != 0) == packedT) { rc = bfhipFail(BFABI_ERROR_FILE_ERROR, "corrupt operator file (adjoint plan kind)"); goto done; }
-    op->hasTplan = 1;
-    op->packedT = packedT;
-    op->flags |= packedT ? BFHIP_FLAG_ADJOINT_PACKED : BFHIP_FLAG_ADJOINT;
-  }
-  if ((rc = readDeviceArray(fp, &op->dArena, (size_t)fh.arenaElems * fh.elemSize, NULL))) goto done;
-  if (packedT && (rc = readDeviceArray(fp, &op->dArenaT, (size_t)arenaElemsT * fh.elemSize, NULL))) goto done;
-  if ((rc = ensureTemp(op, o.maxRhs ? o.maxRhs : 1))) goto done;
-  if ((rc = bfdevMalloc(&op->dZero, 4096))) goto done;
-  if ((rc = bfdevMemset(op->dZero, 0, 4096))) goto done;
-  if (op->flags & BFHIP_FLAG_PROFILE) {
-    uint64_t S = op->plan.numStages;
-    op->evStart = calloc(BF_EV_POOL * S, sizeof(void *)); op->evStop = calloc(BF_EV_POOL * S, sizeof(void *));
-    op->stageMs = calloc(S, sizeof(double)); op->stageLaunches = calloc(S, sizeof(uint64_t));
-    if (!op->evStart || !op->evStop || !op->stageMs || !op->stageLaunches) { rc = bfhipFail(BFABI_ERROR_MEMORY_ERROR, "host OOM"); goto done; }
-    for (uint64_t s = 0; s < BF_EV_POOL * S && !rc; ++s) { rc = bfdevEventCreate(&op->evStart[s]); if (!rc) rc = bfdevEventCreate(&op->evStop[s]); }
-  }
-done:
-  fclose(fp);
-  if (rc) { bfhipFree(&op); if (prevDev >= 0) bfdevSetDevice(prevDev); return rc; }
-  if (prevDev >= 0 && o.device >= 0) bfdevSetDevice(prevDev);
-  *out = op;
-  return 0;
-}
-
-/* =============================================================================
- * BfMat vtable shim
- * ============================================================================= */
-typedef struct BfhipMat {
-  BfAbiMat super;             /* must be first: this IS a BfMat */
-  BfhipOperator *op;          /* the operator; with `sh`: this rank's share of it (shape queries go to `sh`) */
-  int ownsOperator;
-  int transposed;             /* bfMatTranspose has been applied an odd number of times: Mul / MulVec run the adjoint plan */
-  struct BfhipSharded *sh;    /* bfhipShardedMatNew: applies are the sharded step (every rank's host calls with the same vectors) */
-  int ownsSharded;
-} BfhipMat;
-
-/* rows / columns of the operator the object stands for (untransposed), and the host-vector apply behind every slot */
-static uint64_t shimOpRows(BfhipMat const *s) { return s->sh ? bfhipShardedGetNumRows(s->sh) : bfhipGetNumRows(s->op); }
-static uint64_t shimOpCols(BfhipMat const *s) { return s->sh ? bfhipShardedGetNumCols(s->sh) : bfhipGetNumCols(s->op); }
-static int applyHost(BfhipOperator *op, int transpose, void const *X, size_t ldx, size_t nrhs, void *Y, size_t ldy);
-static int shimApplyHost(BfhipMat const *s, int transpose, void const *X, size_t ldx, size_t nrhs, void *Y, size_t ldy) {
-  return s->sh ? bfhipShardedApplyHost(s->sh, transpose, X, ldx, nrhs, Y, ldy) : applyHost(s->op, transpose, X, ldx, nrhs, Y, ldy);
-}
-
-/* Failures surface the way the reference's own Mul failures do: the global error code is set
- * (bfSetError, src/error.c:20-24) and NULL is returned (the RAISE_ERROR / BF_ERROR_END idiom, e.g.
- * src/mat_product.c:404-405).  libbfhip does not link the reference; when the host process has
- * it loaded its bfSetError is found at run time.  Note that bfSetError asserts on a non-zero code
- * (src/error.c:21), so in a reference build with assertions a failed Mul is as fatal as the
- * reference's own BF_DIE() paths; bfhipSetErrorForwarding(0) keeps failures to NULL +
- * bfhipLastErrorMessage(). */
-#include <dlfcn.h>
-static int forwardErrors = 1;
-void bfhipSetErrorForwarding(int on) { forwardErrors = on; }
-static void shimRaise(int code) {
-  if (!forwardErrors || !code) return;
-  static void (*setError)(int);
-  static int looked;
-  if (!looked) { looked = 1; setError = (void (*)(int))dlsym(RTLD_DEFAULT, "bfSetError"); }
-  if (setError) setError(code);
-}
-#define SHIM_FAIL(code, ...) do { shimRaise(bfhipFail((code), __VA_ARGS__)); return NULL; } while (0)
-
-/* shape of what the object currently stands for: A, or A^T after bfMatTranspose (the reference's transposed product
- * answers with its reversed, transposed factors' shapes: src/mat_product.c:146-192, 409-420) */
-static size_t shimGetNumRows(BfAbiMat const *m) { BfhipMat const *s = (BfhipMat const *)m; return s->transposed ? shimOpCols(s) : shimOpRows(s); }
-static size_t shimGetNumCols(BfAbiMat const *m) { BfhipMat const *s = (BfhipMat const *)m; return s->transposed ? shimOpRows(s) : shimOpCols(s); }
-static int shimGetType(BfAbiMat const *m) { (void)m; return BFABI_TYPE_MAT_FUNC; }
-static size_t shimNumBytes(BfAbiMat const *m) { return bfhipNumBytes(((BfhipMat const *)m)->op); }
-static void shimDelete(BfAbiMat **m) {
-  if (!m || !*m) return;
-  BfhipMat *s = (BfhipMat *)*m;
-  /* a view never owns the operator (bfMatDenseRealDeinit skips the payload of a view the same way,
-   * src/mat_dense_real.c:1667-1672) */
-  if (s->ownsSharded && s->sh && !(s->super.props & BFABI_MAT_PROPS_VIEW)) bfhipShardedFree(&s->sh);
-  if (s->ownsOperator && !(s->super.props & BFABI_MAT_PROPS_VIEW)) bfhipFree(&s->op);
-  free(s);
-  *m = NULL;
-}
-/* GetView: a shallow copy flagged VIEW, what every reference type returns (e.g.
- * bfMatDenseRealGetView, src/mat_dense_real.c:67-85).  bfMatBlockDenseGetBlockConst calls it on
- * every sub-block of a BlockDense on each Mul (src/mat_block_dense.c:1043-1061, via bfMatGet
- * with BF_POLICY_VIEW), so a shim placed INSIDE a reference container needs it. */
-static BfAbiMat *shimGetView(BfAbiMat *m) {
-  BfhipMat *v = malloc(sizeof *v);
-  if (!v) SHIM_FAIL(BFABI_ERROR_MEMORY_ERROR, "host OOM");
-  *v = *(BfhipMat *)m;
-  v->super.props |= BFABI_MAT_PROPS_VIEW;
-  return &v->super;
-}
-
-/* Y = A X for a reference dense RHS; the result is allocated through the
- * RHS's own EmptyLike slot so the reference owns and frees it
- * (bfMatBlockCooMul does the same with ZerosLike, mat_block_coo.c:401). */
-static void *shimMulImpl(void const *rhsV, BfhipMat const *self, int transpose) {
-  BfAbiMat const *rhs = rhsV;
-  BfhipOperator *op = self ? self->op : NULL;
-  if (!op || !rhs || !rhs->vtbl) SHIM_FAIL(BFABI_ERROR_INVALID_ARGUMENTS, "NULL operand");
-  if (transpose && !op->hasTplan) SHIM_FAIL(BFABI_ERROR_NOT_IMPLEMENTED, "Mul on a transposed operator needs BFHIP_FLAG_ADJOINT");
-  uint64_t const inLen = transpose ? shimOpRows(self) : shimOpCols(self), outLen = transpose ? shimOpCols(self) : shimOpRows(self);
-  BfAbiGetTypeFn getType = (BfAbiGetTypeFn)rhs->vtbl->slot[BFABI_SLOT_GetType];
-  if (!getType || getType(rhs) != BFABI_TYPE_MAT_DENSE_COMPLEX || op->srcDtype != BFHIP_C128)
-    /* same restriction as bfMatDenseComplexMul's switch (mat_dense_complex.c:1036-1047) */
-    SHIM_FAIL(BFABI_ERROR_NOT_IMPLEMENTED, "Mul needs a complex operator and a BfMatDenseComplex right-hand side");
-  if (rhs->props & (BFABI_MAT_PROPS_TRANS | BFABI_MAT_PROPS_CONJ)) SHIM_FAIL(BFABI_ERROR_NOT_IMPLEMENTED, "transposed right-hand side");
-  BfAbiMatDenseComplex const *x = (BfAbiMatDenseComplex const *)rhs;
-  if (rhs->numRows != inLen)
-    SHIM_FAIL(BFABI_ERROR_INCOMPATIBLE_SHAPES, "operator has %llu columns, right-hand side %llu rows", (unsigned long long)inLen, (unsigned long long)rhs->numRows);
-  BfAbiLikeFn emptyLike = (BfAbiLikeFn)rhs->vtbl->slot[BFABI_SLOT_EmptyLike];
-  if (!emptyLike) SHIM_FAIL(BFABI_ERROR_INVALID_ARGUMENTS, "right-hand side has no EmptyLike");
-  /* a column-strided right-hand side (a view of every k-th column, a column range of a wider matrix:
-   * bfMatDenseComplexGetColRange leaves colStride as it is, src/mat_dense_complex.c:648-672) is gathered into a packed
-   * copy first -- cblas_zgemm in the reference cannot take it either (it passes ldb = rowStride and assumes unit column
-   * stride, :1754), so this is more than the reference does, not less */
-  /* A transposed COMPLEX object multiplies as its conjugate transpose, as in the reference: bfMatTranspose ends in
-   * bfMatDenseComplexTranspose = bfMatConjTrans on every dense leaf (src/mat_dense_complex.c:1475-1478, src/mat.c:359-362) and
-   * getCblasTranspose maps the flags to CblasConjTrans (:27-35).  A^H X = conj(A^T conj(X)): the right-hand side is
-   * conjugated into the packed copy, the result in place. */
-  void *packed = NULL;
-  void const *xdata = x->data;
-  size_t xld = x->rowStride;
-  if (x->colStride != 1 || transpose) {
-    if (x->colStride == 0) SHIM_FAIL(BFABI_ERROR_INVALID_ARGUMENTS, "right-hand side with colStride 0");
-    size_t const nr = rhs->numRows, nc = rhs->numCols;
-    packed = malloc((nr && nc ? nr * nc : 1) * 16);
-    if (!packed) SHIM_FAIL(BFABI_ERROR_MEMORY_ERROR, "host OOM");
-    for (size_t i = 0; i < nr; ++i)
-      for (size_t q = 0; q < nc; ++q) {
-        double const *e = (double const *)((char const *)x->data + (i * x->rowStride + q * x->colStride) * 16);
-        double *d = (double *)((char *)packed + (i * nc + q) * 16);
-        d[0] = e[0]; d[1] = transpose ? -e[1] : e[1];
-      }
-    xdata = packed; xld = nc;
-  }
-  BfAbiMat *res = emptyLike(rhs, outLen, rhs->numCols);
-  if (!res) { free(packed); SHIM_FAIL(BFABI_ERROR_MEMORY_ERROR, "EmptyLike failed"); }
-  BfAbiMatDenseComplex *y = (BfAbiMatDenseComplex *)res;
-  int rc;
-  if (y->colStride != 1) rc = bfhipFail(BFABI_ERROR_NOT_IMPLEMENTED, "EmptyLike returned a result with colStride != 1");
-  else rc = shimApplyHost(self, transpose, xdata, xld, rhs->numCols, y->data, y->rowStride);
-  if (!rc && transpose)
-    for (size_t i = 0; i < outLen; ++i)
-      for (size_t q = 0; q < rhs->numCols; ++q) ((double *)y->data)[2 * (i * y->rowStride + q) + 1] *= -1.0;
-  free(packed);
-  if (rc) {
-    BfAbiDeleteFn del = (BfAbiDeleteFn)res->vtbl->slot[BFABI_SLOT_Delete];
-    if (del) del(&res);
-    shimRaise(rc);
-    return NULL;
-  }
-  return res;
-}
-
-void *bfhipMatMulFunc(void const *rhsV, void *opV) {
-  BfhipMat tmp;
-  memset(&tmp, 0, sizeof tmp);
-  tmp.op = opV;
-  return shimMulImpl(rhsV, &tmp, 0);
-}
-
-static BfAbiMat *shimMul(BfAbiMat const *lhs, BfAbiMat const *rhs) {
-  return shimMulImpl(rhs, (BfhipMat const *)lhs, ((BfhipMat const *)lhs)->transposed);
-}
-
-/* bfMatRmul(A_hip, X) = X A (slot 44, src/mat.c:195-197; bfMatProductRmul walks the factors in order, src/mat_product.c:282-310, down
- * to bfMatDenseComplexRmul's one zgemm, src/mat_dense_complex.c:1075-1133 -- a dense complex `otherMat` only, :1125-1133).
- * X A = (A^T X^T)^T: the adjoint plan applied to the rows of X as right-hand sides.  X^T is gathered into a packed copy (any row /
- * column stride of X), the result is scattered into a matrix allocated through X's EmptyLike.  After bfMatTranspose the object
- * stands for A^H (shimMulImpl): X A^H = conj(conj(X) A^T) = conj((A conj(X)^T)^T), the FORWARD plan between two conjugations. */
-static BfAbiMat *shimRmul(BfAbiMat const *lhs, BfAbiMat const *other) {
-  BfhipMat const *self = (BfhipMat const *)lhs;
-  BfhipOperator *op = self ? self->op : NULL;
-  if (!op || !other || !other->vtbl) SHIM_FAIL(BFABI_ERROR_INVALID_ARGUMENTS, "NULL operand");
-  int const conj = self->transposed, transpose = !self->transposed;          /* which plan runs */
-  if (transpose && !op->hasTplan) SHIM_FAIL(BFABI_ERROR_NOT_IMPLEMENTED, "Rmul needs an operator compiled with BFHIP_FLAG_ADJOINT");
-  BfAbiGetTypeFn getType = (BfAbiGetTypeFn)other->vtbl->slot[BFABI_SLOT_GetType];
-  if (!getType || getType(other) != BFABI_TYPE_MAT_DENSE_COMPLEX || op->srcDtype != BFHIP_C128)
-    SHIM_FAIL(BFABI_ERROR_NOT_IMPLEMENTED, "Rmul needs a complex operator and a BfMatDenseComplex left operand");
-  if (other->props & (BFABI_MAT_PROPS_TRANS | BFABI_MAT_PROPS_CONJ)) SHIM_FAIL(BFABI_ERROR_NOT_IMPLEMENTED, "transposed left operand");
-  /* rows / columns of what the object stands for */
-  uint64_t const rows = self->transposed ? shimOpCols(self) : shimOpRows(self), cols = self->transposed ? shimOpRows(self) : shimOpCols(self);
-  size_t const m = other->numRows, k = other->numCols;
-  if (k != rows) SHIM_FAIL(BFABI_ERROR_INCOMPATIBLE_SHAPES, "operator has %llu rows, left operand %llu columns", (unsigned long long)rows, (unsigned long long)k);
-  BfAbiLikeFn emptyLike = (BfAbiLikeFn)other->vtbl->slot[BFABI_SLOT_EmptyLike];
-  if (!emptyLike) SHIM_FAIL(BFABI_ERROR_INVALID_ARGUMENTS, "left operand has no EmptyLike");
-  BfAbiMatDenseComplex const *x = (BfAbiMatDenseComplex const *)other;
-  double *xt = malloc((k && m ? k * m : 1) * 16), *zt = malloc((cols && m ? cols * m : 1) * 16);
-  if (!xt || !zt) { free(xt); free(zt); SHIM_FAIL(BFABI_ERROR_MEMORY_ERROR, "host OOM"); }
-  for (size_t q = 0; q < m; ++q)
-    for (size_t i = 0; i < k; ++i) {
-      double const *e = (double const *)((char const *)x->data + (q * x->rowStride + i * x->colStride) * 16);
-      xt[2 * (i * m + q)] = e[0]; xt[2 * (i * m + q) + 1] = conj ? -e[1] : e[1];
-    }
-  int rc = shimApplyHost(self, transpose, xt, m, m, zt, m);          /* (k x m) -> (cols x m) */
-  free(xt);
-  if (rc) { free(zt); shimRaise(rc); return NULL; }
-  BfAbiMat *res = emptyLike(other, m, cols);
-  if (!res) { free(zt); SHIM_FAIL(BFABI_ERROR_MEMORY_ERROR, "EmptyLike failed"); }
-  BfAbiMatDenseComplex *y = (BfAbiMatDenseComplex *)res;
-  for (size_t q = 0; q < m; ++q)
-    for (size_t j = 0; j < cols; ++j) {
-      double *d = (double *)((char *)y->data + (q * y->rowStride + j * y->colStride) * 16);
-      d[0] = zt[2 * (j * m + q)]; d[1] = conj ? -zt[2 * (j * m + q) + 1] : zt[2 * (j * m + q) + 1];
-    }
-  free(zt);
-  return res;
-}
-
-/* bfMatTranspose (slot 63, src/mat.c:271-273): in place, as bfMatProductTranspose reverses and transposes its factors
- * (src/mat_product.c:409-420).  The adjoint plan over the same packed leaves exists already (BFHIP_FLAG_ADJOINT), so the
- * object only changes which of its two plans Mul / MulVec / RmulVec run and what GetNumRows / GetNumCols answer; twice
- * is the identity.  For a REAL operator that is the transpose; a COMPLEX one multiplies as its conjugate transpose
- * afterwards, as the reference's does (its dense complex leaves transpose by bfMatConjTrans: shimMulImpl).  The slot returns nothing: without an
- * adjoint plan the reference's error state is raised (NOT_IMPLEMENTED) and the object is left as it was. */
-static void shimTranspose(BfAbiMat *m) {
-  BfhipMat *s = (BfhipMat *)m;
-  if (!s->op->hasTplan) { shimRaise(bfhipFail(BFABI_ERROR_NOT_IMPLEMENTED, "Transpose needs an operator compiled with BFHIP_FLAG_ADJOINT")); return; }
-  s->transposed = !s->transposed;
-  size_t const r = s->super.numRows;
-  s->super.numRows = s->super.numCols;
-  s->super.numCols = r;
-}
-
-/* y = A x (transpose == 0) or z = x^T A as a vector (bfMatRmulVec) for a reference BfVecReal; real
- * operators only: the block types reject complex vectors (mat_block_coo.c:438-444).  The result
- * is sized by the operator, as the reference's containers size theirs (bfVecRealNewWithValue(m, 0)
- * in src/mat_block_dense.c:574-590 and src/mat_block_coo.c:427-444; n for RmulVec, :696-712):
- * a malloc'd BfVecReal {vtbl, props NONE, size, stride 1, malloc'd data} carrying the ARGUMENT's
- * vtable, so that the reference's bfVecDelete -> bfVecRealDeinitAndDealloc frees data and struct with
- * free() (src/vec_real.c:661-676, src/mem.c:65-67).  Rectangular operators are the normal case:
- * cov_matvec applies the N x m operator Phi both ways (examples/covariance/lbo_cov.c:48-60). */
-static BfAbiVec *shimApplyVec(BfAbiMat const *lhs, BfAbiVec const *vec, int rmul) {
-  BfhipOperator *op = ((BfhipMat const *)lhs)->op;
-  char const *const what = rmul ? "RmulVec" : "MulVec";
-  int const transpose = rmul != ((BfhipMat const *)lhs)->transposed;          /* x^T (A^T) = (A x)^T */
-  if (!vec || !vec->vtbl) SHIM_FAIL(BFABI_ERROR_INVALID_ARGUMENTS, "%s: NULL vector", what);
-  BfAbiVecGetTypeFn getType = (BfAbiVecGetTypeFn)vec->vtbl->slot[BFABI_VSLOT_GetType];
-  if (!getType || getType(vec) != BFABI_TYPE_VEC_REAL || op->srcDtype != BFHIP_F64)
-    SHIM_FAIL(BFABI_ERROR_NOT_IMPLEMENTED, "%s needs a real operator and a BfVecReal", what);
-  if (transpose && !op->hasTplan) SHIM_FAIL(BFABI_ERROR_NOT_IMPLEMENTED, "%s needs an operator compiled with BFHIP_FLAG_ADJOINT", what);
-  BfhipMat const *self = (BfhipMat const *)lhs;
-  uint64_t const inLen = transpose ? shimOpRows(self) : shimOpCols(self);
-  uint64_t const outLen = transpose ? shimOpCols(self) : shimOpRows(self);
-  if (vec->size != inLen)
-    SHIM_FAIL(BFABI_ERROR_INCOMPATIBLE_SHAPES, "%s: operator expects %llu entries, vector has %llu", what, (unsigned long long)inLen, (unsigned long long)vec->size);
-  BfAbiVecReal const *x = (BfAbiVecReal const *)vec;
-  BfAbiVecReal *y = malloc(sizeof *y);
-  double *data = malloc((outLen ? outLen : 1) * sizeof(double));
-  if (!y || !data) { free(y); free(data); SHIM_FAIL(BFABI_ERROR_MEMORY_ERROR, "host OOM"); }
-  y->super.vtbl = vec->vtbl;
-  y->super.props = BFABI_VEC_PROPS_NONE;
-  y->super.size = outLen;
-  y->stride = 1;
-  y->data = data;
-  int rc = shimApplyHost(self, transpose, x->data, x->stride, 1, y->data, 1);
-  if (rc) { free(data); free(y); shimRaise(rc); return NULL; }
-  return &y->super;
-}
-static BfAbiVec *shimMulVec(BfAbiMat const *lhs, BfAbiVec const *vec) { return shimApplyVec(lhs, vec, 0); }
-static BfAbiVec *shimRmulVec(BfAbiMat const *lhs, BfAbiVec const *vec) { return shimApplyVec(lhs, vec, 1); }
-
-/* ToType (slot 54, bfMatToType) densifies through the extraction of bfhip_extract.c.  The slot is referenced weakly so that this
- * file still links without that one (the host sanitizer harness links the plan-side files alone: there the slot stays NULL). */
-extern BfAbiMat *bfhipShimToType(BfAbiMat const *m, int type) __attribute__((weak));
-
-static BfAbiMatVtable ShimVtable = {.slot = {
-  [BFABI_SLOT_GetView] = (void *)shimGetView,
-  [BFABI_SLOT_RmulVec] = (void *)shimRmulVec,
-  [BFABI_SLOT_Delete] = (void *)shimDelete,
-  [BFABI_SLOT_GetType] = (void *)shimGetType,
-  [BFABI_SLOT_NumBytes] = (void *)shimNumBytes,
-  [BFABI_SLOT_GetNumRows] = (void *)shimGetNumRows,
-  [BFABI_SLOT_GetNumCols] = (void *)shimGetNumCols,
-  [BFABI_SLOT_Mul] = (void *)shimMul,
-  [BFABI_SLOT_Rmul] = (void *)shimRmul,
-  [BFABI_SLOT_MulVec] = (void *)shimMulVec,
-  [BFABI_SLOT_Transpose] = (void *)shimTranspose,
-  [BFABI_SLOT_ToType] = (void *)bfhipShimToType,
-}};
-
-int bfhipShimGet(void const *mat, BfhipOperator **op, int *transposed, int *sharded) {
-  BfhipMat const *s = mat;
-  if (!s || s->super.vtbl != &ShimVtable) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "not a bfhipMatNew object");
-  if (op) *op = s->op;
-  if (transposed) *transposed = s->transposed;
-  if (sharded) *sharded = s->sh != NULL;
-  return 0;
-}
-void bfhipShimRaise(int code) { shimRaise(code); }
-
-void *bfhipMatNew(BfhipOperator *op, int ownsOperator) {
-  if (!op) { bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL operator"); return NULL; }
-  BfhipMat *m = calloc(1, sizeof *m);
-  if (!m) { bfhipFail(BFABI_ERROR_MEMORY_ERROR, "host OOM"); return NULL; }
-  m->super.vtbl = &ShimVtable;
-  m->super.props = BFABI_MAT_PROPS_NONE;
-  m->super.numRows = op->plan.numRows;
-  m->super.numCols = op->plan.numCols;
-  m->op = op;
-  m->ownsOperator = ownsOperator;
-  return m;
-}
-
-/* the same object over a sharded operator: shapes are the whole operator's, applies are the sharded step */
-void *bfhipShardedMatNew(struct BfhipSharded *sh, int ownsSharded) {
-  if (!sh) { bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL sharded operator"); return NULL; }
-  BfhipMat *m = calloc(1, sizeof *m);
-  if (!m) { bfhipFail(BFABI_ERROR_MEMORY_ERROR, "host OOM"); return NULL; }
-  m->super.vtbl = &ShimVtable;
-  m->super.props = BFABI_MAT_PROPS_NONE;
-  m->super.numRows = bfhipShardedGetNumRows(sh);
-  m->super.numCols = bfhipShardedGetNumCols(sh);
-  m->op = bfhipShardedOperator(sh);
-  m->sh = sh;
-  m->ownsSharded = ownsSharded;
-  return m;
-}

@@ -11,7 +11,7 @@
  * the DMA of panel t overlaps the apply of panel t + 1, and the CPU unpacks panel t - 1 while both run.
  *
  * This file is not part of the host sanitizer harness (tests/test_host_asan.py): it is where the new device launchers are called
- * from.  bfhip_api.c reaches it only through the weakly referenced shim slot and the release pointer stored on the operator. */
+ * from.  bfhip_shim.c reaches it only through the weakly referenced shim slot, bfhip_api.c through the release pointer stored on the operator. */
 #define _GNU_SOURCE
 #include "bfhip_internal.h"
 #include "../../include/bfhip_abi.h"

@@ -268,7 +268,7 @@ int bfhipShardedApplyHost(struct BfhipSharded *sh, int transpose, void const *X,
 struct BfhipOperator *bfhipShardedOperator(struct BfhipSharded const *sh);
 
 /* ------------------------------------------------------------------------
- * Device layer (implemented in bfhip_device.hip)
+ * Device layer (implemented in bfhip_device.hip; the GMRES / refinement kernels at the end of the section in bfhip_gmres.hip)
  * ---------------------------------------------------------------------- */
 int bfdevSetDevice(int device);                 /* -1: keep current; returns BfError */
 int bfdevGetDevice(int *device);
@@ -415,7 +415,7 @@ static inline uint32_t bfSelectReduceKernel(uint32_t dtype, int longLists) {
 uint32_t bfdevPersistentGrid(void);
 int bfdevLaunchPersistC128(void const *stageParams, uint32_t grid, void *tickets, void *timeline, void *stream);
 
-/* dependency-driven launch of a whole forward complex128 plan (bfFlowKernelC128): see bfhip_device.hip */
+/* dependency-driven launch of a whole forward complex128 plan (bfFlowKernelC128): see bfhip_experimental.hip */
 typedef struct BfFlowArgs {
   void const *arena;
   void const *items, *pieces, *itemOut, *writers;   /* flat over all stages; pieces' `ld` holds the vector id they read */
@@ -444,7 +444,7 @@ typedef struct BfReduceArgs {
 int bfdevLaunchReduce(BfReduceArgs const *a, uint32_t count, void *stream);
 int bfdevScalePermute(void *dst, void const *src, void const *scale, int power, uint64_t const *perm, uint64_t n, uint32_t dtype, void *stream);
 
-/* device-resident GMRES building blocks (complex128; bfhip_gmres.c drives them).
+/* device-resident GMRES building blocks (bfhip_gmres.hip; complex128; bfhip_gmres.c drives them).
  * Vectors are n x nrhs row-major; reductions are per RHS column, two-stage and
  * in fixed order (per-block partials, then a tree over the partials), so a
  * solve is bit-reproducible.  `nb` = number of row blocks = partials per RHS. */
@@ -666,7 +666,7 @@ void bfdevStreamDestroy(void *stream);
 int bfdevStreamWaitEvent(void *stream, void *ev);
 int bfdevMemcpy2DAsync(void *dst, size_t dpitch, void const *src, size_t spitch, size_t width, size_t height, void *stream);
 
-/* host side of the extraction (bfhip_api.c keeps the state on the operator; bfhip_extract.c owns what it means) */
+/* host side of the extraction (the operator of bfhip_operator.h keeps the state, bfhip_api.c releases it; bfhip_extract.c owns what it means) */
 /* the operator's extraction workspace slot; `release` is stored and called on it by bfhipFree */
 void **bfhipOperatorExtractSlot(struct BfhipOperator *op, void (*release)(void *));
 /* largest vector-arena elements per right-hand side of the operator's plans (what bfhipOperatorReserveRhs allocates per RHS) */
@@ -682,7 +682,7 @@ void bfhipShimRaise(int code);     /* the reference's bfSetError(code), when for
  * of 64 (<= 0xffff, <= nrhs) that fits; MEMORY_ERROR when not even min(64, nrhs) columns fit.  Host-only. */
 int bfhipHostApplyPanelWidth(uint64_t nrhs, uint64_t perColBytes, uint64_t budget, uint64_t *width);
 
-/* block-Jacobi preconditioner (bfhip_precond.c reads the operator through these; bfhip_api.c does not call it) */
+/* block-Jacobi preconditioner (bfhip_precond.c reads the operator through these; none of bfhip_api.c, bfhip_file.c, bfhip_shim.c, bfhip_inspect.c calls it) */
 /* the forward plan: host mirrors on a plan-only operator, device tables (dItems, dPieces, reduce d*) otherwise */
 BfPlan const *bfhipOperatorPlan(struct BfhipOperator const *op);
 void const *bfhipOperatorArena(struct BfhipOperator const *op);    /* leaf arena on the device; NULL for a plan-only operator */

@@ -1,0 +1,67 @@
+/* bfhip_operator.h -- struct BfhipOperator and the few helpers shared by the files that implement it: bfhip_api.c
+ * (lifetime, compile, apply), bfhip_file.c (save / load), bfhip_shim.c (BfMat vtable) and bfhip_inspect.c (plan inspection).
+ * Private to those four: every other file reads an operator through the bfhipOperator* accessors of bfhip_internal.h.
+ */
+#ifndef BFHIP_OPERATOR_H
+#define BFHIP_OPERATOR_H
+
+#include "bfhip_internal.h"
+
+struct BfhipOperator {
+  BfPlan plan;
+  BfPlan tplan;               /* plan of A^T over the same leaf arena (BFHIP_FLAG_ADJOINT) */
+  int hasTplan;
+  uint32_t srcDtype;          /* dtype of the operand as given (C128 / F64) */
+  int device;
+  uint32_t flags;
+  void *dArena;               /* leaf data */
+  void *dArenaT;              /* BFHIP_FLAG_ADJOINT_PACKED: the leaves of A^T packed for tplan, a FORWARD plan of the transposed expression */
+  void *dTemp;                /* vector arena: intermediates + partial slots, tempElems * maxRhs */
+  void *dZero;                /* 4 KiB of zeros */
+  uint32_t tempRhs;
+  uint64_t metaBytes;
+  uint64_t leafBytesAlgorithmic;
+  /* staging for the host-pointer apply */
+  void *dX, *dY;
+  void *hX, *hY;              /* pinned host mirrors of dX / dY */
+  void *evHost[4];            /* "piece i of the result is in hY" (created on first use) */
+  uint32_t xyRhs;
+  /* profiling */
+  void **evStart, **evStop;   /* [BF_EV_POOL][numStages]: one set per apply in flight, so timing an apply never waits for the one before */
+  double *stageMs;
+  uint64_t *stageLaunches;
+  uint32_t lastNrhs;
+  uint64_t evIssued, evHarvested;   /* applies whose events were recorded / read back */
+  uint64_t applyCount;              /* forward applies so far */
+  void *dCov;                       /* scratch of the covariance products (2 vectors of the longer side) */
+  uint32_t profEvery;               /* events around one apply in profEvery (0, 1: every apply) */
+  /* BFHIP_FLAG_PLAN_ONLY: the IR is kept (borrowed leaf pointers!) for bfhipPlanPackArena; irT: its transposed view when the
+   * adjoint plan has an arena of its own (BFHIP_FLAG_ADJOINT_PACKED), for bfhipPlanPackArenaT */
+  BfIr *ir, *irT;
+  int packedT;
+  uint64_t seed;
+  /* dependency-driven launch of the forward plan (complex128, one right-hand side): flat copies of the index tables */
+  int flow;
+  void *dFlowItems, *dFlowPieces, *dFlowItemOut, *dFlowWriters, *dFlowCounters;
+  uint32_t flowNumItems, flowGrid, flowEpoch, flowQueueBase, flowMaxWriters;
+  uint64_t flowNumBufs;
+  uint8_t evFlow[64];               /* per event set: that apply ran as ONE launch (its time is recorded under stage 0) */
+  uint32_t rhsBlocks;               /* bfhipSetRhsBlocks: 0 = off, else the smallest nrhs whose forward stages run the complex64 block kernels */
+  uint64_t hostApplyBudget;         /* device bytes the host-vector apply may use for vectors; 0 = free memory - BF_HOST_BUDGET_MARGIN */
+  void *extract;                    /* workspace of the dense extraction (bfhip_extract.c), released by extractRelease */
+  void (*extractRelease)(void *);
+};
+
+#define BF_ARENA_SLACK 256u
+#define BF_HOST_PIECE_ROWS 8192u    /* host vectors of more than 4 x this many rows cross PCIe in 4 pieces, copy and DMA overlapped */
+#define BF_EV_POOL 64u
+#define BF_HOST_BUDGET_MARGIN (512ull << 20)   /* automatic host-apply budget: what the device has free, less this */
+
+/* defined in bfhip_api.c; not exported from the library */
+#define BF_HIDDEN __attribute__((visibility("hidden")))
+BF_HIDDEN int packLeavesPlan(BfPlan const *pl, void *dArena, BfIr const *ir, uint64_t seed, void *hostDst);
+BF_HIDDEN int finishOperator(BfhipOperator *op, uint32_t maxRhs);
+BF_HIDDEN void stageLaunchArgs(BfhipOperator const *op, BfPlan const *plan, BfStage const *st, uint32_t nrhs, BfLaunchArgs *a);
+BF_HIDDEN int applyHost(BfhipOperator *op, int transpose, void const *X, size_t ldx, size_t nrhs, void *Y, size_t ldy);
+
+#endif

@@ -14,7 +14,7 @@
  * the result is compiled as a BlockDiag of dense leaves through bfhipCompileIrFill.
  *
  * This file is not part of the host sanitizer harness (tests/test_host_asan.py): it calls the new device launchers.
- * bfhip_api.c does not reference it. */
+ * Neither bfhip_api.c nor bfhip_file.c, bfhip_shim.c or bfhip_inspect.c references it. */
 #define _GNU_SOURCE
 #include "bfhip_internal.h"
 #include "../../include/bfhip_abi.h"

@@ -1,4 +1,4 @@
-"""Test infrastructure: designed GMRES cases that reach the edges of the device Krylov kernels (bfhip_device.hip,
+"""Test infrastructure: designed GMRES cases that reach the edges of the device Krylov kernels (bfhip_gmres.hip,
 bfGmres*Kernel) and of their driver (bfhip_gmres.c, bfGmresRun).
 
 The kernels split each column of length n into nb = min(ceil(n / 256), 1024) row blocks of ceil(n / nb) rows

@@ -1,4 +1,4 @@
-"""The device GMRES (bfhip_gmres.c around the bfGmres* kernels) on every case of tests/gmres_catalogue.py, under both
+"""The device GMRES (bfhip_gmres.c around the bfGmres* kernels of bfhip_gmres.hip) on every case of tests/gmres_catalogue.py, under both
 orthogonalisations and through both entries, against the long-double reference and bounds of tests/gmres_highprec.py:
 finite X, the residual, forward and consistency bounds at the reported numIter, zero-residual columns returned bit for bit,
 bit-identical repeats, host entry = device entry, and exact 2^k equivariance."""

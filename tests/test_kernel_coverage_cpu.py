@@ -32,7 +32,11 @@ def _reached(case, dtype):
 def test_kernel_ids_have_names():
     names = [_capi.kernel_name(i) for i in range(_capi.KERNEL_COUNT)]
     assert all(names) and len(set(names)) == _capi.KERNEL_COUNT
-    assert _capi.kernel_name(_capi.KERNEL_COUNT) is None
+    ext = [_capi.kernel_name(i) for i in range(_capi.KERNEL_EXT_BASE, _capi.KERNEL_EXT_END)]
+    assert all(ext) and len(set(names + ext)) == len(names) + len(ext)
+    assert ext[_capi.KERNEL_C64_MFMA2 - _capi.KERNEL_EXT_BASE] == "bfStageKernelC64Mfma<2 tiles>"
+    for i in (*range(_capi.KERNEL_COUNT, _capi.KERNEL_EXT_BASE), _capi.KERNEL_EXT_END):      # neither range: no name
+        assert _capi.kernel_name(i) is None
     assert names[kc.k_t(kc.C64, True, True, True)] == "bfStageKernelT<C64, wide, coop, nrhs=1>"
     assert names[kc.k_reduce(kc.F32, True)] == "bfReduceKernel<F32, long>"
     assert names[kc.k_tboth(kc.F64, False)] == "bfStageKernelTBoth<F64, nrhs>1>"
