@@ -20,6 +20,9 @@ FLAG_EXACT_COMPLEX = 32
 KERNEL_COUNT = 61          # BFHIP_KERNEL_COUNT (include/bfhip.h): kernel ids of the apply path
 KERNEL_EXT_BASE, KERNEL_EXT_END = 64, 67      # the extension range: kernels only an opted-in operator runs (bfhipSetRhsBlocks)
 KERNEL_C64_MFMA1, KERNEL_C64_MFMA2, KERNEL_C64_MFMA4 = 64, 65, 66
+KERNEL_REAL_EXT_BASE, KERNEL_REAL_EXT_END = 72, 78      # the second extension range: the real element types' block kernels (bfhipSetRealRhsBlocks)
+KERNEL_F64_MFMA1, KERNEL_F64_MFMA2, KERNEL_F64_MFMA4 = 72, 73, 74
+KERNEL_F32_MFMA1, KERNEL_F32_MFMA2, KERNEL_F32_MFMA4 = 75, 76, 77
 
 
 def kernel_name(kernel_id):
@@ -429,6 +432,8 @@ def load():
     lib.bfhipSetHostApplyBudget.restype = C.c_int
     lib.bfhipSetRhsBlocks.argtypes = [vp, C.c_uint32]
     lib.bfhipSetRhsBlocks.restype = C.c_int
+    lib.bfhipSetRealRhsBlocks.argtypes = [vp, C.c_uint32]
+    lib.bfhipSetRealRhsBlocks.restype = C.c_int
     u64p = C.POINTER(C.c_uint64)
     lib.bfhipExtractDevice.argtypes = [vp, u64p, C.c_size_t, u64p, C.c_size_t, vp, C.c_size_t, C.POINTER(BfhipExtractOptions), vp]
     lib.bfhipExtractDevice.restype = C.c_int

@@ -1058,6 +1058,17 @@ int bfhipSetRhsBlocks(BfhipOperator *op, uint32_t minRhs) {
   return 0;
 }
 
+/* The same switch for the real element types, in the same field (an operator has one element type). */
+int bfhipSetRealRhsBlocks(BfhipOperator *op, uint32_t minRhs) {
+  if (!op) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL operator");
+  if (op->plan.dtype != BFHIP_F64 && op->plan.dtype != BFHIP_F32)
+    return bfhipFail(BFABI_ERROR_NOT_IMPLEMENTED, "bfhipSetRealRhsBlocks is the switch of the real element types (F64, F32): complex64 operators take "
+                     "bfhipSetRhsBlocks, complex128 operators already run block kernels (bfStageKernelC128Mfma*) at nrhs >= 2");
+  if (minRhs == 1) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "minRhs must be 0 (off) or at least 2");
+  op->rhsBlocks = minRhs;
+  return 0;
+}
+
 /* A caller who knows the lifetime of its vectors (the Krylov basis of a solver, a right-hand side applied many times) registers
  * them once: bfhipApply / the shim's Mul then DMA straight from / to them instead of packing through the staging buffer. */
 int bfhipHostRegister(void *p, size_t bytes) {

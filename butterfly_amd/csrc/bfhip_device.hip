@@ -133,6 +133,7 @@ __global__ __launch_bounds__(BF_C128_WG_WAVES * 64) BF_C128_ATTR void bfStageKer
 
 #include "bfhip_stage_mfma.h"
 #include "bfhip_stage_mfma_c64.h"
+#include "bfhip_stage_mfma_real.h"
 
 // One row-major piece of MR rows (see the row-major branch of bfStageKernelReal): lane owns 16-byte units u = lane,
 // lane + 64, ... of every row; UNR units are in flight at once, so (MR + 1) * UNR independent loads per lane.  All
@@ -1083,6 +1084,19 @@ int bfdevLaunchStage(BfLaunchArgs const *a, void *stream) {
       { int handled = 0; int const rcx = bfdevLaunchStageExperimental(a, &p, grid, stream, &handled); if (handled) return rcx; }     /* EXPERIMENTAL=1 builds only */
 #endif
       hipLaunchKernelGGL(bfStageKernelC128, dim3(grid), dim3(BF_C128_WG_WAVES * 64), 0, s, p);
+    }
+    else if (L[i].kernel >= BFHIP_KERNEL_REAL_EXT_BASE) {
+      /* F64 / F32 with bfhipSetRealRhsBlocks: one wavefront per item, ordinary and small items alike */
+      dim3 const g((uint32_t)a->numItems), b(64);
+      switch (L[i].kernel) {
+        case BFHIP_KERNEL_F64_MFMA1: hipLaunchKernelGGL((bfStageKernelRealMfma<BFHIP_F64, 1, 4>), g, b, 0, s, p); break;
+        case BFHIP_KERNEL_F64_MFMA2: hipLaunchKernelGGL((bfStageKernelRealMfma<BFHIP_F64, 2, 4>), g, b, 0, s, p); break;
+        case BFHIP_KERNEL_F64_MFMA4: hipLaunchKernelGGL((bfStageKernelRealMfma<BFHIP_F64, 4, 4>), g, b, 0, s, p); break;
+        case BFHIP_KERNEL_F32_MFMA1: hipLaunchKernelGGL((bfStageKernelRealMfma<BFHIP_F32, 1, 4>), g, b, 0, s, p); break;
+        case BFHIP_KERNEL_F32_MFMA2: hipLaunchKernelGGL((bfStageKernelRealMfma<BFHIP_F32, 2, 4>), g, b, 0, s, p); break;
+        case BFHIP_KERNEL_F32_MFMA4: hipLaunchKernelGGL((bfStageKernelRealMfma<BFHIP_F32, 4, 4>), g, b, 0, s, p); break;
+        default: return bfhipFail(BFABI_ERROR_RUNTIME_ERROR, "internal: kernel id %u is not a stage kernel", L[i].kernel);
+      }
     }
     else if (L[i].kernel >= BFHIP_KERNEL_EXT_BASE) {
       /* complex64 with bfhipSetRhsBlocks: one wavefront per item, ordinary and small items alike */

@@ -104,10 +104,20 @@ static char const *const kernelNamesExt[] = {
   [BFHIP_KERNEL_C64_MFMA2 - BFHIP_KERNEL_EXT_BASE] = "bfStageKernelC64Mfma<2 tiles>",
   [BFHIP_KERNEL_C64_MFMA4 - BFHIP_KERNEL_EXT_BASE] = "bfStageKernelC64Mfma<4 tiles>",
 };
+static char const *const kernelNamesRealExt[] = {
+  [BFHIP_KERNEL_F64_MFMA1 - BFHIP_KERNEL_REAL_EXT_BASE] = "bfStageKernelRealMfma<F64, 1 tile>",
+  [BFHIP_KERNEL_F64_MFMA2 - BFHIP_KERNEL_REAL_EXT_BASE] = "bfStageKernelRealMfma<F64, 2 tiles>",
+  [BFHIP_KERNEL_F64_MFMA4 - BFHIP_KERNEL_REAL_EXT_BASE] = "bfStageKernelRealMfma<F64, 4 tiles>",
+  [BFHIP_KERNEL_F32_MFMA1 - BFHIP_KERNEL_REAL_EXT_BASE] = "bfStageKernelRealMfma<F32, 1 tile>",
+  [BFHIP_KERNEL_F32_MFMA2 - BFHIP_KERNEL_REAL_EXT_BASE] = "bfStageKernelRealMfma<F32, 2 tiles>",
+  [BFHIP_KERNEL_F32_MFMA4 - BFHIP_KERNEL_REAL_EXT_BASE] = "bfStageKernelRealMfma<F32, 4 tiles>",
+};
+_Static_assert(sizeof kernelNamesRealExt / sizeof kernelNamesRealExt[0] == BFHIP_KERNEL_REAL_EXT_END - BFHIP_KERNEL_REAL_EXT_BASE, "kernelNamesRealExt: one entry per id of the second extension range");
 _Static_assert(sizeof kernelNames / sizeof kernelNames[0] == BFHIP_KERNEL_COUNT, "kernelNames: one entry per BfhipKernelId");
 _Static_assert(sizeof kernelNamesExt / sizeof kernelNamesExt[0] == BFHIP_KERNEL_EXT_END - BFHIP_KERNEL_EXT_BASE, "kernelNamesExt: one entry per id of the extension range");
 char const *bfhipKernelName(uint32_t id) {
   if (id >= BFHIP_KERNEL_EXT_BASE && id < BFHIP_KERNEL_EXT_END) return kernelNamesExt[id - BFHIP_KERNEL_EXT_BASE];
+  if (id >= BFHIP_KERNEL_REAL_EXT_BASE && id < BFHIP_KERNEL_REAL_EXT_END) return kernelNamesRealExt[id - BFHIP_KERNEL_REAL_EXT_BASE];
   return id < BFHIP_KERNEL_COUNT ? kernelNames[id] : NULL;
 }
 

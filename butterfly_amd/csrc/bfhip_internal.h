@@ -316,7 +316,7 @@ typedef struct BfLaunchArgs {
   int transposed;        /* pieces carry `ld`: lanes own columns of the forward pieces */
   void *tickets;         /* NULL, or BF_TICKET_POOLS x BF_TICKET_STRIDE uint32 owned by this stage, zero between launches (see BfStage.dTickets) */
   uint32_t exactComplex; /* BFHIP_FLAG_EXACT_COMPLEX: the matrix-core kernels form complex products with four real multiplications */
-  uint32_t rhsBlocks;    /* bfhipSetRhsBlocks: forward complex64 stages of nrhs >= rhsBlocks run the block kernels; 0 = off */
+  uint32_t rhsBlocks;    /* bfhipSetRhsBlocks (complex64) / bfhipSetRealRhsBlocks (F64, F32): forward stages of nrhs >= rhsBlocks run the block kernels; 0 = off */
 } BfLaunchArgs;
 #define BF_TICKET_POOLS 64u
 #define BF_TICKET_STRIDE 64u      /* uint32 between two pools' counters: a 256-byte block each -- counters that share a cache line share its atomic unit (measured: 64 packed counters behaved like one) */
@@ -377,6 +377,12 @@ static inline uint32_t bfSelectStageKernels(BfLaunchArgs const *a, BfKernelLaunc
   if (a->dtype == BFHIP_C64 && a->rhsBlocks && a->nrhs >= a->rhsBlocks) {
     out[0].numRanges = 1; out[0].first[0] = 0; out[0].count[0] = a->numItems; out[0].coop[0] = 0;
     out[0].kernel = BFHIP_KERNEL_C64_MFMA1 + (a->nrhs <= 16 ? 0u : a->nrhs <= 32 ? 1u : 2u);
+    return 1;
+  }
+  /* F64 / F32 with their block kernels switched on (bfhipSetRealRhsBlocks): the same single launch */
+  if ((a->dtype == BFHIP_F64 || a->dtype == BFHIP_F32) && a->rhsBlocks && a->nrhs >= a->rhsBlocks) {
+    out[0].numRanges = 1; out[0].first[0] = 0; out[0].count[0] = a->numItems; out[0].coop[0] = 0;
+    out[0].kernel = (a->dtype == BFHIP_F64 ? BFHIP_KERNEL_F64_MFMA1 : BFHIP_KERNEL_F32_MFMA1) + (a->nrhs <= 16 ? 0u : a->nrhs <= 32 ? 1u : 2u);
     return 1;
   }
   /* the real family: items [firstSmall, numItems) are small (four to a wavefront) */

@@ -46,7 +46,7 @@ struct BfhipOperator {
   uint32_t flowNumItems, flowGrid, flowEpoch, flowQueueBase, flowMaxWriters;
   uint64_t flowNumBufs;
   uint8_t evFlow[64];               /* per event set: that apply ran as ONE launch (its time is recorded under stage 0) */
-  uint32_t rhsBlocks;               /* bfhipSetRhsBlocks: 0 = off, else the smallest nrhs whose forward stages run the complex64 block kernels */
+  uint32_t rhsBlocks;               /* bfhipSetRhsBlocks / bfhipSetRealRhsBlocks: 0 = off, else the smallest nrhs whose forward stages run the element type's block kernels */
   uint64_t hostApplyBudget;         /* device bytes the host-vector apply may use for vectors; 0 = free memory - BF_HOST_BUDGET_MARGIN */
   void *extract;                    /* workspace of the dense extraction (bfhip_extract.c), released by extractRelease */
   void (*extractRelease)(void *);

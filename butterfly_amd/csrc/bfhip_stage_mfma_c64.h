@@ -36,8 +36,8 @@
 // one-wavefront workgroup.  The widening converts and the fragment sums are VALU work inside the k-loop (per k-step at MS = 2,
 // NT = 4: 12 converts, 6 adds against 24 MFMAs of 8 passes each); they run while the other wavefront of the SIMD owns the pipe.
 //
-// Only complex64 is built.  A real element type is bfM64Raw / bfM64Step with one scalar per fragment and one MFMA per product
-// (no Gauss sums); table, segments, passes and store stay as they are.
+// Only complex64 is built here.  The real element types (F64, F32) have the same kernel with one scalar per fragment and one MFMA
+// per product in bfhip_stage_mfma_real.h (bfhipSetRealRhsBlocks), which reuses this file's table and constants.
 #ifndef BFHIP_STAGE_MFMA_C64_H
 #define BFHIP_STAGE_MFMA_C64_H
 

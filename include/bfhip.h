@@ -240,8 +240,19 @@ int bfhipSetHostApplyBudget(BfhipOperator *op, uint64_t bytes);
  * deterministic and may differ from the default path's in the last float bit (another summation order).
  * Works on any complex64 operator (compiled, loaded, a complex64 block-Jacobi result, a row shard) and under
  * BFHIP_FLAG_PLAN_ONLY.  Errors: INVALID_ARGUMENTS (NULL operator, minRhs == 1); NOT_IMPLEMENTED for any other element type
- * (complex128 already has block kernels; the real types are not covered). */
+ * (complex128 already has block kernels; the real types are not covered by THIS entry: they have bfhipSetRealRhsBlocks). */
 int bfhipSetRhsBlocks(BfhipOperator *op, uint32_t minRhs);
+
+/* The same switch for F64 / F32 operators (bfStageKernelRealMfma*), with the same contract: 0 = off (the default), otherwise
+ * minRhs >= 2; host-only, works under BFHIP_FLAG_PLAN_ONLY and on compiled, loaded, block-Jacobi-result and row-shard operators.
+ * Forward stages of applies with nrhs >= minRhs run one launch over all items: every leaf element is loaded once per pass of up to
+ * 64 right-hand sides and contracted on the FP64 matrix cores.  F64: products and sums in double as before, in another order.
+ * F32: elements are widened exactly, item sums are accumulated in DOUBLE and rounded to float once at the store (the default F32
+ * kernels accumulate in float), so the block path's results meet a tighter bound and differ from the default path's within float
+ * rounding.  Transposed stages, reduces, plan, arena and saved file are untouched; results are deterministic.
+ * Errors: INVALID_ARGUMENTS (NULL operator, minRhs == 1); NOT_IMPLEMENTED for the complex element types (complex64 has
+ * bfhipSetRhsBlocks; complex128 runs block kernels by default). */
+int bfhipSetRealRhsBlocks(BfhipOperator *op, uint32_t minRhs);
 
 /* ---- dense extraction ------------------------------------------------------ */
 /* Entries of the operator, Out[i * ldOut + j] = A[rows[i], cols[j]]: a block A[I, J] (a near-field block, a check against the
@@ -627,8 +638,13 @@ typedef enum BfhipKernelId {
  * [BFHIP_KERNEL_COUNT, BFHIP_KERNEL_EXT_BASE) are unused. */
 #define BFHIP_KERNEL_EXT_BASE 64u
 enum { BFHIP_KERNEL_C64_MFMA1 = 64, BFHIP_KERNEL_C64_MFMA2 = 65, BFHIP_KERNEL_C64_MFMA4 = 66, BFHIP_KERNEL_EXT_END = 67 };   /* forward complex64 block kernels: nrhs <= 16, <= 32, more */
+/* Second extension range: the forward block kernels of the real element types (bfhipSetRealRhsBlocks); per type nrhs <= 16,
+ * <= 32, more.  Ids [BFHIP_KERNEL_EXT_END, BFHIP_KERNEL_REAL_EXT_BASE) are unused. */
+#define BFHIP_KERNEL_REAL_EXT_BASE 72u
+enum { BFHIP_KERNEL_F64_MFMA1 = 72, BFHIP_KERNEL_F64_MFMA2 = 73, BFHIP_KERNEL_F64_MFMA4 = 74,
+       BFHIP_KERNEL_F32_MFMA1 = 75, BFHIP_KERNEL_F32_MFMA2 = 76, BFHIP_KERNEL_F32_MFMA4 = 77, BFHIP_KERNEL_REAL_EXT_END = 78 };
 /* "bfStageKernelT<F64, wide, coop, nrhs=1>"-style name of a kernel id; NULL for an id that is neither below BFHIP_KERNEL_COUNT
- * nor in [BFHIP_KERNEL_EXT_BASE, BFHIP_KERNEL_EXT_END) */
+ * nor in one of the two extension ranges */
 const char *bfhipKernelName(uint32_t id);
 /* The kernels, in launch order, that applying stage `stage` (numbering as bfhipPlanGetStage) to `nrhs` right-hand sides
  * launches: the stage's own kernels, then one reduce kernel per reduce launch.  Works under BFHIP_FLAG_PLAN_ONLY (no device).
