@@ -23,6 +23,11 @@ KERNEL_C64_MFMA1, KERNEL_C64_MFMA2, KERNEL_C64_MFMA4 = 64, 65, 66
 KERNEL_REAL_EXT_BASE, KERNEL_REAL_EXT_END = 72, 78      # the second extension range: the real element types' block kernels (bfhipSetRealRhsBlocks)
 KERNEL_F64_MFMA1, KERNEL_F64_MFMA2, KERNEL_F64_MFMA4 = 72, 73, 74
 KERNEL_F32_MFMA1, KERNEL_F32_MFMA2, KERNEL_F32_MFMA4 = 75, 76, 77
+KERNEL_T_EXT_BASE, KERNEL_T_EXT_END = 80, 92      # the third extension range: the shared-leaf adjoint's block kernels (bfhipSetAdjointRhsBlocks)
+KERNEL_T_C128_MFMA1, KERNEL_T_C128_MFMA2, KERNEL_T_C128_MFMA4 = 80, 81, 82
+KERNEL_T_F64_MFMA1, KERNEL_T_F64_MFMA2, KERNEL_T_F64_MFMA4 = 83, 84, 85
+KERNEL_T_F32_MFMA1, KERNEL_T_F32_MFMA2, KERNEL_T_F32_MFMA4 = 86, 87, 88
+KERNEL_T_C64_MFMA1, KERNEL_T_C64_MFMA2, KERNEL_T_C64_MFMA4 = 89, 90, 91
 
 
 def kernel_name(kernel_id):
@@ -434,6 +439,8 @@ def load():
     lib.bfhipSetRhsBlocks.restype = C.c_int
     lib.bfhipSetRealRhsBlocks.argtypes = [vp, C.c_uint32]
     lib.bfhipSetRealRhsBlocks.restype = C.c_int
+    lib.bfhipSetAdjointRhsBlocks.argtypes = [vp, C.c_uint32]
+    lib.bfhipSetAdjointRhsBlocks.restype = C.c_int
     u64p = C.POINTER(C.c_uint64)
     lib.bfhipExtractDevice.argtypes = [vp, u64p, C.c_size_t, u64p, C.c_size_t, vp, C.c_size_t, C.POINTER(BfhipExtractOptions), vp]
     lib.bfhipExtractDevice.restype = C.c_int

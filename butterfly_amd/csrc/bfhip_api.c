@@ -686,7 +686,7 @@ void stageLaunchArgs(BfhipOperator const *op, BfPlan const *plan, BfStage const 
   a->x = NULL; a->y = NULL; a->temp = op->dTemp; a->zero = op->dZero; a->nrhs = nrhs; a->dtype = plan->dtype; a->maxRows = st->maxRows;
   a->transposed = plan->transposed;
   a->tickets = NULL;
-  a->exactComplex = (op->flags & BFHIP_FLAG_EXACT_COMPLEX) != 0; a->rhsBlocks = plan == &op->plan ? op->rhsBlocks : 0;      /* the adjoint's plans (shared or packed) keep their kernels */
+  a->exactComplex = (op->flags & BFHIP_FLAG_EXACT_COMPLEX) != 0; a->rhsBlocks = plan == &op->plan ? op->rhsBlocks : op->adjointRhsBlocks;      /* the adjoint's plans (shared or packed) have a switch of their own */
 }
 
 static int runPlan(BfhipOperator *op, BfPlan *plan, void const *dX, size_t nrhs, void *dY, void *stream) {
@@ -1066,6 +1066,15 @@ int bfhipSetRealRhsBlocks(BfhipOperator *op, uint32_t minRhs) {
                      "bfhipSetRhsBlocks, complex128 operators already run block kernels (bfStageKernelC128Mfma*) at nrhs >= 2");
   if (minRhs == 1) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "minRhs must be 0 (off) or at least 2");
   op->rhsBlocks = minRhs;
+  return 0;
+}
+
+/* The adjoint plan's switch, a field of its own: stageLaunchArgs hands it to the launches of op->tplan, shared-leaf or packed. */
+int bfhipSetAdjointRhsBlocks(BfhipOperator *op, uint32_t minRhs) {
+  if (!op) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL operator");
+  if (minRhs == 1) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "minRhs must be 0 (off) or at least 2");
+  if (!op->hasTplan) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "operator has no adjoint plan (compile with BFHIP_FLAG_ADJOINT or BFHIP_FLAG_ADJOINT_PACKED)");
+  op->adjointRhsBlocks = minRhs;
   return 0;
 }
 

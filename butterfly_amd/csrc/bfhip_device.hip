@@ -134,6 +134,7 @@ __global__ __launch_bounds__(BF_C128_WG_WAVES * 64) BF_C128_ATTR void bfStageKer
 #include "bfhip_stage_mfma.h"
 #include "bfhip_stage_mfma_c64.h"
 #include "bfhip_stage_mfma_real.h"
+#include "bfhip_stage_mfma_t.h"
 
 // One row-major piece of MR rows (see the row-major branch of bfStageKernelReal): lane owns 16-byte units u = lane,
 // lane + 64, ... of every row; UNR units are in flight at once, so (MR + 1) * UNR independent loads per lane.  All
@@ -1084,6 +1085,19 @@ int bfdevLaunchStage(BfLaunchArgs const *a, void *stream) {
       { int handled = 0; int const rcx = bfdevLaunchStageExperimental(a, &p, grid, stream, &handled); if (handled) return rcx; }     /* EXPERIMENTAL=1 builds only */
 #endif
       hipLaunchKernelGGL(bfStageKernelC128, dim3(grid), dim3(BF_C128_WG_WAVES * 64), 0, s, p);
+    }
+    else if (L[i].kernel >= BFHIP_KERNEL_T_EXT_BASE) {
+      /* shared-leaf adjoint with bfhipSetAdjointRhsBlocks: one wavefront per item, narrow, wide and shared items alike */
+      dim3 const g((uint32_t)((a->numItems + BF_TM_WG_WAVES - 1) / BF_TM_WG_WAVES)), b(64 * BF_TM_WG_WAVES);
+#define BF_TM_CASES(DT, NAME, W4) \
+        case BFHIP_KERNEL_T_##NAME##_MFMA1: hipLaunchKernelGGL((bfStageKernelTMfma<DT, 1, 4>), g, b, 0, s, p); break; \
+        case BFHIP_KERNEL_T_##NAME##_MFMA2: hipLaunchKernelGGL((bfStageKernelTMfma<DT, 2, 4>), g, b, 0, s, p); break; \
+        case BFHIP_KERNEL_T_##NAME##_MFMA4: hipLaunchKernelGGL((bfStageKernelTMfma<DT, 4, W4>), g, b, 0, s, p); break;
+      switch (L[i].kernel) {
+        BF_TM_CASES(BFHIP_C128, C128, 2) BF_TM_CASES(BFHIP_F64, F64, 4) BF_TM_CASES(BFHIP_F32, F32, 4) BF_TM_CASES(BFHIP_C64, C64, 2)
+        default: return bfhipFail(BFABI_ERROR_RUNTIME_ERROR, "internal: kernel id %u is not a stage kernel", L[i].kernel);
+      }
+#undef BF_TM_CASES
     }
     else if (L[i].kernel >= BFHIP_KERNEL_REAL_EXT_BASE) {
       /* F64 / F32 with bfhipSetRealRhsBlocks: one wavefront per item, ordinary and small items alike */

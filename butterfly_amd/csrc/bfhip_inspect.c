@@ -112,12 +112,21 @@ static char const *const kernelNamesRealExt[] = {
   [BFHIP_KERNEL_F32_MFMA2 - BFHIP_KERNEL_REAL_EXT_BASE] = "bfStageKernelRealMfma<F32, 2 tiles>",
   [BFHIP_KERNEL_F32_MFMA4 - BFHIP_KERNEL_REAL_EXT_BASE] = "bfStageKernelRealMfma<F32, 4 tiles>",
 };
+static char const *const kernelNamesTExt[] = {
+#define BF_TM_NAMES(ID, DT) \
+  [ID##_MFMA1 - BFHIP_KERNEL_T_EXT_BASE] = "bfStageKernelTMfma<" DT ", 1 tile>", [ID##_MFMA2 - BFHIP_KERNEL_T_EXT_BASE] = "bfStageKernelTMfma<" DT ", 2 tiles>", \
+  [ID##_MFMA4 - BFHIP_KERNEL_T_EXT_BASE] = "bfStageKernelTMfma<" DT ", 4 tiles>"
+  BF_TM_NAMES(BFHIP_KERNEL_T_C128, "C128"), BF_TM_NAMES(BFHIP_KERNEL_T_F64, "F64"), BF_TM_NAMES(BFHIP_KERNEL_T_F32, "F32"), BF_TM_NAMES(BFHIP_KERNEL_T_C64, "C64"),
+#undef BF_TM_NAMES
+};
+_Static_assert(sizeof kernelNamesTExt / sizeof kernelNamesTExt[0] == BFHIP_KERNEL_T_EXT_END - BFHIP_KERNEL_T_EXT_BASE, "kernelNamesTExt: one entry per id of the third extension range");
 _Static_assert(sizeof kernelNamesRealExt / sizeof kernelNamesRealExt[0] == BFHIP_KERNEL_REAL_EXT_END - BFHIP_KERNEL_REAL_EXT_BASE, "kernelNamesRealExt: one entry per id of the second extension range");
 _Static_assert(sizeof kernelNames / sizeof kernelNames[0] == BFHIP_KERNEL_COUNT, "kernelNames: one entry per BfhipKernelId");
 _Static_assert(sizeof kernelNamesExt / sizeof kernelNamesExt[0] == BFHIP_KERNEL_EXT_END - BFHIP_KERNEL_EXT_BASE, "kernelNamesExt: one entry per id of the extension range");
 char const *bfhipKernelName(uint32_t id) {
   if (id >= BFHIP_KERNEL_EXT_BASE && id < BFHIP_KERNEL_EXT_END) return kernelNamesExt[id - BFHIP_KERNEL_EXT_BASE];
   if (id >= BFHIP_KERNEL_REAL_EXT_BASE && id < BFHIP_KERNEL_REAL_EXT_END) return kernelNamesRealExt[id - BFHIP_KERNEL_REAL_EXT_BASE];
+  if (id >= BFHIP_KERNEL_T_EXT_BASE && id < BFHIP_KERNEL_T_EXT_END) return kernelNamesTExt[id - BFHIP_KERNEL_T_EXT_BASE];
   return id < BFHIP_KERNEL_COUNT ? kernelNames[id] : NULL;
 }
 

@@ -316,7 +316,8 @@ typedef struct BfLaunchArgs {
   int transposed;        /* pieces carry `ld`: lanes own columns of the forward pieces */
   void *tickets;         /* NULL, or BF_TICKET_POOLS x BF_TICKET_STRIDE uint32 owned by this stage, zero between launches (see BfStage.dTickets) */
   uint32_t exactComplex; /* BFHIP_FLAG_EXACT_COMPLEX: the matrix-core kernels form complex products with four real multiplications */
-  uint32_t rhsBlocks;    /* bfhipSetRhsBlocks (complex64) / bfhipSetRealRhsBlocks (F64, F32): forward stages of nrhs >= rhsBlocks run the block kernels; 0 = off */
+  uint32_t rhsBlocks;    /* forward plan: bfhipSetRhsBlocks (complex64) / bfhipSetRealRhsBlocks (F64, F32); adjoint plan (shared or packed):
+                          * bfhipSetAdjointRhsBlocks: stages of nrhs >= rhsBlocks run the block kernels; 0 = off */
 } BfLaunchArgs;
 #define BF_TICKET_POOLS 64u
 #define BF_TICKET_STRIDE 64u      /* uint32 between two pools' counters: a 256-byte block each -- counters that share a cache line share its atomic unit (measured: 64 packed counters behaved like one) */
@@ -340,6 +341,12 @@ static inline uint32_t bfSelectStageKernels(BfLaunchArgs const *a, BfKernelLaunc
   if (!a->numItems || !bfDtypeKnown(a->dtype)) return 0;
   uint32_t const one = a->nrhs == 1;
   if (a->transposed) {
+    /* shared-leaf adjoint with its block kernels switched on (bfhipSetAdjointRhsBlocks): one launch over all items, narrow, wide and shared alike */
+    if (a->rhsBlocks && a->nrhs >= a->rhsBlocks) {
+      out[0].numRanges = 1; out[0].first[0] = 0; out[0].count[0] = a->numItems; out[0].coop[0] = 0;
+      out[0].kernel = BFHIP_KERNEL_T_EXT_BASE + 3u * (a->dtype == BFHIP_C128 ? 0u : 1u + bfDtypeRealIndex(a->dtype)) + (a->nrhs <= 16 ? 0u : a->nrhs <= 32 ? 1u : 2u);
+      return 1;
+    }
     uint64_t const numNarrow = a->numNarrow < a->numItems ? a->numNarrow : a->numItems;
     if (a->dtype != BFHIP_C128 && numNarrow && numNarrow < a->numItems && a->maxRowsRest > 16) {
       uint64_t const cntW = a->numItems - numNarrow;

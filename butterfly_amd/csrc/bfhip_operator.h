@@ -47,6 +47,7 @@ struct BfhipOperator {
   uint64_t flowNumBufs;
   uint8_t evFlow[64];               /* per event set: that apply ran as ONE launch (its time is recorded under stage 0) */
   uint32_t rhsBlocks;               /* bfhipSetRhsBlocks / bfhipSetRealRhsBlocks: 0 = off, else the smallest nrhs whose forward stages run the element type's block kernels */
+  uint32_t adjointRhsBlocks;        /* bfhipSetAdjointRhsBlocks: the same for the stages of the adjoint plan (shared-leaf: bfStageKernelTMfma; packed: the forward block kernels); independent of rhsBlocks */
   uint64_t hostApplyBudget;         /* device bytes the host-vector apply may use for vectors; 0 = free memory - BF_HOST_BUDGET_MARGIN */
   void *extract;                    /* workspace of the dense extraction (bfhip_extract.c), released by extractRelease */
   void (*extractRelease)(void *);

@@ -35,6 +35,7 @@ def _options(device=-1, flags=0, max_rhs=1, demote_to_f32=False, seed=0, row_blo
 
 RHS_BLOCKS_DEFAULT = 2      # what rhs_blocks=True stands for: the block kernels read the operand once where the default path reads it nrhs times
 REAL_RHS_BLOCKS_DEFAULT = 2 # what real_rhs_blocks=True stands for (F64 / F32 operators)
+ADJOINT_RHS_BLOCKS_DEFAULT = 2   # what adjoint_rhs_blocks=True stands for (any element type)
 
 
 class HipOperator:
@@ -43,14 +44,17 @@ class HipOperator:
         self._keep = list(keep)
         self._lib = _capi.load()
 
-    def _with_rhs_blocks(self, rhs_blocks, real_rhs_blocks=None):
-        """The constructors' `rhs_blocks=` (complex64) and `real_rhs_blocks=` (F64 / F32) keywords: None / False / 0 leaves the
-        switch off, True = RHS_BLOCKS_DEFAULT / REAL_RHS_BLOCKS_DEFAULT, else min_rhs."""
+    def _with_rhs_blocks(self, rhs_blocks, real_rhs_blocks=None, adjoint_rhs_blocks=None):
+        """The constructors' `rhs_blocks=` (complex64), `real_rhs_blocks=` (F64 / F32) and `adjoint_rhs_blocks=` (the adjoint plan
+        of any element type) keywords: None / False / 0 leaves the switch off, True = RHS_BLOCKS_DEFAULT / REAL_RHS_BLOCKS_DEFAULT /
+        ADJOINT_RHS_BLOCKS_DEFAULT, else min_rhs."""
         try:
             if rhs_blocks:
                 self.set_rhs_blocks(RHS_BLOCKS_DEFAULT if rhs_blocks is True else rhs_blocks)
             if real_rhs_blocks:
                 self.set_real_rhs_blocks(REAL_RHS_BLOCKS_DEFAULT if real_rhs_blocks is True else real_rhs_blocks)
+            if adjoint_rhs_blocks:
+                self.set_adjoint_rhs_blocks(ADJOINT_RHS_BLOCKS_DEFAULT if adjoint_rhs_blocks is True else adjoint_rhs_blocks)
         except Exception:
             self.close()
             raise
@@ -66,18 +70,24 @@ class HipOperator:
         (bfStageKernelRealMfma*); 0 = off (the default), otherwise min_rhs >= 2."""
         check(self._lib.bfhipSetRealRhsBlocks(self._h, int(min_rhs)))
 
+    def set_adjoint_rhs_blocks(self, min_rhs):
+        """bfhipSetAdjointRhsBlocks (any element type; the operator needs an adjoint plan): the adjoint plan's stages of applies
+        with nrhs >= min_rhs run block kernels (shared leaves: bfStageKernelTMfma; packed: the forward block kernels); 0 = off
+        (the default), otherwise min_rhs >= 2."""
+        check(self._lib.bfhipSetAdjointRhsBlocks(self._h, int(min_rhs)))
+
     # ---- construction ------------------------------------------------------
     @classmethod
-    def from_bfmat(cls, bfmat_ptr, rhs_blocks=None, real_rhs_blocks=None, **opts):
+    def from_bfmat(cls, bfmat_ptr, rhs_blocks=None, real_rhs_blocks=None, adjoint_rhs_blocks=None, **opts):
         """Compile a reference BfMat object graph (bfhipCompile)."""
         lib = _capi.load()
         h = C.c_void_p()
         o = _options(**opts)
         check(lib.bfhipCompile(C.c_void_p(bfmat_ptr), C.byref(o), C.byref(h)))
-        return cls(h.value)._with_rhs_blocks(rhs_blocks, real_rhs_blocks)
+        return cls(h.value)._with_rhs_blocks(rhs_blocks, real_rhs_blocks, adjoint_rhs_blocks)
 
     @classmethod
-    def from_desc(cls, desc, leaf_values=None, root=None, rhs_blocks=None, real_rhs_blocks=None, **opts):
+    def from_desc(cls, desc, leaf_values=None, root=None, rhs_blocks=None, real_rhs_blocks=None, adjoint_rhs_blocks=None, **opts):
         """Compile a flat descriptor (bfhipCompileDesc); leaves without values are
         synthesized on the device from `seed`."""
         lib = _capi.load()
@@ -86,12 +96,12 @@ class HipOperator:
         o = _options(**opts)
         check(lib.bfhipCompileDesc(da.byref(), C.byref(o), C.byref(h)))
         keep = [da] if (o.flags & _capi.FLAG_PLAN_ONLY) else []
-        return cls(h.value, keep=keep)._with_rhs_blocks(rhs_blocks, real_rhs_blocks)
+        return cls(h.value, keep=keep)._with_rhs_blocks(rhs_blocks, real_rhs_blocks, adjoint_rhs_blocks)
 
     @classmethod
     def build_helm2(cls, desc, points, wavenumber, root=None, workspace_bytes=0, layer_pot="S", normals=None,
                     col_weights=None, self_value=0.0, kr_order=0, orig_index=None, alpha=0.0, beta=0.0, tgt_points=None,
-                    tgt_normals=None, rhs_blocks=None, real_rhs_blocks=None, **opts):
+                    tgt_normals=None, rhs_blocks=None, real_rhs_blocks=None, adjoint_rhs_blocks=None, **opts):
         """bfhipBuildHelm2: lay out `desc` (helm2_structure with recipes=True) and
         compute every leaf on the device from its recipe.  `points` (and
         `normals` for layer_pot="Sp"): [N, 2] in quadtree order.  The operator
@@ -109,11 +119,11 @@ class HipOperator:
         h = C.c_void_p()
         o = _options(**opts)
         check(lib.bfhipBuildHelm2(da.byref(), prob.byref(), C.byref(o), C.byref(h), C.byref(st)))
-        return cls(h.value)._with_rhs_blocks(rhs_blocks, real_rhs_blocks), st.as_dict()
+        return cls(h.value)._with_rhs_blocks(rhs_blocks, real_rhs_blocks, adjoint_rhs_blocks), st.as_dict()
 
     @classmethod
     def fac_helm2_make_multilevel(cls, points, wavenumber, normals=None, col_weights=None, layer_pot="S", self_value=0.0,
-                                  kr_order=0, alpha=0.0, beta=0.0, workspace_bytes=0, tgt_points=None, tgt_normals=None, rhs_blocks=None, real_rhs_blocks=None,
+                                  kr_order=0, alpha=0.0, beta=0.0, workspace_bytes=0, tgt_points=None, tgt_normals=None, rhs_blocks=None, real_rhs_blocks=None, adjoint_rhs_blocks=None,
                                   **opts):
         """bfhipFacHelm2MakeMultilevel[2]: points (original order) -> device operator in one native
         call (C layout + device build).  Returns (operator, perm, build statistics), or with
@@ -133,16 +143,16 @@ class HipOperator:
         check(lib.bfhipFacHelm2MakeMultilevel2(ptr(pts), ptr(nrm), ptr(w), len(pts), ptr(tpts), ptr(tnrm), len(tperm), params.byref(), C.byref(o),
                                                C.byref(h), perm.ctypes.data, tperm.ctypes.data if len(tperm) else None, C.byref(st)))
         perm = perm.astype(np.int64)
-        return cls(h.value)._with_rhs_blocks(rhs_blocks, real_rhs_blocks), (perm if tpts is None else (perm, tperm.astype(np.int64))), st.as_dict()
+        return cls(h.value)._with_rhs_blocks(rhs_blocks, real_rhs_blocks, adjoint_rhs_blocks), (perm if tpts is None else (perm, tperm.astype(np.int64))), st.as_dict()
 
     @classmethod
-    def load(cls, path, rhs_blocks=None, real_rhs_blocks=None, **opts):
+    def load(cls, path, rhs_blocks=None, real_rhs_blocks=None, adjoint_rhs_blocks=None, **opts):
         """bfhipLoad: a previously saved operator, straight into HBM."""
         lib = _capi.load()
         h = C.c_void_p()
         o = _options(**opts)
         check(lib.bfhipLoad(str(path).encode(), C.byref(o), C.byref(h)))
-        return cls(h.value)._with_rhs_blocks(rhs_blocks, real_rhs_blocks)
+        return cls(h.value)._with_rhs_blocks(rhs_blocks, real_rhs_blocks, adjoint_rhs_blocks)
 
     def save(self, path):
         """bfhipSave: packed leaf arena + index metadata of the compiled operator."""

@@ -254,6 +254,22 @@ int bfhipSetRhsBlocks(BfhipOperator *op, uint32_t minRhs);
  * bfhipSetRhsBlocks; complex128 runs block kernels by default). */
 int bfhipSetRealRhsBlocks(BfhipOperator *op, uint32_t minRhs);
 
+/* The adjoint's switch, for all four element types and independent of the two forward switches: 0 = off (the default: every
+ * apply runs exactly the kernels it runs today), otherwise minRhs >= 2; host-only, works under BFHIP_FLAG_PLAN_ONLY and on
+ * compiled, loaded, block-Jacobi-result and row-shard operators.  The stages of the ADJOINT plan of applies with nrhs >= minRhs
+ * (bfhipApplyTranspose[Device], the shim's Rmul, bfhipExtract* with BFHIP_EXTRACT_VIA_ADJOINT, bfhipShardedApplyTransposeDevice):
+ *   - shared-leaf plan (BFHIP_FLAG_ADJOINT): one launch of bfStageKernelTMfma over all items of the stage, narrow, wide and
+ *     shared alike: every leaf element is loaded once per pass of up to 64 right-hand sides (the default kernels walk the item
+ *     once per right-hand side) and contracted on the FP64 matrix cores.  F32 / complex64 fragments are widened exactly,
+ *     everything accumulates in double and is rounded once at the store; complex products are four real products
+ *     (BFHIP_FLAG_EXACT_COMPLEX changes nothing);
+ *   - packed plan (BFHIP_FLAG_ADJOINT_PACKED, a forward plan): complex64 / F64 / F32 stages run the forward block kernels
+ *     (bfStageKernelC64Mfma*, bfStageKernelRealMfma*); complex128 already does.
+ * Plan, arenas, saved file, forward stages and every reduce are untouched; results are deterministic (one owner per output,
+ * no atomics) and differ from the default path's within the element type's rounding (another summation order).
+ * Errors: INVALID_ARGUMENTS (NULL operator, minRhs == 1, an operator without an adjoint plan). */
+int bfhipSetAdjointRhsBlocks(BfhipOperator *op, uint32_t minRhs);
+
 /* ---- dense extraction ------------------------------------------------------ */
 /* Entries of the operator, Out[i * ldOut + j] = A[rows[i], cols[j]]: a block A[I, J] (a near-field block, a check against the
  * dense kernel) or, with rows = cols = NULL, the whole matrix (what the reference's bfMatToType densifies, src/mat_product.c:377-407).
@@ -643,8 +659,16 @@ enum { BFHIP_KERNEL_C64_MFMA1 = 64, BFHIP_KERNEL_C64_MFMA2 = 65, BFHIP_KERNEL_C6
 #define BFHIP_KERNEL_REAL_EXT_BASE 72u
 enum { BFHIP_KERNEL_F64_MFMA1 = 72, BFHIP_KERNEL_F64_MFMA2 = 73, BFHIP_KERNEL_F64_MFMA4 = 74,
        BFHIP_KERNEL_F32_MFMA1 = 75, BFHIP_KERNEL_F32_MFMA2 = 76, BFHIP_KERNEL_F32_MFMA4 = 77, BFHIP_KERNEL_REAL_EXT_END = 78 };
+/* Third extension range: the block kernels of the shared-leaf adjoint (bfhipSetAdjointRhsBlocks), bfStageKernelTMfma: per element
+ * type (in the order of the transposed ids above: C128, F64, F32, C64) nrhs <= 16, <= 32, more.  Ids [BFHIP_KERNEL_REAL_EXT_END,
+ * BFHIP_KERNEL_T_EXT_BASE) are unused. */
+#define BFHIP_KERNEL_T_EXT_BASE 80u
+enum { BFHIP_KERNEL_T_C128_MFMA1 = 80, BFHIP_KERNEL_T_C128_MFMA2 = 81, BFHIP_KERNEL_T_C128_MFMA4 = 82,
+       BFHIP_KERNEL_T_F64_MFMA1 = 83, BFHIP_KERNEL_T_F64_MFMA2 = 84, BFHIP_KERNEL_T_F64_MFMA4 = 85,
+       BFHIP_KERNEL_T_F32_MFMA1 = 86, BFHIP_KERNEL_T_F32_MFMA2 = 87, BFHIP_KERNEL_T_F32_MFMA4 = 88,
+       BFHIP_KERNEL_T_C64_MFMA1 = 89, BFHIP_KERNEL_T_C64_MFMA2 = 90, BFHIP_KERNEL_T_C64_MFMA4 = 91, BFHIP_KERNEL_T_EXT_END = 92 };
 /* "bfStageKernelT<F64, wide, coop, nrhs=1>"-style name of a kernel id; NULL for an id that is neither below BFHIP_KERNEL_COUNT
- * nor in one of the two extension ranges */
+ * nor in one of the three extension ranges */
 const char *bfhipKernelName(uint32_t id);
 /* The kernels, in launch order, that applying stage `stage` (numbering as bfhipPlanGetStage) to `nrhs` right-hand sides
  * launches: the stage's own kernels, then one reduce kernel per reduce launch.  Works under BFHIP_FLAG_PLAN_ONLY (no device).
