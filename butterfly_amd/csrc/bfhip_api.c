@@ -1047,32 +1047,37 @@ int bfhipSetHostApplyBudget(BfhipOperator *op, uint64_t bytes) {
   return 0;
 }
 
-/* Host-only: the setting travels to the stage selection in every BfLaunchArgs (stageLaunchArgs), nothing else reads it. */
-int bfhipSetRhsBlocks(BfhipOperator *op, uint32_t minRhs) {
+/* The three switches of the right-hand-side block kernels.  Host-only: the setting travels to the stage selection in every BfLaunchArgs
+ * (stageLaunchArgs), nothing else reads it.  Their common checks, in the order all three make them: the operator, the element type
+ * (`dtypes` = a bit per element type the switch serves, `wrongType` = the refusal's text for the others), the value. */
+static int rhsBlocksCheck(BfhipOperator const *op, uint32_t minRhs, uint32_t dtypes, char const *wrongType) {
   if (!op) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL operator");
-  if (op->plan.dtype != BFHIP_C64)
-    return bfhipFail(BFABI_ERROR_NOT_IMPLEMENTED, "right-hand-side block kernels are a complex64 switch: complex128 operators already run block kernels "
-                     "(bfStageKernelC128Mfma*) at nrhs >= 2, and the real element types (F64, F32) are not covered");
+  if (!(dtypes >> op->plan.dtype & 1u)) return bfhipFail(BFABI_ERROR_NOT_IMPLEMENTED, "%s", wrongType);
   if (minRhs == 1) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "minRhs must be 0 (off) or at least 2");
-  op->rhsBlocks = minRhs;
   return 0;
+}
+
+int bfhipSetRhsBlocks(BfhipOperator *op, uint32_t minRhs) {
+  int const rc = rhsBlocksCheck(op, minRhs, 1u << BFHIP_C64,
+                                "right-hand-side block kernels are a complex64 switch: complex128 operators already run block kernels "
+                                "(bfStageKernelC128Mfma*) at nrhs >= 2, and the real element types (F64, F32) are not covered");
+  if (!rc) op->rhsBlocks = minRhs;
+  return rc;
 }
 
 /* The same switch for the real element types, in the same field (an operator has one element type). */
 int bfhipSetRealRhsBlocks(BfhipOperator *op, uint32_t minRhs) {
-  if (!op) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL operator");
-  if (op->plan.dtype != BFHIP_F64 && op->plan.dtype != BFHIP_F32)
-    return bfhipFail(BFABI_ERROR_NOT_IMPLEMENTED, "bfhipSetRealRhsBlocks is the switch of the real element types (F64, F32): complex64 operators take "
-                     "bfhipSetRhsBlocks, complex128 operators already run block kernels (bfStageKernelC128Mfma*) at nrhs >= 2");
-  if (minRhs == 1) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "minRhs must be 0 (off) or at least 2");
-  op->rhsBlocks = minRhs;
-  return 0;
+  int const rc = rhsBlocksCheck(op, minRhs, 1u << BFHIP_F64 | 1u << BFHIP_F32,
+                                "bfhipSetRealRhsBlocks is the switch of the real element types (F64, F32): complex64 operators take "
+                                "bfhipSetRhsBlocks, complex128 operators already run block kernels (bfStageKernelC128Mfma*) at nrhs >= 2");
+  if (!rc) op->rhsBlocks = minRhs;
+  return rc;
 }
 
 /* The adjoint plan's switch, a field of its own: stageLaunchArgs hands it to the launches of op->tplan, shared-leaf or packed. */
 int bfhipSetAdjointRhsBlocks(BfhipOperator *op, uint32_t minRhs) {
-  if (!op) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL operator");
-  if (minRhs == 1) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "minRhs must be 0 (off) or at least 2");
+  int const rc = rhsBlocksCheck(op, minRhs, ~0u, NULL);
+  if (rc) return rc;
   if (!op->hasTplan) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "operator has no adjoint plan (compile with BFHIP_FLAG_ADJOINT or BFHIP_FLAG_ADJOINT_PACKED)");
   op->adjointRhsBlocks = minRhs;
   return 0;

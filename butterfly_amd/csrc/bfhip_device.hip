@@ -132,9 +132,7 @@ __global__ __launch_bounds__(BF_C128_WG_WAVES * 64) BF_C128_ATTR void bfStageKer
 }
 
 #include "bfhip_stage_mfma.h"
-#include "bfhip_stage_mfma_c64.h"
-#include "bfhip_stage_mfma_real.h"
-#include "bfhip_stage_mfma_t.h"
+#include "bfhip_stage_mfma_blocks.h"
 
 // One row-major piece of MR rows (see the row-major branch of bfStageKernelReal): lane owns 16-byte units u = lane,
 // lane + 64, ... of every row; UNR units are in flight at once, so (MR + 1) * UNR independent loads per lane.  All
@@ -1086,41 +1084,24 @@ int bfdevLaunchStage(BfLaunchArgs const *a, void *stream) {
 #endif
       hipLaunchKernelGGL(bfStageKernelC128, dim3(grid), dim3(BF_C128_WG_WAVES * 64), 0, s, p);
     }
-    else if (L[i].kernel >= BFHIP_KERNEL_T_EXT_BASE) {
-      /* shared-leaf adjoint with bfhipSetAdjointRhsBlocks: one wavefront per item, narrow, wide and shared items alike */
-      dim3 const g((uint32_t)((a->numItems + BF_TM_WG_WAVES - 1) / BF_TM_WG_WAVES)), b(64 * BF_TM_WG_WAVES);
-#define BF_TM_CASES(DT, NAME, W4) \
-        case BFHIP_KERNEL_T_##NAME##_MFMA1: hipLaunchKernelGGL((bfStageKernelTMfma<DT, 1, 4>), g, b, 0, s, p); break; \
-        case BFHIP_KERNEL_T_##NAME##_MFMA2: hipLaunchKernelGGL((bfStageKernelTMfma<DT, 2, 4>), g, b, 0, s, p); break; \
-        case BFHIP_KERNEL_T_##NAME##_MFMA4: hipLaunchKernelGGL((bfStageKernelTMfma<DT, 4, W4>), g, b, 0, s, p); break;
-      switch (L[i].kernel) {
-        BF_TM_CASES(BFHIP_C128, C128, 2) BF_TM_CASES(BFHIP_F64, F64, 4) BF_TM_CASES(BFHIP_F32, F32, 4) BF_TM_CASES(BFHIP_C64, C64, 2)
-        default: return bfhipFail(BFABI_ERROR_RUNTIME_ERROR, "internal: kernel id %u is not a stage kernel", L[i].kernel);
-      }
-#undef BF_TM_CASES
-    }
-    else if (L[i].kernel >= BFHIP_KERNEL_REAL_EXT_BASE) {
-      /* F64 / F32 with bfhipSetRealRhsBlocks: one wavefront per item, ordinary and small items alike */
-      dim3 const g((uint32_t)a->numItems), b(64);
-      switch (L[i].kernel) {
-        case BFHIP_KERNEL_F64_MFMA1: hipLaunchKernelGGL((bfStageKernelRealMfma<BFHIP_F64, 1, 4>), g, b, 0, s, p); break;
-        case BFHIP_KERNEL_F64_MFMA2: hipLaunchKernelGGL((bfStageKernelRealMfma<BFHIP_F64, 2, 4>), g, b, 0, s, p); break;
-        case BFHIP_KERNEL_F64_MFMA4: hipLaunchKernelGGL((bfStageKernelRealMfma<BFHIP_F64, 4, 4>), g, b, 0, s, p); break;
-        case BFHIP_KERNEL_F32_MFMA1: hipLaunchKernelGGL((bfStageKernelRealMfma<BFHIP_F32, 1, 4>), g, b, 0, s, p); break;
-        case BFHIP_KERNEL_F32_MFMA2: hipLaunchKernelGGL((bfStageKernelRealMfma<BFHIP_F32, 2, 4>), g, b, 0, s, p); break;
-        case BFHIP_KERNEL_F32_MFMA4: hipLaunchKernelGGL((bfStageKernelRealMfma<BFHIP_F32, 4, 4>), g, b, 0, s, p); break;
-        default: return bfhipFail(BFABI_ERROR_RUNTIME_ERROR, "internal: kernel id %u is not a stage kernel", L[i].kernel);
-      }
-    }
     else if (L[i].kernel >= BFHIP_KERNEL_EXT_BASE) {
-      /* complex64 with bfhipSetRhsBlocks: one wavefront per item, ordinary and small items alike */
-      dim3 const g((uint32_t)a->numItems), b(64);
+      /* the opt-in block kernels (bfhipSetRhsBlocks, bfhipSetRealRhsBlocks, bfhipSetAdjointRhsBlocks): one wavefront per item, every kind
+       * of item alike; a workgroup of the forward kernels is one wavefront, of the transposed kernel BF_TM_WG_WAVES list neighbours */
+      uint32_t const wg = L[i].kernel >= BFHIP_KERNEL_T_EXT_BASE ? BF_TM_WG_WAVES : 1;
+      dim3 const g((uint32_t)((a->numItems + wg - 1) / wg)), b(64 * wg);
+      /* ids ID_MFMA1 / 2 / 4 = KERNEL<DT (if it has one), tiles, wavefronts per SIMD>: 4 at one tile, W2 at two, W4 at four */
+#define BF_BLK_CASES(ID, KERNEL, W2, W4, ...) \
+        case ID##_MFMA1: hipLaunchKernelGGL((KERNEL<__VA_ARGS__ __VA_OPT__(,) 1, 4>), g, b, 0, s, p); break; \
+        case ID##_MFMA2: hipLaunchKernelGGL((KERNEL<__VA_ARGS__ __VA_OPT__(,) 2, W2>), g, b, 0, s, p); break; \
+        case ID##_MFMA4: hipLaunchKernelGGL((KERNEL<__VA_ARGS__ __VA_OPT__(,) 4, W4>), g, b, 0, s, p); break;
       switch (L[i].kernel) {
-        case BFHIP_KERNEL_C64_MFMA1: hipLaunchKernelGGL((bfStageKernelC64Mfma<1, 4>), g, b, 0, s, p); break;
-        case BFHIP_KERNEL_C64_MFMA2: hipLaunchKernelGGL((bfStageKernelC64Mfma<2, 3>), g, b, 0, s, p); break;
-        case BFHIP_KERNEL_C64_MFMA4: hipLaunchKernelGGL((bfStageKernelC64Mfma<4, 2>), g, b, 0, s, p); break;
+        BF_BLK_CASES(BFHIP_KERNEL_C64, bfStageKernelC64Mfma, 3, 2)
+        BF_BLK_CASES(BFHIP_KERNEL_F64, bfStageKernelRealMfma, 4, 4, BFHIP_F64) BF_BLK_CASES(BFHIP_KERNEL_F32, bfStageKernelRealMfma, 4, 4, BFHIP_F32)
+        BF_BLK_CASES(BFHIP_KERNEL_T_C128, bfStageKernelTMfma, 4, 2, BFHIP_C128) BF_BLK_CASES(BFHIP_KERNEL_T_F64, bfStageKernelTMfma, 4, 4, BFHIP_F64)
+        BF_BLK_CASES(BFHIP_KERNEL_T_F32, bfStageKernelTMfma, 4, 4, BFHIP_F32) BF_BLK_CASES(BFHIP_KERNEL_T_C64, bfStageKernelTMfma, 4, 2, BFHIP_C64)
         default: return bfhipFail(BFABI_ERROR_RUNTIME_ERROR, "internal: kernel id %u is not a stage kernel", L[i].kernel);
       }
+#undef BF_BLK_CASES
     }
     else if (L[i].kernel <= BFHIP_KERNEL_C128_MFMA4_EXACT) {
       dim3 const g((uint32_t)((a->numItems + BF_MF_WG_WAVES - 1) / BF_MF_WG_WAVES)), b(64 * BF_MF_WG_WAVES);

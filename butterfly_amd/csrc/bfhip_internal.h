@@ -336,17 +336,26 @@ typedef struct BfKernelLaunch {
 } BfKernelLaunch;
 static inline uint32_t bfDtypeRealIndex(uint32_t dt) { return dt == BFHIP_F64 ? 0u : dt == BFHIP_F32 ? 1u : 2u; }   /* F64, F32, C64 */
 static inline uint32_t bfDtypeKnown(uint32_t dt) { return dt == BFHIP_C128 || dt == BFHIP_F64 || dt == BFHIP_F32 || dt == BFHIP_C64; }
+/* the matrix-core kernels come in three widths: passes of 1, 2 or 4 tiles of 16 right-hand sides (ids ..._MFMA1, _MFMA2, _MFMA4 in a row) */
+static inline uint32_t bfRhsTileIndex(uint32_t nrhs) { return nrhs <= 16 ? 0u : nrhs <= 32 ? 1u : 2u; }
+/* first id of the opt-in block kernels of a plan (bfhip_stage_mfma_blocks.h); 0: none (complex128 forward runs bfStageKernelC128Mfma* whatever the switch) */
+static inline uint32_t bfRhsBlockKernelBase(int transposed, uint32_t dt) {
+  if (transposed) return BFHIP_KERNEL_T_EXT_BASE + 3u * (dt == BFHIP_C128 ? 0u : 1u + bfDtypeRealIndex(dt));      /* C128, F64, F32, C64 */
+  return dt == BFHIP_C64 ? BFHIP_KERNEL_C64_MFMA1 : dt == BFHIP_F64 ? BFHIP_KERNEL_F64_MFMA1 : dt == BFHIP_F32 ? BFHIP_KERNEL_F32_MFMA1 : 0u;
+}
 /* returns the number of launches (0 - 2) written to out[]; an unknown dtype gives 0 */
 static inline uint32_t bfSelectStageKernels(BfLaunchArgs const *a, BfKernelLaunch out[2]) {
   if (!a->numItems || !bfDtypeKnown(a->dtype)) return 0;
   uint32_t const one = a->nrhs == 1;
+  /* the plan's block kernels switched on (forward plan: bfhipSetRhsBlocks / bfhipSetRealRhsBlocks; adjoint plan, shared-leaf or packed:
+   * bfhipSetAdjointRhsBlocks): one launch over all items -- ordinary and small, or narrow, wide and shared alike */
+  uint32_t const blockBase = bfRhsBlockKernelBase(a->transposed, a->dtype);
+  if (blockBase && a->rhsBlocks && a->nrhs >= a->rhsBlocks) {
+    out[0].numRanges = 1; out[0].first[0] = 0; out[0].count[0] = a->numItems; out[0].coop[0] = 0;
+    out[0].kernel = blockBase + bfRhsTileIndex(a->nrhs);
+    return 1;
+  }
   if (a->transposed) {
-    /* shared-leaf adjoint with its block kernels switched on (bfhipSetAdjointRhsBlocks): one launch over all items, narrow, wide and shared alike */
-    if (a->rhsBlocks && a->nrhs >= a->rhsBlocks) {
-      out[0].numRanges = 1; out[0].first[0] = 0; out[0].count[0] = a->numItems; out[0].coop[0] = 0;
-      out[0].kernel = BFHIP_KERNEL_T_EXT_BASE + 3u * (a->dtype == BFHIP_C128 ? 0u : 1u + bfDtypeRealIndex(a->dtype)) + (a->nrhs <= 16 ? 0u : a->nrhs <= 32 ? 1u : 2u);
-      return 1;
-    }
     uint64_t const numNarrow = a->numNarrow < a->numItems ? a->numNarrow : a->numItems;
     if (a->dtype != BFHIP_C128 && numNarrow && numNarrow < a->numItems && a->maxRowsRest > 16) {
       uint64_t const cntW = a->numItems - numNarrow;
@@ -377,19 +386,7 @@ static inline uint32_t bfSelectStageKernels(BfLaunchArgs const *a, BfKernelLaunc
   if (a->dtype == BFHIP_C128) {
     out[0].numRanges = 1; out[0].first[0] = 0; out[0].count[0] = a->numItems; out[0].coop[0] = 0;
     if (a->nrhs < BF_MFMA_MIN_RHS) out[0].kernel = BFHIP_KERNEL_C128;
-    else out[0].kernel = (a->exactComplex ? BFHIP_KERNEL_C128_MFMA1_EXACT : BFHIP_KERNEL_C128_MFMA1) + (a->nrhs <= 16 ? 0u : a->nrhs <= 32 ? 1u : 2u);
-    return 1;
-  }
-  /* complex64 with the block kernels switched on: one launch over all items, ordinary and small alike */
-  if (a->dtype == BFHIP_C64 && a->rhsBlocks && a->nrhs >= a->rhsBlocks) {
-    out[0].numRanges = 1; out[0].first[0] = 0; out[0].count[0] = a->numItems; out[0].coop[0] = 0;
-    out[0].kernel = BFHIP_KERNEL_C64_MFMA1 + (a->nrhs <= 16 ? 0u : a->nrhs <= 32 ? 1u : 2u);
-    return 1;
-  }
-  /* F64 / F32 with their block kernels switched on (bfhipSetRealRhsBlocks): the same single launch */
-  if ((a->dtype == BFHIP_F64 || a->dtype == BFHIP_F32) && a->rhsBlocks && a->nrhs >= a->rhsBlocks) {
-    out[0].numRanges = 1; out[0].first[0] = 0; out[0].count[0] = a->numItems; out[0].coop[0] = 0;
-    out[0].kernel = (a->dtype == BFHIP_F64 ? BFHIP_KERNEL_F64_MFMA1 : BFHIP_KERNEL_F32_MFMA1) + (a->nrhs <= 16 ? 0u : a->nrhs <= 32 ? 1u : 2u);
+    else out[0].kernel = (a->exactComplex ? BFHIP_KERNEL_C128_MFMA1_EXACT : BFHIP_KERNEL_C128_MFMA1) + bfRhsTileIndex(a->nrhs);
     return 1;
   }
   /* the real family: items [firstSmall, numItems) are small (four to a wavefront) */

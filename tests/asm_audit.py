@@ -12,7 +12,11 @@ before it may still be writing.  Straight-line model of every innermost MFMA loo
 counters ahead of the loop (so that its prologue requests are in the queues), the body three times (a load at the bottom of an
 iteration met by a reader at the top of the next).  s_waitcnt retires all but the n youngest of a queue; scalar loads (which
 return out of order) are counted conservatively as entries that only lgkmcnt(0) retires."""
+import functools
+import os
 import re
+import subprocess
+import tempfile
 
 _VREG = re.compile(r"\bv(\d+)\b|\bv\[(\d+):(\d+)\]")
 _LABEL = re.compile(r"^(\.LBB\d+_\d+):")
@@ -27,6 +31,31 @@ def _vregs(text):
         else:
             out.update(range(int(m.group(2)), int(m.group(3)) + 1))
     return out
+
+
+@functools.lru_cache(maxsize=None)
+def device_code_object():
+    """(asm_text, usage) of butterfly_amd/csrc/bfhip_device.hip compiled for gfx950 with -Rpass-analysis=kernel-resource-usage:
+    the device assembly, and per kernel symbol the remarks' figures ({"VGPRs": n, "ScratchSize": n, "LDS Size": n, "Occupancy": n,
+    "VGPRs Spill": n, ...}; units in brackets dropped from the keys).  Compiled once per process, whoever asks."""
+    hipcc = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "bin", "hipcc")
+    src = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "butterfly_amd", "csrc", "bfhip_device.hip")
+    with tempfile.TemporaryDirectory() as tmp:
+        r = subprocess.run([hipcc, "-O3", "-fPIC", "--offload-arch=gfx950", "-std=c++17", "-Rpass-analysis=kernel-resource-usage",
+                            "--cuda-device-only", "-S", src, "-o", os.path.join(tmp, "d.s")], capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr[-2000:]
+        asm = open(os.path.join(tmp, "d.s")).read()
+    usage, cur = {}, None
+    for line in r.stderr.splitlines():
+        m = re.search(r"Function Name: (\S+)", line)
+        if m:
+            cur = m.group(1)
+            usage[cur] = {}
+            continue
+        m = re.search(r"remark:\s+(\w[\w ]*?)(?: \[[\w/]+\])?: (\d+) \[", line)
+        if cur and m:
+            usage[cur][m.group(1)] = int(m.group(2))
+    return asm, usage
 
 
 def function_body(asm_text, symbol):

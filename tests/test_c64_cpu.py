@@ -6,8 +6,6 @@ complex128 value rounded once to float."""
 import ctypes as C
 import os
 import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
@@ -212,22 +210,8 @@ def test_helm2_builders_refuse_complex64():
 
 
 def test_c64_kernels_use_no_scratch_and_spill_nothing():
-    hipcc = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "bin", "hipcc")
-    src = os.path.join(ROOT, "butterfly_amd", "csrc", "bfhip_device.hip")
-    with tempfile.TemporaryDirectory() as tmp:
-        r = subprocess.run([hipcc, "-O3", "-fPIC", "--offload-arch=gfx950", "-std=c++17", "-Rpass-analysis=kernel-resource-usage",
-                            "-c", src, "-o", os.path.join(tmp, "d.o")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    usage, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1)
-            usage[cur] = {}
-            continue
-        m = re.search(r"remark:\s+(\w[\w ]*?)(?: \[bytes/lane\])?: (\d+) \[", line)
-        if cur and m:
-            usage[cur][m.group(1)] = int(m.group(2))
+    import asm_audit
+    _, usage = asm_audit.device_code_object()
     c64 = {k: v for k, v in usage.items() if "ILi3E" in k or "bfReduceKernelIfLi2E" in k}
     names = " ".join(c64)
     for family in ("bfStageKernelReal", "bfStageKernelRealBoth", "bfStageKernelSmall", "bfStageKernelT", "bfStageKernelTBoth",

@@ -10,8 +10,6 @@
 import ctypes as C
 import os
 import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
@@ -121,23 +119,7 @@ def test_refusals_and_extension_ids():
 
 def test_block_kernels_use_no_scratch_and_contract_in_double():
     import asm_audit
-    hipcc = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "bin", "hipcc")
-    src = os.path.join(ROOT, "butterfly_amd", "csrc", "bfhip_device.hip")
-    with tempfile.TemporaryDirectory() as tmp:
-        r = subprocess.run([hipcc, "-O3", "-fPIC", "--offload-arch=gfx950", "-std=c++17", "-Rpass-analysis=kernel-resource-usage",
-                            "--cuda-device-only", "-S", src, "-o", os.path.join(tmp, "d.s")], capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr[-2000:]
-        asm = open(os.path.join(tmp, "d.s")).read()
-    usage, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1)
-            usage[cur] = {}
-            continue
-        m = re.search(r"remark:\s+(\w[\w ]*?)(?: \[[\w/]+\])?: (\d+) \[", line)
-        if cur and m:
-            usage[cur][m.group(1)] = int(m.group(2))
+    asm, usage = asm_audit.device_code_object()
     mine = {k: v for k, v in usage.items() if re.match(r"_Z\d+bfStageKernelC64MfmaI", k)}
     assert len(mine) == 3, sorted(mine)
     for sym, v in mine.items():
