@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 #include <dlfcn.h>
+#include <pthread.h>
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
@@ -38,19 +39,43 @@ struct Rccl {
 };
 Rccl g;
 
-int loadRccl() {
+pthread_mutex_t gLoadLock = PTHREAD_MUTEX_INITIALIZER;
+
+// Fills a local table and publishes it whole, under a lock: first bfhipComm* calls may race (include/bfhip.h "Threads")
+int loadRcclLocked() {
   if (g.lib) return 0;
   char const *names[] = {"librccl.so.1", "librccl.so"};
   void *lib = NULL;
+  char const *named = getenv("BFHIP_RCCL_LIBRARY");     // a path names THE library: nothing else is tried (include/bfhip.h)
+  if (named && *named) {
+    lib = dlopen(named, RTLD_NOW | RTLD_LOCAL);
+    if (!lib) return bfhipFail(BFABI_ERROR_RUNTIME_ERROR, "BFHIP_RCCL_LIBRARY=%s cannot be loaded: %s", named, dlerror());
+  } else named = NULL;
   for (int pass = 0; pass < 2 && !lib; ++pass)         // pass 0: a copy already mapped (torch's); pass 1: load one
     for (int i = 0; i < 2 && !lib; ++i) lib = dlopen(names[i], RTLD_NOW | RTLD_GLOBAL | (pass == 0 ? RTLD_NOLOAD : 0));
   if (!lib) return bfhipFail(BFABI_ERROR_RUNTIME_ERROR, "RCCL not found (librccl.so.1): %s", dlerror());
-#define SYM(field, name) do { *(void **)&g.field = dlsym(lib, name); if (!g.field) return bfhipFail(BFABI_ERROR_RUNTIME_ERROR, "RCCL lacks %s", name); } while (0)
+  Rccl t;
+  memset(&t, 0, sizeof t);
+  char const *lacks = NULL;
+#define SYM(field, name) do { *(void **)&t.field = dlsym(lib, name); if (!t.field && !lacks) lacks = name; } while (0)
   SYM(GetUniqueId, "ncclGetUniqueId"); SYM(CommInitRank, "ncclCommInitRank"); SYM(CommDestroy, "ncclCommDestroy"); SYM(CommAbort, "ncclCommAbort");
   SYM(AllGather, "ncclAllGather"); SYM(AllReduce, "ncclAllReduce"); SYM(GetErrorString, "ncclGetErrorString");
 #undef SYM
-  g.lib = lib;
+  if (lacks) {
+    (void)dlclose(lib);
+    if (named) return bfhipFail(BFABI_ERROR_RUNTIME_ERROR, "BFHIP_RCCL_LIBRARY=%s lacks %s", named, lacks);
+    return bfhipFail(BFABI_ERROR_RUNTIME_ERROR, "RCCL lacks %s", lacks);
+  }
+  t.lib = lib;
+  g = t;
   return 0;
+}
+
+int loadRccl() {
+  pthread_mutex_lock(&gLoadLock);
+  int const rc = loadRcclLocked();
+  pthread_mutex_unlock(&gLoadLock);
+  return rc;
 }
 
 int ncclFail(ncclResult_t r, char const *what) {

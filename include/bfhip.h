@@ -350,7 +350,14 @@ int bfhipSolveGMRESDevice(BfhipOperator *op, const void *dB, size_t nrhs, const 
  *                     summation order is RCCL's: equal to one GPU to rounding, not bit for bit (ROWS is).
  * Everything is enqueued on `stream` behind the stage kernels; nothing synchronizes the host.  RCCL is
  * looked up at run time (the copy already in the process, else librccl.so.1); without it these entry
- * points return RUNTIME_ERROR and the rest of the library works. */
+ * points return RUNTIME_ERROR and the rest of the library works.
+ * The environment variable BFHIP_RCCL_LIBRARY, read at the first bfhipComm* call of the process, names the collective
+ * library by path (a host whose RCCL is not on the default path; a stand-in that exports the same seven nccl* symbols):
+ * it is then the ONLY library tried (dlopen RTLD_NOW | RTLD_LOCAL), and a path that cannot be loaded is a RUNTIME_ERROR
+ * naming it, as is one that loads but lacks a symbol -- no fallback to librccl.  Unset or empty: the lookup above.
+ * Threads: a BfhipSharded / BfhipComm belongs to one thread at a time; different threads may drive DIFFERENT sharded
+ * operators (each over its own operator and communicator) concurrently.  The library lookup itself is serialised: the
+ * first bfhipComm* calls of a process may come from several threads at once. */
 typedef struct BfhipComm BfhipComm;
 typedef struct BfhipSharded BfhipSharded;
 enum { BFHIP_SHARD_ROWS = 0, BFHIP_SHARD_BLOCKS = 1 };

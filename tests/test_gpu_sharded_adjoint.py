@@ -8,7 +8,10 @@ bfhipShardedApplyTransposeDevice / CovMatvecDevice / SolveGMRESDevice, bfhipShar
 
 Reference anchors: src/mat_product.c:312-345, src/mat_block_dense.c:696-758 (Rmul mirrors), examples/covariance/
 lbo_cov.c:48-60 (cov_matvec), src/linalg.c:47-317 (bfSolveGMRES).  The 2- and 3-rank torch rendition of the same
-steps runs on CPU over gloo (tests/test_dist_cpu.py)."""
+steps runs on CPU over gloo (tests/test_dist_cpu.py); the C path itself with 2, 3 and 5 ranks -- slot arithmetic, the
+segment kernels, group sums, the adjoint gather, the abort path, GMRES agreement across ranks -- runs on one GPU over an
+in-process stand-in for the collectives (tests/test_gpu_shard_ranks.py).  What no test covers: RCCL's own transport over
+xGMI, and any scaling figure."""
 import ctypes as C
 import os
 
