@@ -486,6 +486,18 @@ def load():
     lib.bfhipCovSampleDevice.restype = C.c_int
     lib.bfhipCovMatvecDevice.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     lib.bfhipCovMatvecDevice.restype = C.c_int
+    lib.bfhipCovSampleBlockDevice.argtypes = [vp, vp, vp, vp, C.c_size_t, vp, vp]
+    lib.bfhipCovSampleBlockDevice.restype = C.c_int
+    lib.bfhipCovMatvecBlockDevice.argtypes = [vp, vp, vp, vp, vp, C.c_size_t, vp, vp]
+    lib.bfhipCovMatvecBlockDevice.restype = C.c_int
+    lib.bfhipNormalValue.argtypes = [C.c_uint64, C.c_uint64]
+    lib.bfhipNormalValue.restype = C.c_double
+    lib.bfhipFillNormalDevice.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, vp]
+    lib.bfhipFillNormalDevice.restype = C.c_int
+    lib.bfhipCovDrawDevice.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint64, C.c_size_t, vp, vp]
+    lib.bfhipCovDrawDevice.restype = C.c_int
+    lib.bfhipCovMomentsDevice.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, vp, vp, vp]
+    lib.bfhipCovMomentsDevice.restype = C.c_int
     lib.bfhipSetProfileSampling.argtypes = [vp, C.c_uint32]
     lib.bfhipSetProfileSampling.restype = C.c_int
     lib.bfhipPlanGetInfo.argtypes = [vp, C.POINTER(BfhipPlanInfo)]

@@ -836,11 +836,19 @@ int bfhipApplyTransposeDevice(BfhipOperator *op, void const *dX, size_t nrhs, vo
 }
 
 /* ---- covariance products (the caller of the real path) ------------------------ */
-static int covScratch(BfhipOperator *op) {
-  if (op->dCov) return 0;
-  /* two vectors of the longer side: [permuted input | A^T result] resp. [scaled input | A result] */
+int covScratch(BfhipOperator *op, size_t nrhs, void *stream) {
+  if (op->dCov && op->covRhs >= nrhs) return 0;
+  /* two blocks of the longer side: [permuted input | A^T result] resp. [scaled input | A result].  Growing is not
+   * stream-ordered (work enqueued earlier may still read the old blocks): drain first, as runPlan does for the vector arena */
   uint64_t const big = op->plan.numRows > op->plan.numCols ? op->plan.numRows : op->plan.numCols;
-  return bfdevMalloc(&op->dCov, 2 * big * op->plan.elemSize + 32);
+  int rc;
+  if (op->dCov) {
+    if ((rc = bfdevSync(stream))) return rc;
+    bfdevFree(op->dCov); op->dCov = NULL; op->covRhs = 0;
+  }
+  if ((rc = bfdevMalloc(&op->dCov, 2 * big * nrhs * op->plan.elemSize + 32))) return rc;
+  op->covRhs = (uint32_t)nrhs;
+  return 0;
 }
 
 int bfhipCovSampleDevice(BfhipOperator *op, void const *dGammaLam, uint64_t const *dRowPerm, void const *dW, void *dZ, void *stream) {
@@ -852,7 +860,7 @@ int bfhipCovSampleDevice(BfhipOperator *op, void const *dGammaLam, uint64_t cons
   if (prev != op->device && (rc = bfdevSetDevice(op->device))) return rc;
   uint64_t const m = op->plan.numRows, n = op->plan.numCols, big = m > n ? m : n;
   size_t const es = op->plan.elemSize;
-  if ((rc = covScratch(op))) goto out;
+  if ((rc = covScratch(op, 1, stream))) goto out;
   char *t0 = op->dCov, *t1 = (char *)op->dCov + big * es;
   void const *xin = dW;
   if (dGammaLam) { if ((rc = bfdevScalePermute(t0, dW, dGammaLam, 1, NULL, n, op->plan.dtype, stream))) goto out; xin = t0; }
@@ -873,7 +881,7 @@ int bfhipCovMatvecDevice(BfhipOperator *op, void const *dGammaLam, uint64_t cons
   if (prev != op->device && (rc = bfdevSetDevice(op->device))) return rc;
   uint64_t const m = op->plan.numRows, n = op->plan.numCols, big = m > n ? m : n;
   size_t const es = op->plan.elemSize;
-  if ((rc = covScratch(op))) goto out;
+  if ((rc = covScratch(op, 1, stream))) goto out;
   char *t0 = op->dCov, *t1 = (char *)op->dCov + big * es;
   void const *vin = dV;
   if (dRevRowPerm) { if ((rc = bfdevScalePermute(t0, dV, NULL, 0, dRevRowPerm, m, op->plan.dtype, stream))) goto out; vin = t0; }
@@ -885,6 +893,9 @@ out:
   if (prev >= 0 && prev != op->device) bfdevSetDevice(prev);
   return rc;
 }
+
+/* (the batched entries -- block products, device normals, draw, streaming moments -- are in bfhip_cov.c) */
+double bfhipNormalValue(uint64_t seed, uint64_t idx) { return bfhip_normal_value(seed, idx); }
 
 /* The host-vector apply behind bfhipApply and every slot of the vtable shim (the path an unmodified reference caller takes:
  * bfSolveGMRES calls bfMatMul once per iteration, src/linalg.c:125,155).  What each of X and Y is decides what it costs:

@@ -454,6 +454,16 @@ typedef struct BfReduceArgs {
 int bfdevLaunchReduce(BfReduceArgs const *a, uint32_t count, void *stream);
 int bfdevScalePermute(void *dst, void const *src, void const *scale, int power, uint64_t const *perm, uint64_t n, uint32_t dtype, void *stream);
 
+/* the batched covariance entries' plumbing (bfhip_cov.hip): blocks are row-major rows x nrhs, densely packed, F64 / F32 */
+/* dst[perm ? perm[i] : i, :] = src[i, :] * (scale ? scale[i]^power : 1); src == dst is legal when perm == NULL */
+int bfdevCovScalePermute(void *dst, void const *src, void const *scale, int power, uint64_t const *perm, uint64_t rows, uint32_t nrhs, uint32_t dtype, void *stream);
+/* d[i] = N(seed, firstIdx + i) (bfhip_normal_value) */
+int bfdevFillNormal(void *d, uint64_t count, uint64_t firstIdx, uint32_t dtype, uint64_t seed, void *stream);
+/* w[j, s] = N(seed, (firstSample + s) * cols + j) * (gamma ? gamma[j] : 1), w is cols x nrhs */
+int bfdevCovDrawFill(void *w, void const *gamma, uint64_t cols, uint32_t nrhs, uint32_t dtype, uint64_t seed, uint64_t firstSample, void *stream);
+/* sum[perm ? perm[i] : i] += sum_q t[i, q], sumSq[...] += sum_q t[i, q]^2 over the b columns of t (rows x b); either output may be NULL */
+int bfdevCovMoments(void const *t, uint64_t rows, uint32_t b, uint32_t dtype, uint64_t const *perm, double *sum, double *sumSq, void *stream);
+
 /* device-resident GMRES building blocks (bfhip_gmres.hip; complex128; bfhip_gmres.c drives them).
  * Vectors are n x nrhs row-major; reductions are per RHS column, two-stage and
  * in fixed order (per-block partials, then a tree over the partials), so a

@@ -1,6 +1,6 @@
 /* bfhip_operator.h -- struct BfhipOperator and the few helpers shared by the files that implement it: bfhip_api.c
- * (lifetime, compile, apply), bfhip_file.c (save / load), bfhip_shim.c (BfMat vtable) and bfhip_inspect.c (plan inspection).
- * Private to those four: every other file reads an operator through the bfhipOperator* accessors of bfhip_internal.h.
+ * (lifetime, compile, apply), bfhip_file.c (save / load), bfhip_shim.c (BfMat vtable), bfhip_inspect.c (plan inspection) and
+ * bfhip_cov.c (batched covariance sampling).  Private to those five: every other file reads an operator through the bfhipOperator* accessors of bfhip_internal.h.
  */
 #ifndef BFHIP_OPERATOR_H
 #define BFHIP_OPERATOR_H
@@ -33,7 +33,8 @@ struct BfhipOperator {
   uint32_t lastNrhs;
   uint64_t evIssued, evHarvested;   /* applies whose events were recorded / read back */
   uint64_t applyCount;              /* forward applies so far */
-  void *dCov;                       /* scratch of the covariance products (2 vectors of the longer side) */
+  void *dCov;                       /* scratch of the covariance products (2 blocks of the longer side x covRhs columns) */
+  uint32_t covRhs;                  /* columns dCov holds (0: none yet; the single-vector entries ask for 1, the block entries grow it) */
   uint32_t profEvery;               /* events around one apply in profEvery (0, 1: every apply) */
   /* BFHIP_FLAG_PLAN_ONLY: the IR is kept (borrowed leaf pointers!) for bfhipPlanPackArena; irT: its transposed view when the
    * adjoint plan has an arena of its own (BFHIP_FLAG_ADJOINT_PACKED), for bfhipPlanPackArenaT */
@@ -63,6 +64,8 @@ struct BfhipOperator {
 BF_HIDDEN int packLeavesPlan(BfPlan const *pl, void *dArena, BfIr const *ir, uint64_t seed, void *hostDst);
 BF_HIDDEN int finishOperator(BfhipOperator *op, uint32_t maxRhs);
 BF_HIDDEN void stageLaunchArgs(BfhipOperator const *op, BfPlan const *plan, BfStage const *st, uint32_t nrhs, BfLaunchArgs *a);
+/* the covariance entries' scratch holds at least `nrhs` columns after this (bfhip_api.c; the batched entries of bfhip_cov.c share it) */
+BF_HIDDEN int covScratch(BfhipOperator *op, size_t nrhs, void *stream);
 BF_HIDDEN int applyHost(BfhipOperator *op, int transpose, void const *X, size_t ldx, size_t nrhs, void *Y, size_t ldy);
 
 #endif

@@ -537,6 +537,80 @@ class HipOperator:
                                              C.c_void_p(v.data_ptr()), C.c_void_p(z.data_ptr()), C.c_void_p(s.cuda_stream)))
         return z
 
+    # ---- batched covariance sampling (bfhip_cov.c): blocks are [rows, nrhs] tensors, row-major ----------------
+    @staticmethod
+    def _ptr(t):
+        return C.c_void_p(t.data_ptr()) if t is not None else None
+
+    @staticmethod
+    def _cov_device(*tensors):
+        # where a call without an input tensor works: with its device arguments, else on the current device
+        import torch
+        for t in tensors:
+            if t is not None:
+                return t.device
+        return torch.device("cuda", torch.cuda.current_device())
+
+    def cov_sample_block_device(self, gamma_lam, row_perm, W):
+        """Z = P A diag(gamma_lam) W for a block W [numCols, nrhs] (bfhipCovSampleBlockDevice): column q is what
+        cov_sample_device makes of W[:, q]."""
+        import torch
+        if W.dim() != 2 or not W.is_contiguous():
+            raise ValueError("W must be a contiguous [numCols, nrhs] tensor")
+        z = torch.empty((self.shape[0], W.shape[1]), dtype=W.dtype, device=W.device)
+        s = torch.cuda.current_stream(W.device)
+        check(self._lib.bfhipCovSampleBlockDevice(self._h, self._ptr(gamma_lam), self._ptr(row_perm), self._ptr(W), W.shape[1],
+                                                  self._ptr(z), C.c_void_p(s.cuda_stream)))
+        return z
+
+    def cov_matvec_block_device(self, gamma_lam, row_perm, rev_row_perm, V):
+        """Z = P A diag(gamma_lam)^2 A^T P' V for a block V [numRows, nrhs] (bfhipCovMatvecBlockDevice)."""
+        import torch
+        if V.dim() != 2 or not V.is_contiguous():
+            raise ValueError("V must be a contiguous [numRows, nrhs] tensor")
+        z = torch.empty_like(V)
+        s = torch.cuda.current_stream(V.device)
+        check(self._lib.bfhipCovMatvecBlockDevice(self._h, self._ptr(gamma_lam), self._ptr(row_perm), self._ptr(rev_row_perm),
+                                                  self._ptr(V), V.shape[1], self._ptr(z), C.c_void_p(s.cuda_stream)))
+        return z
+
+    def cov_draw_device(self, gamma_lam, row_perm, seed, first, nrhs):
+        """Z [numRows, nrhs]: samples first .. first + nrhs - 1 of the field, from normals generated on the device
+        (bfhipCovDrawDevice): w_s[j] = N(seed, (first + s) * numCols + j), whatever the split into calls."""
+        import torch
+        dev = self._cov_device(gamma_lam, row_perm)
+        z = torch.empty((self.shape[0], int(nrhs)), dtype=self._torch_dtype(), device=dev)
+        s = torch.cuda.current_stream(dev)
+        check(self._lib.bfhipCovDrawDevice(self._h, self._ptr(gamma_lam), self._ptr(row_perm), int(seed), int(first), int(nrhs),
+                                           self._ptr(z), C.c_void_p(s.cuda_stream)))
+        return z
+
+    def cov_moments_device(self, gamma_lam, row_perm, seed, first, num, batch=64, sum=None, sumsq=None):
+        """Adds the sum and the sum of squares over samples first .. first + num - 1, per point, to the float64 [numRows]
+        tensors `sum` / `sumsq` (bfhipCovMomentsDevice; zero them before the first call; None: that moment is not
+        formed, one of the two is needed).  The samples are never stored.  Returns (sum, sumsq)."""
+        import torch
+        for t in (sum, sumsq):
+            if t is not None and (t.dtype != torch.float64 or t.numel() != self.shape[0] or not t.is_contiguous()):
+                raise ValueError("moments are contiguous float64 [numRows] tensors")
+        dev = self._cov_device(sum, sumsq, gamma_lam, row_perm)
+        s = torch.cuda.current_stream(dev)
+        check(self._lib.bfhipCovMomentsDevice(self._h, self._ptr(gamma_lam), self._ptr(row_perm), int(seed), int(first), int(num),
+                                              int(batch), self._ptr(sum), self._ptr(sumsq), C.c_void_p(s.cuda_stream)))
+        return sum, sumsq
+
+    def fill_normal(self, tensor, seed, first_idx=0):
+        """tensor.flat[i] = N(seed, first_idx + i) (bfhipFillNormalDevice); a contiguous float64 / float32 tensor on the
+        device.  Returns it."""
+        import torch
+        if not tensor.is_contiguous():
+            raise ValueError("fill_normal takes a contiguous tensor")
+        dt = {torch.float64: BFHIP_F64, torch.float32: BFHIP_F32}.get(tensor.dtype, 0xffffffff)
+        s = torch.cuda.current_stream(tensor.device)
+        with torch.cuda.device(tensor.device):
+            check(self._lib.bfhipFillNormalDevice(self._ptr(tensor), tensor.numel(), int(first_idx), dt, int(seed), C.c_void_p(s.cuda_stream)))
+        return tensor
+
     def set_profile_sampling(self, every):
         """Bracket one apply in `every` with events (bfhipSetProfileSampling)."""
         check(self._lib.bfhipSetProfileSampling(self._h, int(every)))

@@ -579,6 +579,52 @@ int bfhipCovSampleDevice(BfhipOperator *op, const void *dGammaLam, const uint64_
 int bfhipCovMatvecDevice(BfhipOperator *op, const void *dGammaLam, const uint64_t *dRowPerm, const uint64_t *dRevRowPerm,
                          const void *dV, void *dZ, void *stream);
 
+/* ---- batched covariance sampling ------------------------------------------------ */
+/* lbo_cov.c:219-225 draws numSamples samples one after another, each from a fresh bfVecRealNewRandn, then evaluates covariance
+ * columns with cov_matvec.  These entries are that loop in blocks, resident on the device.  All vectors are row-major
+ * rows x nrhs, densely packed (the layout of bfhipApplyDevice); P and P' scatter whole rows: out[perm[i], :] = in[i, :].
+ *
+ * Block products: column q of the result is what the single-vector entry computes for column q of the input -- the same
+ * sequence with nrhs right-hand sides through every step (sample: scale, A, scatter; matvec: scatter, A^T, scale twice, A,
+ * scatter).  Which stage kernels run is decided by the operator's switches (bfhipSetRealRhsBlocks, bfhipSetAdjointRhsBlocks)
+ * and nothing else: off (the default), a column equals the single-vector result to rounding (bit for bit at nrhs = 1); on,
+ * the leaves are read once per pass of 64 columns.  dW [numCols x nrhs], dV and dZ [numRows x nrhs]; 1 <= nrhs <= 65535.
+ * The scratch (2 x the longer side x nrhs elements) grows on demand; growing is not stream-ordered and drains `stream`
+ * first (as growing the vector arena does).  A call that grows nothing only enqueues work and can be captured in a graph. */
+int bfhipCovSampleBlockDevice(BfhipOperator *op, const void *dGammaLam, const uint64_t *dRowPerm, const void *dW, size_t nrhs, void *dZ,
+                              void *stream);
+int bfhipCovMatvecBlockDevice(BfhipOperator *op, const void *dGammaLam, const uint64_t *dRowPerm, const uint64_t *dRevRowPerm,
+                              const void *dV, size_t nrhs, void *dZ, void *stream);
+
+/* Standard normals without a host: value `idx` of the normal stream for `seed` (= bfhip_normal_value, include/bfhip_synth.h:
+ * Box-Muller over two counters of the synthetic stream; one normal per index, independent of every other index).  The device
+ * evaluates the same formula in double and rounds once for F32; host and device agree to the accuracy of log / cos (within
+ * 8 ulp of double), not bit for bit.  bfhipFillNormalDevice: d[i] = N(seed, firstIdx + i), i < count, on the current device;
+ * dtype BFHIP_F64 or BFHIP_F32 (TYPE_ERROR otherwise). */
+double bfhipNormalValue(uint64_t seed, uint64_t idx);
+int bfhipFillNormalDevice(void *d, uint64_t count, uint64_t firstIdx, uint32_t dtype, uint64_t seed, void *stream);
+
+/* Draw: dZ[:, s] = P A GammaLam w_s for s < nrhs with w_s[j] = N(seed, (firstSample + s) * numCols + j), generated on the
+ * device (already scaled) in one kernel; the rest is bfhipCovSampleBlockDevice.  The normals of a sample depend on
+ * (seed, firstSample + s) alone: calls with (firstSample, nrhs) = (0, a) and (a, b) use bit for bit the W of one call (0, a + b).
+ *
+ * Moments: samples firstSample .. firstSample + numSamples - 1, `batch` at a time (0 -> 64, at most 64; the last batch may
+ * be shorter), WITHOUT storing them: per row i of each batch's un-permuted result T the sums over its columns of T[i, q] and
+ * of T[i, q]^2 are formed in double (F32 values widened exactly) and ADDED to dSum[perm[i]] / dSumSq[perm[i]] (double
+ * [numRows] each; either may be NULL, not both; the caller zeroes them before the first call): mean = sum / K and
+ * var = sumSq / K - mean^2 after K samples.  One thread owns each output row, the order of every sum is fixed, no atomics:
+ * results are identical from run to run.  dRowPerm must be a permutation (an index >= numRows is dropped; a repeated one
+ * would lose updates).
+ *
+ * Errors of the six entries, all raised before the device is touched: INVALID_ARGUMENTS (a NULL operator, input or output;
+ * nrhs == 0 or > 65535; batch > 64; numSamples == 0; both moment outputs NULL; matvec on an operator without
+ * BFHIP_FLAG_ADJOINT), TYPE_ERROR (a complex operator; a fill dtype that is not real), then RUNTIME_ERROR for a
+ * BFHIP_FLAG_PLAN_ONLY operator. */
+int bfhipCovDrawDevice(BfhipOperator *op, const void *dGammaLam, const uint64_t *dRowPerm, uint64_t seed, uint64_t firstSample,
+                       size_t nrhs, void *dZ, void *stream);
+int bfhipCovMomentsDevice(BfhipOperator *op, const void *dGammaLam, const uint64_t *dRowPerm, uint64_t seed, uint64_t firstSample,
+                          uint64_t numSamples, uint32_t batch, double *dSum, double *dSumSq, void *stream);
+
 /* ---- plan inspection (no device needed) ---------------------------------- */
 /* The flattened per-stage layout, as the kernels see it.  Valid only for an
  * operator compiled with BFHIP_FLAG_PLAN_ONLY (the host mirrors are dropped
