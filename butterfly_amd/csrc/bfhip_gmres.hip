@@ -287,15 +287,18 @@ __global__ __launch_bounds__(BF_GM_THREADS) void bfRefinePromoteKernel(float2 co
   dst[e] = make_double2((double)v.x, (double)v.y);
 }
 
-// per column q: nrm = sqrt(sum of the |R|^2 partials of bfGmresResidualKernel); scale[q] = nrm (as computed: the host reads it);
-// Rhat = R / nrm, or the unit vector 1/sqrt(n) where nrm is not positive (a zero column must not become 0/0)
-__global__ __launch_bounds__(BF_GM_THREADS) void bfRefineScaleKernel(double2 const *R, double2 const *partialIn, double2 *Rhat, double *scale,
-                                                                    uint64_t n, uint32_t nrhs, uint32_t nb) {
+// R and partialIn are bfGmresScaleKernel's: the residual column scaled by 2^-e (e = expIn[q]) and the per-block |R|^2 of the scaled
+// column, which neither underflow nor overflow.  Per column q: nrm = sqrt(sum of the partials); scale[q] = 2^e nrm, the norm of
+// the unscaled column (as computed: the host reads it); Rhat = R / nrm, or the unit vector 1/sqrt(n) where nrm is not positive
+// (a zero column must not become 0/0).  Where the unscaled squares would not have left the range, 2^e nrm and Rhat are what the
+// unscaled column gives, bit for bit: the power of two commutes with every rounding on the way.
+__global__ __launch_bounds__(BF_GM_THREADS) void bfRefineScaleKernel(double2 const *R, double2 const *partialIn, double const *expIn, double2 *Rhat,
+                                                                    double *scale, uint64_t n, uint32_t nrhs, uint32_t nb) {
   __shared__ double2 sh[BF_GM_THREADS];
   uint32_t const q = blockIdx.y;
   double2 const s = bfSumPartials(partialIn, q, nb, sh);
   double const nrm = sqrt(s.x);
-  if (blockIdx.x == 0 && threadIdx.x == 0) scale[q] = nrm;
+  if (blockIdx.x == 0 && threadIdx.x == 0) scale[q] = ldexp(nrm, (int)expIn[q]);
   bool const live = nrm > 0.0;
   double const unit = 1.0 / sqrt((double)n);
   uint64_t r0, r1;
@@ -375,9 +378,10 @@ int bfdevRefinePromote(void const *src64, void *dst128, uint64_t count, void *st
   hipLaunchKernelGGL(bfRefinePromoteKernel, bfRefineGrid(count), dim3(BF_GM_THREADS), 0, (hipStream_t)stream, (float2 const *)src64, (double2 *)dst128, count);
   return hipFail(hipGetLastError(), "refine promote launch");
 }
-int bfdevRefineScale(void const *R, void const *partialIn, void *Rhat, double *scale, uint64_t n, uint32_t nrhs, uint32_t nb, void *stream) {
+int bfdevRefineScale(void const *R, void const *partialIn, double const *expIn, void *Rhat, double *scale, uint64_t n, uint32_t nrhs, uint32_t nb,
+                     void *stream) {
   hipLaunchKernelGGL(bfRefineScaleKernel, dim3(nb, nrhs), dim3(BF_GM_THREADS), 0, (hipStream_t)stream, (double2 const *)R, (double2 const *)partialIn,
-                     (double2 *)Rhat, scale, n, nrhs, nb);
+                     expIn, (double2 *)Rhat, scale, n, nrhs, nb);
   return hipFail(hipGetLastError(), "refine scale launch");
 }
 int bfdevRefineUpdate(void const *Xin, void const *D, double const *scale, void *Xout, uint64_t n, uint32_t nrhs, void *stream) {

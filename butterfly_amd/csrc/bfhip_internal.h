@@ -491,9 +491,11 @@ int bfdevGmresUpdate(void const *X0, void const *V, void const *y, uint32_t j, v
  * count = complex elements.  Demote rounds each component to nearest. */
 int bfdevRefineDemote(void const *src128, void *dst64, uint64_t count, void *stream);
 int bfdevRefinePromote(void const *src64, void *dst128, uint64_t count, void *stream);
-/* per column q: s = sqrt(sum of the nb |R|^2 partials); s > 0: Rhat = R / s, scale[q] = s; s == 0: Rhat = 1/sqrt(n) (a unit
- * right-hand side), scale[q] = 0.  scale: nrhs doubles on the device */
-int bfdevRefineScale(void const *R, void const *partialIn, void *Rhat, double *scale, uint64_t n, uint32_t nrhs, uint32_t nb, void *stream);
+/* R, partialIn, expIn: the scaled column, its |R|^2 partials and its exponent e as bfdevGmresResidual leaves them (W, partialScaled,
+ * expOut).  Per column q: s = sqrt(sum of the nb partials); s > 0: Rhat = R / s, scale[q] = 2^e s (the norm of the unscaled column);
+ * s == 0: Rhat = 1/sqrt(n) (a unit right-hand side), scale[q] = 0.  scale: nrhs doubles on the device */
+int bfdevRefineScale(void const *R, void const *partialIn, double const *expIn, void *Rhat, double *scale, uint64_t n, uint32_t nrhs, uint32_t nb,
+                     void *stream);
 /* Xout = Xin + scale[q] * D per column (Xin NULL = zeros); a column with scale 0 is Xin exactly, whatever D holds */
 int bfdevRefineUpdate(void const *Xin, void const *D, double const *scale, void *Xout, uint64_t n, uint32_t nrhs, void *stream);
 int bfdevMemcpyD2HAsync(void *dst, void const *src, size_t bytes, void *stream);

@@ -4,8 +4,9 @@
  * solved by the GMRES of bfhip_gmres.c (bfGmresRun: CGS2 or MGS, optional left preconditioner) applying only the
  * complex64 operator `opLow`, from zero, to a loose relative tolerance; then x += d.  Per step:
  *
- *   1. r = b - A x (bfdevGmresResidual, which also yields the per-column |r|^2 partials);
- *   2. r^_p = r_p / ||r_p|| (bfdevRefineScale).  The inner solver measures convergence as max_p |s| / max_p ||r_p||:
+ *   1. r = b - A x (bfdevGmresResidual), each column scaled by 2^-e_p, e_p the binary exponent of its largest component, with
+ *      the per-column |r|^2 partials of the scaled column: no sum of squares underflows or overflows;
+ *   2. ||r_p|| = 2^e_p sqrt(sum), r^_p = (2^-e_p r_p) / sqrt(sum) (bfdevRefineScale).  The inner solver measures convergence as max_p |s| / max_p ||r_p||:
  *      without the scaling a column whose residual is already small would gain nothing from the inner solve.  A column
  *      whose residual is exactly zero gets the unit right-hand side 1/sqrt(n) and the scale 0;
  *   3. A_low d = r^ to innerTol, maxInner Krylov vectors;
@@ -15,7 +16,16 @@
  * complex64 preconditioner) is wrapped as demote V_j -> apply -> promote into W.  The inner workspace is allocated once
  * per call.  The solve stops at tol, after maxOuter steps, or when a step does not bring the residual below half the
  * previous one (stagnation: rc 0, the residual reported as it is).  dX receives the iterate of the smallest true
- * residual seen.  Every argument is checked before the "no device" test, so plan-only operators reach each refusal. */
+ * residual seen.
+ *
+ * Range of b.  Every norm is taken of a column scaled by a power of two, exactly as the plain solver takes them, so the
+ * solve is exactly equivariant under b -> 2^k b (x0 = NULL): x scales by 2^k bit for bit and the counts, the residual and
+ * the history do not change, as long as b, A x and x themselves stay normal finite complex128 numbers.  Columns of 2^-600
+ * next to columns of 2^+600 are tested; each column has its own exponent.  The inner solve
+ * sees r^ only, whose components are at most 1, so the complex64 operator's narrower exponent range does not limit b.  A
+ * NaN anywhere in b or x0 makes the residual NaN: the loop does not start, x0 (or zeros) comes back with rc 0.
+ *
+ * Every argument is checked before the "no device" test, so plan-only operators reach each refusal. */
 #include "bfhip_internal.h"
 #include "../../include/bfhip_abi.h"
 
@@ -95,8 +105,8 @@ typedef struct BfRefine {
   uint64_t n;
   size_t nrhs;
   uint32_t nb;
-  void *dR, *dRhat, *dPart;
-  double *dScale, *hScale, *bnorm;
+  void *dR, *dRhat, *dPart, *dPartScaled;
+  double *dExp, *dScale, *hScale, *bnorm;
 } BfRefine;
 
 /* max_p ||b_p - A x_p|| / ||b_p|| (a column with b_p = 0: ||A x_p||) with x = NULL meaning zeros; leaves r^ and the
@@ -104,8 +114,8 @@ typedef struct BfRefine {
 static int trueResidual(BfRefine *R, void const *dXc, double *res, void *stream) {
   int rc = 0;
   if (dXc) rc = bfhipApplyDevice(R->op, dXc, R->nrhs, R->dR, stream);
-  if (!rc) rc = bfdevGmresResidual(R->dB, dXc ? R->dR : NULL, R->dR, R->dPart, R->n, (uint32_t)R->nrhs, R->nb, NULL, NULL, stream);
-  if (!rc) rc = bfdevRefineScale(R->dR, R->dPart, R->dRhat, R->dScale, R->n, (uint32_t)R->nrhs, R->nb, stream);
+  if (!rc) rc = bfdevGmresResidual(R->dB, dXc ? R->dR : NULL, R->dR, R->dPart, R->n, (uint32_t)R->nrhs, R->nb, R->dExp, R->dPartScaled, stream);
+  if (!rc) rc = bfdevRefineScale(R->dR, R->dPartScaled, R->dExp, R->dRhat, R->dScale, R->n, (uint32_t)R->nrhs, R->nb, stream);
   if (!rc) rc = bfdevMemcpyD2HAsync(R->hScale, R->dScale, R->nrhs * sizeof(double), stream);
   if (!rc) rc = bfdevSync(stream);
   if (rc) return rc;
@@ -142,6 +152,8 @@ static int refineDevice(BfhipOperator *op, BfhipOperator *opLow, BfhipGmresRefin
   CHECK(bfdevMalloc(&R.dR, vecBytes));
   CHECK(bfdevMalloc(&R.dRhat, vecBytes));
   CHECK(bfdevMalloc(&R.dPart, (size_t)w.nb * nrhs * 16));
+  CHECK(bfdevMalloc(&R.dPartScaled, (size_t)w.nb * nrhs * 16));
+  CHECK(bfdevMalloc((void **)&R.dExp, nrhs * sizeof(double)));
   CHECK(bfdevMalloc((void **)&R.dScale, nrhs * sizeof(double)));
   CHECK(bfdevMalloc(&dD, vecBytes));
   CHECK(bfdevMalloc(&dXalt, vecBytes));
@@ -194,7 +206,7 @@ static int refineDevice(BfhipOperator *op, BfhipOperator *opLow, BfhipGmresRefin
 done:
   (void)bfdevSync(stream);
   bfGmresWorkRelease(&w);
-  bfdevFree(R.dR); bfdevFree(R.dRhat); bfdevFree(R.dPart); bfdevFree(R.dScale);
+  bfdevFree(R.dR); bfdevFree(R.dRhat); bfdevFree(R.dPart); bfdevFree(R.dPartScaled); bfdevFree(R.dExp); bfdevFree(R.dScale);
   bfdevFree(dD); bfdevFree(dXalt); bfdevFree(low.dIn); bfdevFree(low.dOut);
   free(R.hScale); free(R.bnorm);
   return rc;

@@ -456,12 +456,15 @@ int bfhipSolveGMRESOptsDevice(BfhipOperator *op, const BfhipGmresOptions *opt, c
  * maxOuter steps, or on stagnation: a step that does not bring that residual below 0.5 x the previous one.  Stagnation and
  * the step cap return 0 with the residual as it is, like bfhipSolveGMRES when it does not converge.  dX receives the iterate
  * of the smallest residual seen (x0 itself if no step improved on it).  A column whose residual is exactly zero keeps its
- * x_p bit for bit.  Outputs (each may be NULL): numOuter = refinement steps taken, numInner = inner iterations summed over
- * the steps, residual = the true relative residual of dX, history = maxOuter + 1 doubles: the residual of x0, then of each
- * step's iterate (entries past numOuter: NaN).  Types: `op` complex128 and `opLow` complex64 (TYPE_ERROR otherwise), both
- * n x n on one device; dB, dX0 (NULL = zeros) and dX complex128 row-major n x nrhs as for bfhipSolveGMRESDevice.  Every
- * argument is checked before the operator's device is (plan-only operators reach each refusal).  Device operators
- * compiled from a BfMat or a descriptor only: the Helmholtz builders make no complex64 operator. */
+ * x_p bit for bit.  Every norm is taken of the column scaled by a power of two: b may hold columns of any magnitude
+ * whose entries, A x and x are normal finite numbers (2^-600 next to 2^+600 is tested), and b -> 2^k b scales x by 2^k
+ * bit for bit.  A NaN in b or x0 gives residual = NaN, no step and rc 0.  Outputs (each may be NULL): numOuter =
+ * refinement steps taken, numInner = inner iterations summed over the steps, residual = the true relative residual of
+ * dX, history = maxOuter + 1 doubles: the residual of x0, then of each step's iterate (entries past numOuter: NaN).
+ * Types: `op` complex128 and `opLow` complex64 (TYPE_ERROR otherwise), both n x n on one device; dB, dX0 (NULL =
+ * zeros) and dX complex128 row-major n x nrhs as for bfhipSolveGMRESDevice.  Every argument is checked before the
+ * operator's device is (plan-only operators reach each refusal).  Device operators compiled from a BfMat or a
+ * descriptor only: the Helmholtz builders make no complex64 operator. */
 typedef struct BfhipGmresRefineOptions {
   uint32_t structSize;          /* = sizeof(BfhipGmresRefineOptions) */
   uint32_t orthogonalization;   /* inner GMRES: BFHIP_GMRES_ORTH_* (as BfhipGmresOptions) */
