@@ -121,7 +121,7 @@ class BfhipHelm2Problem(C.Structure):
                 ("points", C.c_void_p), ("numPoints", C.c_uint64), ("recipes", C.c_void_p),
                 ("numRecipes", C.c_uint64), ("workspaceBytes", C.c_uint64),
                 ("normals", C.c_void_p), ("colWeights", C.c_void_p), ("selfValue", C.c_double * 2),
-                ("origIndex", C.c_void_p), ("krOrder", C.c_uint32), ("reserved", C.c_uint32),
+                ("origIndex", C.c_void_p), ("krOrder", C.c_uint32), ("outDtype", C.c_uint32),
                 ("alpha", C.c_double * 2), ("beta", C.c_double * 2),
                 ("tgtPoints", C.c_void_p), ("numTgtPoints", C.c_uint64), ("tgtNormals", C.c_void_p)]
 
@@ -191,7 +191,8 @@ class Helm2Problem:
     """Keeps the arrays a BfhipHelm2Problem points to alive."""
 
     def __init__(self, points, wavenumber, recipes=None, workspace_bytes=0, layer_pot="S", normals=None,
-                 col_weights=None, self_value=0.0, kr_order=0, orig_index=None, alpha=0.0, beta=0.0, tgt_points=None, tgt_normals=None):
+                 col_weights=None, self_value=0.0, kr_order=0, orig_index=None, alpha=0.0, beta=0.0, tgt_points=None, tgt_normals=None,
+                 out_dtype=None):
         self.points = np.ascontiguousarray(points, dtype=np.float64)
         assert self.points.ndim == 2 and self.points.shape[1] == 2
         if recipes is None:
@@ -219,6 +220,7 @@ class Helm2Problem:
         assert self.orig_index is None or self.orig_index.shape == (len(self.points),)
         s.origIndex = None if self.orig_index is None else self.orig_index.ctypes.data
         s.krOrder = int(kr_order)
+        s.outDtype = BFHIP_C128 if out_dtype is None else int(out_dtype)      # BFHIP_C64: a complex64 operator (builder entries only)
         al, be = complex(alpha), complex(beta)
         s.alpha[0], s.alpha[1], s.beta[0], s.beta[1] = al.real, al.imag, be.real, be.imag
         self.tgt_points = None if tgt_points is None else np.ascontiguousarray(tgt_points, dtype=np.float64)
@@ -566,6 +568,9 @@ def load():
     lib.bfhipBuildHelm2.argtypes = [C.POINTER(BfhipDesc), C.POINTER(BfhipHelm2Problem), C.POINTER(BfhipOptions), C.POINTER(vp),
                                     C.POINTER(BfhipBuildStats)]
     lib.bfhipBuildHelm2.restype = C.c_int
+    lib.bfhipBuildHelm2Pair.argtypes = [C.POINTER(BfhipDesc), C.POINTER(BfhipHelm2Problem), C.POINTER(BfhipOptions), C.POINTER(BfhipOptions),
+                                        C.POINTER(vp), C.POINTER(vp), C.POINTER(BfhipBuildStats)]
+    lib.bfhipBuildHelm2Pair.restype = C.c_int
     lib.bfhipHelm2BuildLeaf.argtypes = [C.POINTER(BfhipHelm2Problem), C.c_uint64, C.c_int, vp]
     lib.bfhipHelm2BuildLeaf.restype = C.c_int
     lib.bfhipLstSqTruncated.argtypes = [C.c_uint64, vp, vp, vp, vp, vp, C.POINTER(BfhipLstSqInfo), C.POINTER(BfhipLstSqOptions), C.c_int]

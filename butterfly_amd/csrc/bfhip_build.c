@@ -53,6 +53,8 @@ static uint32_t leafRows(BfhipHelm2Recipe const *r) { return r->kind == BFHIP_LE
 static int checkProblem(BfhipHelm2Problem const *prob) {
   if (!prob) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL problem");
   if (prob->structSize < sizeof(BfhipHelm2Problem)) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "BfhipHelm2Problem.structSize too small");
+  if (prob->outDtype != BFHIP_C128 && prob->outDtype != BFHIP_C64)
+    return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "outDtype must be 0 (BFHIP_C128) or BFHIP_C64, got %u", prob->outDtype);
   if (prob->layerPot != BFHIP_LAYER_POTENTIAL_SINGLE && prob->layerPot != BFHIP_LAYER_POTENTIAL_PV_NORMAL_DERIV_SINGLE &&
       prob->layerPot != BFHIP_LAYER_POTENTIAL_PV_DOUBLE && prob->layerPot != BFHIP_LAYER_POTENTIAL_COMBINED_FIELD)
     return bfhipFail(BFABI_ERROR_NOT_IMPLEMENTED, "layer potential %u is not built on the device (S = 1, D = 2, S' = 3, combined = 5 are)",
@@ -363,29 +365,40 @@ static void batchSizes(BfhipHelm2Problem const *prob, uint64_t const *idx, uint6
 }
 
 /* ---- arena fill: called by the compile step instead of packing host values ---- */
+typedef struct PieceRec { uint64_t rec, dataOff; uint32_t row0, col0, mr, mrPad, ncols, rowMajor, ld; } PieceRec;
+
+/* One arena the batches are packed into: a plan's pieces grouped by recipe (sorted[pieceBegin[i] .. pieceBegin[i + 1]) are
+ * recipe i's), of either storage type.  bfhipBuildHelm2 has one, bfhipBuildHelm2Pair two filled from the same batches. */
+typedef struct PackTarget {
+  void *dArena;
+  uint32_t dtype;            /* BFHIP_C128 or BFHIP_C64 */
+  int whole;                 /* the plan is the whole square operator (the KR correction can be checked on it) */
+  PieceRec *sorted;
+  uint64_t *pieceBegin;      /* [numRecipes + 2] */
+} PackTarget;
+
+#define MAX_TARGETS 2
 typedef struct BuildCtx {
   BfhipHelm2Problem const *prob;
   BfhipBuildStats *stats;
+  PackTarget tgt[MAX_TARGETS];
+  uint32_t numTargets, wanted;       /* collected so far; the values are built once `wanted` arenas are known */
 } BuildCtx;
 
-typedef struct PieceRec { uint64_t rec, dataOff; uint32_t row0, col0, mr, mrPad, ncols; } PieceRec;
+static void buildCtxFree(BuildCtx *ctx) {
+  for (uint32_t t = 0; t < MAX_TARGETS; ++t) { free(ctx->tgt[t].sorted); free(ctx->tgt[t].pieceBegin); }
+  memset(ctx->tgt, 0, sizeof ctx->tgt);
+  ctx->numTargets = 0;
+}
 
-static int fillArena(BfPlan const *pl, BfIr const *ir, void *dArena, void *vctx) {
-  BuildCtx *ctx = vctx;
-  BfhipHelm2Problem const *prob = ctx->prob;
-  BfhipBuildStats *st = ctx->stats;
+/* the plan's non-identity pieces, grouped by recipe; every recipe and its leaf checked on the way */
+static int collectTarget(BfPlan const *pl, BfIr const *ir, void *dArena, BfhipHelm2Problem const *prob, PackTarget *T) {
   int rc = 0;
-  if (pl->dtype != BFHIP_C128) return bfhipFail(BFABI_ERROR_TYPE_ERROR, "the Helmholtz builder fills complex128 operands");
+  if (pl->dtype != BFHIP_C128 && pl->dtype != BFHIP_C64) return bfhipFail(BFABI_ERROR_TYPE_ERROR, "the Helmholtz builder fills complex128 or complex64 operands");
   uint64_t const R = prob->numRecipes;
   int64_t *recOf = malloc((ir->numNodes + 1) * sizeof *recOf);
   uint64_t *pieceBegin = calloc(R + 2, sizeof *pieceBegin);
   PieceRec *pieces = NULL, *sorted = NULL;
-  uint64_t *batch = NULL, *storeOff = NULL;
-  BfPackPiece *pack = NULL;
-  DevEnv dev;
-  memset(&dev, 0, sizeof dev);
-  BatchBufs bufs;
-  memset(&bufs, 0, sizeof bufs);
   if (!recOf || !pieceBegin) { rc = bfhipFail(BFABI_ERROR_MEMORY_ERROR, "host OOM (builder)"); goto done; }
   for (uint64_t i = 0; i < ir->numNodes; ++i) recOf[i] = -1;
   for (uint64_t i = 0; i < R && !rc; ++i) {
@@ -426,6 +439,7 @@ static int fillArena(BfPlan const *pl, BfIr const *ir, void *dArena, void *vctx)
         PieceRec *p = &pieces[np++];
         p->rec = (uint64_t)rec; p->dataOff = pc->dataOff; p->row0 = src->row0; p->col0 = src->col0;
         p->mr = mr; p->mrPad = mrPad; p->ncols = pc->ncols;
+        p->rowMajor = (pc->flags & BF_PIECE_ROWMAJOR) != 0; p->ld = pc->ld;
         pieceBegin[rec + 1] += 1;
       }
     }
@@ -439,6 +453,34 @@ static int fillArena(BfPlan const *pl, BfIr const *ir, void *dArena, void *vctx)
     for (uint64_t i = 0; i < np; ++i) sorted[cursor[pieces[i].rec]++] = pieces[i];
     free(cursor);
   }
+  T->dArena = dArena; T->dtype = pl->dtype;
+  T->whole = !prob->tgtPoints && pl->numRows == prob->numPoints && pl->numCols == prob->numPoints;
+  T->sorted = sorted; T->pieceBegin = pieceBegin;
+  sorted = NULL; pieceBegin = NULL;
+done:
+  free(recOf); free(pieceBegin); free(pieces); free(sorted);
+  return rc;
+}
+
+/* does recipe i's leaf survive in any of the plans */
+static int recipeKept(BuildCtx const *ctx, uint64_t i) {
+  for (uint32_t t = 0; t < ctx->numTargets; ++t)
+    if (ctx->tgt[t].pieceBegin[i + 1] != ctx->tgt[t].pieceBegin[i]) return 1;
+  return 0;
+}
+
+/* every kept recipe computed once, batch by batch, and each batch packed into every arena its leaves survive in */
+static int buildAndPack(BuildCtx *ctx) {
+  BfhipHelm2Problem const *prob = ctx->prob;
+  BfhipBuildStats *st = ctx->stats;
+  uint64_t const R = prob->numRecipes;
+  int rc = 0;
+  uint64_t *batch = NULL, *storeOff = NULL;
+  BfPackPiece *pack = NULL;
+  DevEnv dev;
+  memset(&dev, 0, sizeof dev);
+  BatchBufs bufs;
+  memset(&bufs, 0, sizeof bufs);
 
   char const *penv = getenv("BFHIP_JACOBI_PROFILE");
   int const profile = penv && penv[0] == '1';
@@ -463,7 +505,7 @@ static int fillArena(BfPlan const *pl, BfIr const *ir, void *dArena, void *vctx)
     for (uint64_t j = 0; j < R;) {
       uint64_t nb = 0, cost = 0;
       for (; j < R; ++j) {
-        if (pieceBegin[j + 1] == pieceBegin[j]) continue;
+        if (!recipeKept(ctx, j)) continue;
         uint64_t const c = recipeCost(&prob->recipes[j]);
         if (nb && cost + c > budget) break;
         batch[nb++] = j; cost += c;
@@ -477,40 +519,47 @@ static int fillArena(BfPlan const *pl, BfIr const *ir, void *dArena, void *vctx)
   }
   uint64_t i = 0;
   while (i < R && !rc) {
-    /* next batch: recipes whose leaves survive in this plan, until the workspace is full */
-    uint64_t nb = 0, cost = 0, packCount = 0;
+    /* next batch: recipes whose leaves survive in one of the plans, until the workspace is full */
+    uint64_t nb = 0, cost = 0;
     for (; i < R; ++i) {
-      if (pieceBegin[i + 1] == pieceBegin[i]) continue;          /* sharded away */
+      if (!recipeKept(ctx, i)) continue;                         /* sharded away */
       uint64_t const c = recipeCost(&prob->recipes[i]);
       if (nb && cost + c > budget) break;
-      batch[nb++] = i; cost += c; packCount += pieceBegin[i + 1] - pieceBegin[i];
+      batch[nb++] = i; cost += c;
     }
     if (!nb) break;
     void *dStore = NULL;
     if (profile) { double const t = nowSeconds(); fprintf(stderr, "[build] host before batch %.3f s\n", t - tph); tph = t; }
     if ((rc = buildBatch(prob, batch, nb, &dev.env, &bufs, &dStore, storeOff, st))) break;
     if (profile) { double const t = nowSeconds(); fprintf(stderr, "[build] batch total %.3f s (%llu recipes)\n", t - tph, (unsigned long long)nb); tph = t; }
-    pack = malloc((packCount + 1) * sizeof *pack);
-    if (!pack) rc = bfhipFail(BFABI_ERROR_MEMORY_ERROR, "host OOM (builder pack list)");
-    uint64_t q = 0;
-    for (uint64_t b = 0; b < nb && !rc; ++b) {
-      uint64_t const rec = batch[b];
-      uint32_t const ld = leafRows(&prob->recipes[rec]);
-      for (uint64_t k = pieceBegin[rec]; k < pieceBegin[rec + 1]; ++k) {
-        PieceRec const *p = &sorted[k];
-        pack[q].dataOff = p->dataOff;
-        pack[q].srcOff = storeOff[b] + (uint64_t)p->col0 * ld + p->row0;
-        pack[q].srcLd = ld; pack[q].mr = p->mr; pack[q].mrPad = p->mrPad; pack[q].ncols = p->ncols;
-        ++q;
+    for (uint32_t t = 0; t < ctx->numTargets && !rc; ++t) {
+      PackTarget const *T = &ctx->tgt[t];
+      uint64_t packCount = 0, q = 0;
+      for (uint64_t b = 0; b < nb; ++b) packCount += T->pieceBegin[batch[b] + 1] - T->pieceBegin[batch[b]];
+      pack = malloc((packCount + 1) * sizeof *pack);
+      if (!pack) { rc = bfhipFail(BFABI_ERROR_MEMORY_ERROR, "host OOM (builder pack list)"); break; }
+      for (uint64_t b = 0; b < nb; ++b) {
+        uint64_t const rec = batch[b];
+        uint32_t const ld = leafRows(&prob->recipes[rec]);
+        for (uint64_t k = T->pieceBegin[rec]; k < T->pieceBegin[rec + 1]; ++k) {
+          PieceRec const *p = &T->sorted[k];
+          pack[q].dataOff = p->dataOff;
+          pack[q].srcOff = storeOff[b] + (uint64_t)p->col0 * ld + p->row0;
+          pack[q].srcLd = ld; pack[q].mr = p->mr; pack[q].mrPad = p->mrPad; pack[q].ncols = p->ncols;
+          pack[q].rowMajor = p->rowMajor; pack[q].ld = p->ld;
+          ++q;
+        }
       }
+      rc = bfdevBuildPack(T->dArena, T->dtype, dStore, pack, q);
+      free(pack); pack = NULL;
     }
-    if (!rc) rc = bfdevBuildPack(dArena, dStore, pack, q);
-    free(pack); pack = NULL;
     if (profile) { double const t = nowSeconds(); fprintf(stderr, "[build] pack + free  %.3f s\n", t - tph); tph = t; }
   }
   /* every KR pair must have been met exactly once by a dense near-field leaf; a pair inside a
    * butterflied block cannot be corrected through the values */
-  if (!rc && prob->krOrder && !prob->tgtPoints && pl->numRows == prob->numPoints && pl->numCols == prob->numPoints) {
+  int whole = 0;
+  for (uint32_t t = 0; t < ctx->numTargets; ++t) whole |= ctx->tgt[t].whole;
+  if (!rc && prob->krOrder && whole) {
     unsigned long long hits = 0;
     rc = bfdevMemcpyD2H(&hits, dev.dHits, 8);
     if (!rc && hits != 2ull * prob->krOrder * prob->numPoints)
@@ -520,7 +569,53 @@ static int fillArena(BfPlan const *pl, BfIr const *ir, void *dArena, void *vctx)
 done:
   batchBufsFree(&bufs);
   envFree(&dev);
-  free(recOf); free(pieceBegin); free(pieces); free(sorted); free(batch); free(storeOff);
+  free(batch); free(storeOff);
+  return rc;
+}
+
+/* The compile step's fill callback.  The host mirrors of a plan's pieces are gone once its compile returns, so each compile
+ * collects its pieces here; the values are built when the last arena is known (the pair's first compile returns with its arena
+ * still to be written, during the second compile's callback). */
+static int fillArena(BfPlan const *pl, BfIr const *ir, void *dArena, void *vctx) {
+  BuildCtx *ctx = vctx;
+  if (ctx->numTargets >= ctx->wanted || ctx->wanted > MAX_TARGETS) return bfhipFail(BFABI_ERROR_RUNTIME_ERROR, "builder: more arenas than asked for");
+  int const rc = collectTarget(pl, ir, dArena, ctx->prob, &ctx->tgt[ctx->numTargets]);
+  if (rc) return rc;
+  ctx->numTargets += 1;
+  return ctx->numTargets < ctx->wanted ? 0 : buildAndPack(ctx);
+}
+
+/* `opts` as the compile step reads them (fields a shorter struct lacks are 0), with the complex64 store asked for */
+static int c64Options(BfhipOptions const *opts, BfhipOptions *o) {
+  memset(o, 0, sizeof *o);
+  o->device = -1;
+  if (opts) {
+    if (opts->structSize < BFHIP_OPTIONS_SIZE_V1) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "BfhipOptions.structSize too small");
+    memcpy(o, opts, opts->structSize < sizeof *o ? opts->structSize : sizeof *o);
+  }
+  o->structSize = sizeof *o;
+  o->demoteToF32 = 1;
+  return 0;
+}
+
+static int checkBuildOptions(BfhipOptions const *opts) {
+  /* BfhipOptions.demoteToF32 stays refused on the builder entries: complex64 output is asked for through
+   * BfhipHelm2Problem.outDtype (bfhipBuildHelm2) or bfhipBuildHelm2Pair */
+  if (opts && opts->demoteToF32)
+    return bfhipFail(BFABI_ERROR_NOT_IMPLEMENTED, "the Helmholtz builder takes no demoteToF32: complex64 output is BfhipHelm2Problem.outDtype = BFHIP_C64");
+  if (opts && (opts->flags & BFHIP_FLAG_PLAN_ONLY)) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "BFHIP_FLAG_PLAN_ONLY has no device to build on");
+  return 0;
+}
+
+/* what both entries end with: the statistics handed out (also on failure: the counts say why), and an operator whose
+ * least-squares leaves came from an SVD that hit the sweep cap refused -- it is silently wrong
+ * (BFHIP_ALLOW_UNCONVERGED_SVD=1 in the environment keeps it, for diagnosis) */
+static int finishBuild(int rc, BfhipBuildStats const *local, BfhipBuildStats *stats) {
+  if (stats && stats->structSize >= sizeof *local) *stats = *local;
+  if (!rc && stats && stats->structSize < sizeof *local) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "BfhipBuildStats.structSize too small");
+  if (!rc && local->notConverged && !getenv("BFHIP_ALLOW_UNCONVERGED_SVD"))
+    return bfhipFail(BFABI_ERROR_RUNTIME_ERROR, "%llu Jacobi SVD problem(s) did not converge within the sweep cap; operator discarded",
+                     (unsigned long long)local->notConverged);
   return rc;
 }
 
@@ -531,27 +626,60 @@ int bfhipBuildHelm2(BfhipDesc const *desc, BfhipHelm2Problem const *prob, BfhipO
   int rc = checkProblem(prob);
   if (rc) return rc;
   if (desc->dtype != BFHIP_C128) return bfhipFail(BFABI_ERROR_TYPE_ERROR, "the Helmholtz builder fills complex128 operands");
-  /* compile would accept the demotion, and fillArena writes complex128 values: refused before any device work */
-  if (opts && opts->demoteToF32) return bfhipFail(BFABI_ERROR_NOT_IMPLEMENTED, "the Helmholtz builder has no complex64 output (demoteToF32)");
-  if (opts && (opts->flags & BFHIP_FLAG_PLAN_ONLY)) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "BFHIP_FLAG_PLAN_ONLY has no device to build on");
+  if ((rc = checkBuildOptions(opts))) return rc;
+  /* complex64 output: the plan bfhipCompileDesc makes of this descriptor under demoteToF32 */
+  BfhipOptions low;
+  if (prob->outDtype == BFHIP_C64) {
+    if ((rc = c64Options(opts, &low))) return rc;
+    opts = &low;
+  }
   BfhipBuildStats local;
   memset(&local, 0, sizeof local);
   local.structSize = sizeof local;
-  BuildCtx ctx = {prob, &local};
+  BuildCtx ctx;
+  memset(&ctx, 0, sizeof ctx);
+  ctx.prob = prob; ctx.stats = &local; ctx.wanted = 1;
   BfIr ir;
   if ((rc = bfIrFromDesc(desc, &ir))) return rc;
   double const t0 = nowSeconds();
   rc = bfhipCompileIrFill(&ir, opts, fillArena, &ctx, out);
+  buildCtxFree(&ctx);
   local.seconds = nowSeconds() - t0;
-  if (stats && stats->structSize >= sizeof local) *stats = local;     /* also on failure: the counts say why */
-  if (!rc && stats && stats->structSize < sizeof local) { bfhipFree(out); return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "BfhipBuildStats.structSize too small"); }
-  if (!rc && local.notConverged && !getenv("BFHIP_ALLOW_UNCONVERGED_SVD")) {
-    /* a least-squares leaf from an SVD that hit the sweep cap is a silently wrong operator: refuse
-     * it (BFHIP_ALLOW_UNCONVERGED_SVD=1 in the environment keeps the operator, for diagnosis) */
-    bfhipFree(out);
-    return bfhipFail(BFABI_ERROR_RUNTIME_ERROR, "%llu Jacobi SVD problem(s) did not converge within the sweep cap; operator discarded",
-                     (unsigned long long)local.notConverged);
-  }
+  int const rc2 = finishBuild(rc, &local, stats);
+  if (rc2 && !rc) bfhipFree(out);
+  return rc2;
+}
+
+int bfhipBuildHelm2Pair(BfhipDesc const *desc, BfhipHelm2Problem const *prob, BfhipOptions const *opts, BfhipOptions const *optsLow,
+                        BfhipOperator **out, BfhipOperator **outLow, BfhipBuildStats *stats) {
+  if (!desc || !out || !outLow) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL argument");
+  *out = NULL; *outLow = NULL;
+  int rc = checkProblem(prob);
+  if (rc) return rc;
+  if (prob->outDtype != BFHIP_C128)
+    return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "bfhipBuildHelm2Pair makes both operators: outDtype must be 0 (BFHIP_C128)");
+  if (desc->dtype != BFHIP_C128) return bfhipFail(BFABI_ERROR_TYPE_ERROR, "the Helmholtz builder fills complex128 operands");
+  if (!optsLow) optsLow = opts;
+  if ((rc = checkBuildOptions(opts)) || (rc = checkBuildOptions(optsLow))) return rc;
+  if ((opts ? opts->device : -1) != (optsLow ? optsLow->device : -1))
+    return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "bfhipBuildHelm2Pair: both operators live on one device");
+  BfhipOptions low;
+  if ((rc = c64Options(optsLow, &low))) return rc;
+  BfhipBuildStats local;
+  memset(&local, 0, sizeof local);
+  local.structSize = sizeof local;
+  BuildCtx ctx;
+  memset(&ctx, 0, sizeof ctx);
+  ctx.prob = prob; ctx.stats = &local; ctx.wanted = 2;
+  double const t0 = nowSeconds();
+  /* the first compile only collects its pieces (fillArena); its arena is written while the second one fills its own */
+  BfIr ir;
+  if (!(rc = bfIrFromDesc(desc, &ir))) rc = bfhipCompileIrFill(&ir, opts, fillArena, &ctx, out);
+  if (!rc && !(rc = bfIrFromDesc(desc, &ir))) rc = bfhipCompileIrFill(&ir, &low, fillArena, &ctx, outLow);
+  buildCtxFree(&ctx);
+  local.seconds = nowSeconds() - t0;
+  rc = finishBuild(rc, &local, stats);
+  if (rc) { bfhipFree(out); bfhipFree(outLow); }      /* neither is returned: the first one's arena may be unwritten */
   return rc;
 }
 

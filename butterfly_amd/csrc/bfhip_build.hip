@@ -1313,24 +1313,47 @@ int bfdevBuildGemm(BfGemmJob const *hostJobs, uint64_t numJobs) {
 // ---------------------------------------------------------------------------
 // leaf store (column-major leaves of one batch) -> packed arena pieces
 // ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void bfPackKernel(double2 *arena, double2 const *store, BfPackPiece const *pieces, uint64_t base) {
+// The arena element of a store value: complex128 copied, complex64 with each component rounded to nearest even once
+// (what packPiece does on the host for a complex64 plan, bfhip_api.c).
+template <typename T> __device__ __forceinline__ T bfPackCvt(double2 v);
+template <> __device__ __forceinline__ double2 bfPackCvt<double2>(double2 v) { return v; }
+template <> __device__ __forceinline__ float2 bfPackCvt<float2>(double2 v) { return make_float2((float)v.x, (float)v.y); }
+
+// One workgroup per piece.  Column-major pieces: lanes run along the padded rows, contiguous in the arena and (within a column)
+// in the store.  Row-major pieces (a few rows, real-family plans only): a lane owns a column of the padded row, reads that
+// column's mr consecutive store elements and writes one element per row, so for a fixed row consecutive lanes write
+// consecutive elements.  The padding (rows mr..mrPad, columns ncols..ld) is written: the stage kernels read it.
+template <typename T>
+__global__ __launch_bounds__(256) void bfPackKernel(T *arena, double2 const *store, BfPackPiece const *pieces, uint64_t base) {
   BfPackPiece const pc = pieces[base + blockIdx.x];
-  uint32_t const total = pc.mrPad * pc.ncols;
-  double2 *dst = arena + pc.dataOff;
+  T *dst = arena + pc.dataOff;
   double2 const *src = store + pc.srcOff;
+  double2 const zero = make_double2(0.0, 0.0);
+  if (pc.rowMajor) {
+    for (uint32_t c = threadIdx.x; c < pc.ld; c += 256) {
+      double2 const *col = src + (uint64_t)c * pc.srcLd;
+      for (uint32_t r = 0; r < pc.mr; ++r) dst[(uint64_t)r * pc.ld + c] = bfPackCvt<T>(c < pc.ncols ? col[r] : zero);
+    }
+    return;
+  }
+  uint32_t const total = pc.mrPad * pc.ncols;
   for (uint32_t e = threadIdx.x; e < total; e += 256) {
     uint32_t const r = e % pc.mrPad, c = e / pc.mrPad;
-    dst[e] = r < pc.mr ? src[(uint64_t)c * pc.srcLd + r] : make_double2(0.0, 0.0);
+    dst[e] = bfPackCvt<T>(r < pc.mr ? src[(uint64_t)c * pc.srcLd + r] : zero);
   }
 }
 
-int bfdevBuildPack(void *arena, void const *store, BfPackPiece const *hostPieces, uint64_t count) {
+int bfdevBuildPack(void *arena, uint32_t outDtype, void const *store, BfPackPiece const *hostPieces, uint64_t count) {
   if (!count) return 0;
+  if (outDtype != BFHIP_C128 && outDtype != BFHIP_C64) return bfhipFail(BFABI_ERROR_TYPE_ERROR, "the builder packs complex128 or complex64 arenas");
   BfPackPiece *d = NULL;
   int rc = uploadArrayB(&d, hostPieces, count, "pack pieces");
   for (uint64_t done = 0; done < count && !rc;) {
     uint32_t const n = (uint32_t)(count - done > (1u << 30) ? (1u << 30) : count - done);
-    hipLaunchKernelGGL(bfPackKernel, dim3(n), dim3(256), 0, 0, (double2 *)arena, (double2 const *)store, d, done);
+    if (outDtype == BFHIP_C64)
+      hipLaunchKernelGGL(bfPackKernel<float2>, dim3(n), dim3(256), 0, 0, (float2 *)arena, (double2 const *)store, d, done);
+    else
+      hipLaunchKernelGGL(bfPackKernel<double2>, dim3(n), dim3(256), 0, 0, (double2 *)arena, (double2 const *)store, d, done);
     rc = hipFailB(hipGetLastError(), "pack launch");
     done += n;
   }

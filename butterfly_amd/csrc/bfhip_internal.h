@@ -650,12 +650,15 @@ typedef struct BfGemmJob {
 } BfGemmJob;
 int bfdevBuildGemm(BfGemmJob const *hostJobs, uint64_t numJobs);
 
-/* arena[dataOff + c*mrPad + r] = r < mr ? store[srcOff + c*srcLd + r] : 0 */
+/* column-major: arena[dataOff + c*mrPad + r] = r < mr ? store[srcOff + c*srcLd + r] : 0,      r < mrPad, c < ncols
+ * row-major:    arena[dataOff + r*ld + c]    = c < ncols ? store[srcOff + c*srcLd + r] : 0,   r < mr,    c < ld
+ * The store is complex128; the arena holds outDtype (BFHIP_C128: copied; BFHIP_C64: each component rounded to float once). */
 typedef struct BfPackPiece {
   uint64_t dataOff, srcOff;
   uint32_t srcLd, mr, mrPad, ncols;
+  uint32_t rowMajor, ld;     /* BF_PIECE_ROWMAJOR pieces (real-family plans) and their row stride */
 } BfPackPiece;
-int bfdevBuildPack(void *arena, void const *store, BfPackPiece const *hostPieces, uint64_t count);
+int bfdevBuildPack(void *arena, uint32_t outDtype, void const *store, BfPackPiece const *hostPieces, uint64_t count);
 
 int bfdevMemFree(uint64_t *freeBytes);    /* free device memory right now */
 

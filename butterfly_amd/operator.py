@@ -101,19 +101,21 @@ class HipOperator:
     @classmethod
     def build_helm2(cls, desc, points, wavenumber, root=None, workspace_bytes=0, layer_pot="S", normals=None,
                     col_weights=None, self_value=0.0, kr_order=0, orig_index=None, alpha=0.0, beta=0.0, tgt_points=None,
-                    tgt_normals=None, rhs_blocks=None, real_rhs_blocks=None, adjoint_rhs_blocks=None, **opts):
+                    tgt_normals=None, rhs_blocks=None, real_rhs_blocks=None, adjoint_rhs_blocks=None, out_dtype=None, **opts):
         """bfhipBuildHelm2: lay out `desc` (helm2_structure with recipes=True) and
         compute every leaf on the device from its recipe.  `points` (and
         `normals` for layer_pot="Sp"): [N, 2] in quadtree order.  The operator
         built is  self_value * I + (K o KR) diag(col_weights), KR = Kapur-Rokhlin
         factors of order `kr_order` (needs orig_index = the quadtree permutation).
+        out_dtype: None / BFHIP_C128, or BFHIP_C64 for a complex64 operator (the double-precision
+        values rounded once; `demote_to_f32` stays refused here).
         Returns (operator, build statistics)."""
         lib = _capi.load()
         da = DescArrays(desc, root=root)
         recipes = getattr(desc, "recipe_array", None)
         prob = _capi.Helm2Problem(points, wavenumber, recipes if recipes is not None else desc.recipe, workspace_bytes, layer_pot, normals,
                                   col_weights, self_value,
-                                  kr_order, orig_index, alpha, beta, tgt_points, tgt_normals)
+                                  kr_order, orig_index, alpha, beta, tgt_points, tgt_normals, out_dtype)
         st = _capi.BfhipBuildStats()
         st.structSize = C.sizeof(st)
         h = C.c_void_p()
@@ -122,18 +124,40 @@ class HipOperator:
         return cls(h.value)._with_rhs_blocks(rhs_blocks, real_rhs_blocks, adjoint_rhs_blocks), st.as_dict()
 
     @classmethod
+    def build_helm2_pair(cls, desc, points, wavenumber, root=None, workspace_bytes=0, layer_pot="S", normals=None,
+                         col_weights=None, self_value=0.0, kr_order=0, orig_index=None, alpha=0.0, beta=0.0, tgt_points=None,
+                         tgt_normals=None, low_opts=None, **opts):
+        """bfhipBuildHelm2Pair: one value build, two operators -- the complex128 operator build_helm2(**opts) makes and
+        the complex64 one build_helm2(out_dtype=BFHIP_C64, **low_opts) makes (low_opts: a dict of compile options, None =
+        opts), e.g. the operand and the inner operator of solve_gmres_refine_device.  Returns (op, low, build statistics)."""
+        lib = _capi.load()
+        da = DescArrays(desc, root=root)
+        recipes = getattr(desc, "recipe_array", None)
+        prob = _capi.Helm2Problem(points, wavenumber, recipes if recipes is not None else desc.recipe, workspace_bytes, layer_pot, normals,
+                                  col_weights, self_value, kr_order, orig_index, alpha, beta, tgt_points, tgt_normals)
+        st = _capi.BfhipBuildStats()
+        st.structSize = C.sizeof(st)
+        h, hl = C.c_void_p(), C.c_void_p()
+        o = _options(**opts)
+        ol = None if low_opts is None else _options(**low_opts)
+        check(lib.bfhipBuildHelm2Pair(da.byref(), prob.byref(), C.byref(o), None if ol is None else C.byref(ol), C.byref(h), C.byref(hl),
+                                      C.byref(st)))
+        return cls(h.value), cls(hl.value), st.as_dict()
+
+    @classmethod
     def fac_helm2_make_multilevel(cls, points, wavenumber, normals=None, col_weights=None, layer_pot="S", self_value=0.0,
                                   kr_order=0, alpha=0.0, beta=0.0, workspace_bytes=0, tgt_points=None, tgt_normals=None, rhs_blocks=None, real_rhs_blocks=None, adjoint_rhs_blocks=None,
-                                  **opts):
+                                  out_dtype=None, **opts):
         """bfhipFacHelm2MakeMultilevel[2]: points (original order) -> device operator in one native
         call (C layout + device build).  Returns (operator, perm, build statistics), or with
         `tgt_points` (operator, (perm, tgt_perm), statistics); the operator maps x[perm] to
-        y[tgt_perm] (quadtree orders)."""
+        y[tgt_perm] (quadtree orders).  out_dtype as build_helm2."""
         lib = _capi.load()
         f64 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
         ptr = lambda a: None if a is None else a.ctypes.data
         pts, nrm, w, tpts, tnrm = f64(points), f64(normals), f64(col_weights), f64(tgt_points), f64(tgt_normals)
-        params = _capi.Helm2Problem(pts, wavenumber, None, workspace_bytes, layer_pot, None, None, self_value, kr_order, None, alpha, beta)
+        params = _capi.Helm2Problem(pts, wavenumber, None, workspace_bytes, layer_pot, None, None, self_value, kr_order, None, alpha, beta,
+                                    out_dtype=out_dtype)
         st = _capi.BfhipBuildStats()
         st.structSize = C.sizeof(st)
         perm = np.empty(len(pts), dtype=np.uint64)

@@ -107,8 +107,9 @@ typedef struct BfhipOptions {
   uint32_t demoteToF32;     /* 1: store/compute BFHIP_F64 operands in fp32 and BFHIP_C128 operands in complex64 (BFHIP_C64; config 5
                              * extension).  A complex64 operator's bfhipApplyDevice / bfhipApplyTransposeDevice take complex64 device
                              * vectors (interleaved float re / im); its host entries (bfhipApply, the vtable shim) keep taking complex128.
-                             * GMRES, covariance products and the Helmholtz builders refuse complex64 (NOT_IMPLEMENTED / TYPE_ERROR);
-                             * bfhipSolveGMRESRefine[Device] takes one as its inner operator. */
+                             * GMRES and covariance products refuse complex64 (NOT_IMPLEMENTED / TYPE_ERROR); the Helmholtz builders
+                             * refuse this field (NOT_IMPLEMENTED) and make complex64 operators through BfhipHelm2Problem.outDtype
+                             * or bfhipBuildHelm2Pair (bfhip_build.h); bfhipSolveGMRESRefine[Device] takes one as its inner operator. */
   uint32_t reserved0;
   uint64_t seed;            /* value seed for synthetic (data == NULL) leaves */
   /* row sharding: keep only block rows
@@ -463,8 +464,8 @@ int bfhipSolveGMRESOptsDevice(BfhipOperator *op, const BfhipGmresOptions *opt, c
  * dX, history = maxOuter + 1 doubles: the residual of x0, then of each step's iterate (entries past numOuter: NaN).
  * Types: `op` complex128 and `opLow` complex64 (TYPE_ERROR otherwise), both n x n on one device; dB, dX0 (NULL =
  * zeros) and dX complex128 row-major n x nrhs as for bfhipSolveGMRESDevice.  Every argument is checked before the
- * operator's device is (plan-only operators reach each refusal).  Device operators compiled from a BfMat or a
- * descriptor only: the Helmholtz builders make no complex64 operator. */
+ * operator's device is (plan-only operators reach each refusal).  `opLow` may also come from the
+ * Helmholtz builder (outDtype = BFHIP_C64); bfhipBuildHelm2Pair makes `op` and `opLow` from one value build. */
 typedef struct BfhipGmresRefineOptions {
   uint32_t structSize;          /* = sizeof(BfhipGmresRefineOptions) */
   uint32_t orthogonalization;   /* inner GMRES: BFHIP_GMRES_ORTH_* (as BfhipGmresOptions) */

@@ -107,7 +107,12 @@ typedef struct BfhipHelm2Problem {
    * block.  krOrder: 0 (none), 2, 6 or 10; origIndex[t] = original index of tree position t. */
   const uint64_t *origIndex; /* [numPoints] or NULL (needed iff krOrder != 0) */
   uint32_t krOrder;
-  uint32_t reserved;
+  uint32_t outDtype;         /* storage of the operator built: 0 = BFHIP_C128 (the default), or BFHIP_C64 -- the operator
+                                bfhipCompileDesc makes of the descriptor under demoteToF32 (the real family's plan, complex MACs in
+                                double, device entries on complex64 vectors, host entries on complex128), its leaf values the
+                                builder's double-precision ones (decorations folded in double) with each component rounded to
+                                float once, to nearest even.  Anything else: INVALID_ARGUMENTS.  bfhipHelm2BuildLeaf and the
+                                dense applies ignore it (complex128).  (This word was `reserved`: a zeroed struct is unchanged.) */
   double alpha[2], beta[2];  /* COMBINED_FIELD: complex coefficients (BfHelm2.alpha, .beta, include/bf/helm2.h:13-14) */
   /* a separate target tree: rows of the operator follow tgtPoints (quadtree order of THAT tree).
    * NULL: targets are `points` (square operator).  selfValue / KR apply to square operators only. */
@@ -133,9 +138,21 @@ typedef struct BfhipBuildStats {
 
 /* Compile `desc` (all dense leaves must have leafData == NULL and a recipe)
  * and compute the leaf values on the device.  `opts` as bfhipCompileDesc
- * (sharding keeps only the recipes whose leaves survive).  `stats` may be NULL. */
+ * (sharding keeps only the recipes whose leaves survive).  `stats` may be NULL.
+ * prob->outDtype = BFHIP_C64 makes a complex64 operator; opts->demoteToF32 is refused (NOT_IMPLEMENTED) on every builder
+ * entry -- the builder's output type is the problem's, not the compile's. */
 int bfhipBuildHelm2(const BfhipDesc *desc, const BfhipHelm2Problem *prob, const BfhipOptions *opts,
                     BfhipOperator **out, BfhipBuildStats *stats);
+
+/* One value build, two operators: *out is bit for bit what bfhipBuildHelm2 makes with `opts`, *outLow what it makes with
+ * `optsLow` (NULL = opts) and outDtype = BFHIP_C64 -- the operand and the inner operator of bfhipSolveGMRESRefine[Device].
+ * Every leaf is evaluated and every least-squares problem solved once; each batch of leaves is packed into both arenas.
+ * prob->outDtype must be 0 / BFHIP_C128.  Both operators live on one device (different `device` fields: INVALID_ARGUMENTS);
+ * flags, maxRhs and the shard fields may differ: a recipe is built if its leaf survives in either plan and packed where it
+ * survives.  On any failure (the unconverged-SVD refusal included) neither operator is returned.  `stats` counts each leaf,
+ * evaluation and sweep once. */
+int bfhipBuildHelm2Pair(const BfhipDesc *desc, const BfhipHelm2Problem *prob, const BfhipOptions *opts, const BfhipOptions *optsLow,
+                        BfhipOperator **out, BfhipOperator **outLow, BfhipBuildStats *stats);
 
 /* ---- layout: points -> block structure + recipes (host only) ------------------------------
  * What bfFacHelm2MakeMultilevel(helm, quadtree, quadtree) would lay out for `points` (quadtree with
