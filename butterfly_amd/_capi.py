@@ -135,6 +135,18 @@ class BfhipBuildStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_ if n != "structSize"}
 
 
+COND_MAX_OBS = 2048        # BFHIP_COND_MAX_OBS
+
+
+class BfhipCovCondInfo(C.Structure):
+    _fields_ = [("structSize", C.c_uint32), ("numObs", C.c_uint32), ("minPivot", C.c_double), ("maxPivot", C.c_double),
+                ("setupApplies", C.c_uint64), ("factorBytes", C.c_uint64), ("rowsSeconds", C.c_double), ("gramSeconds", C.c_double),
+                ("factorSeconds", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "structSize"}
+
+
 def _pts(rec, spec):
     if spec[0] in ("node", "tnode"):
         rec["kind"], rec["first"], rec["count"] = (PTS_TREE if spec[0] == "node" else PTS_TREE_TGT), spec[1], spec[2] - spec[1]
@@ -500,6 +512,20 @@ def load():
     lib.bfhipCovDrawDevice.restype = C.c_int
     lib.bfhipCovMomentsDevice.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, vp, vp, vp]
     lib.bfhipCovMomentsDevice.restype = C.c_int
+    lib.bfhipCovCondCreate.argtypes = [vp, vp, vp, vp, C.c_size_t, vp, C.POINTER(vp), vp]
+    lib.bfhipCovCondCreate.restype = C.c_int
+    lib.bfhipCovCondFree.argtypes = [C.POINTER(vp)]
+    lib.bfhipCovCondFree.restype = None
+    lib.bfhipCovCondGetInfo.argtypes = [vp, C.POINTER(BfhipCovCondInfo)]
+    lib.bfhipCovCondGetInfo.restype = C.c_int
+    lib.bfhipCovCondSampleBlockDevice.argtypes = [vp, vp, vp, vp, C.c_size_t, vp, vp, vp]
+    lib.bfhipCovCondSampleBlockDevice.restype = C.c_int
+    lib.bfhipCovCondMeanDevice.argtypes = [vp, vp, vp, vp, vp]
+    lib.bfhipCovCondMeanDevice.restype = C.c_int
+    lib.bfhipCovCondDrawDevice.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_size_t, vp, vp]
+    lib.bfhipCovCondDrawDevice.restype = C.c_int
+    lib.bfhipCovCondMomentsDevice.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, vp, vp, vp]
+    lib.bfhipCovCondMomentsDevice.restype = C.c_int
     lib.bfhipSetProfileSampling.argtypes = [vp, C.c_uint32]
     lib.bfhipSetProfileSampling.restype = C.c_int
     lib.bfhipPlanGetInfo.argtypes = [vp, C.POINTER(BfhipPlanInfo)]

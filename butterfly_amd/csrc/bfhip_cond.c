@@ -1,0 +1,297 @@
+/* bfhip_cond.c -- conditioning covariance samples on observations by a direct solve (include/bfhip.h, "conditioning on
+ * observations").  Host side only: Create forms the observed rows of P A GammaLam with the adjoint
+ * block apply, their Gram matrix and its Cholesky factor; a pass of <= 64 samples is then two contractions with the
+ * stored n x k matrix, two triangular solves and ONE block sample (covSampleBlock of bfhip_cov.c, started from the
+ * operator's covariance scratch).  The kernels are bfhip_cond.hip's.  A file of its own, like bfhip_cov.c, so that the
+ * device-free sanitizer build of the host code keeps linking against its stubs unchanged. */
+#include <math.h>
+#include <stdint.h>
+#include <stdlib.h>
+#include <string.h>
+#include <time.h>
+
+#include "bfhip_operator.h"
+#include "../../include/bfhip.h"
+#include "../../include/bfhip_abi.h"
+
+struct BfhipCovCond {
+  BfhipOperator *op;             /* referenced, like dGammaLam and dRowPerm */
+  void const *dGammaLam;
+  uint64_t const *dRowPerm;
+  int device;                    /* the operator's, kept so that Free reads nothing through op */
+  uint32_t k;
+  double *dBt;                   /* [n x k] */
+  double *dL;                    /* [k x k]: G + D, then L */
+  double *dNoiseVar, *dNoiseSd;  /* [k] each; NULL without noise */
+  double *dR;                    /* [k x 64]: R, solved in place into alpha */
+  double *dE;                    /* [k x 64]: the draw's noise block */
+  void *dWn;                     /* [n x 64], operator dtype: the draw's normals */
+  double *dPart;                 /* [chunks x k x 64]: partial sums of R */
+  BfhipCovCondInfo info;
+};
+
+static double nowSeconds(void) {
+  struct timespec t;
+  clock_gettime(CLOCK_MONOTONIC, &t);
+  return (double)t.tv_sec + 1e-9 * (double)t.tv_nsec;
+}
+
+typedef struct { uint64_t obs; uint32_t slot; } ObsKey;
+static int obsKeyCmp(void const *a, void const *b) {
+  uint64_t const x = ((ObsKey const *)a)->obs, y = ((ObsKey const *)b)->obs;
+  return x < y ? -1 : x > y;
+}
+
+static void condRelease(BfhipCovCond *c) {
+  if (!c) return;
+  bfdevFree(c->dBt); bfdevFree(c->dL); bfdevFree(c->dNoiseVar); bfdevFree(c->dNoiseSd); bfdevFree(c->dR); bfdevFree(c->dE); bfdevFree(c->dWn); bfdevFree(c->dPart);
+  free(c);
+}
+
+int bfhipCovCondCreate(BfhipOperator *op, void const *dGammaLam, uint64_t const *dRowPerm, uint64_t const *obs, size_t numObs, double const *noiseVar,
+                       BfhipCovCond **out, void *stream) {
+  if (out) *out = NULL;
+  if (!op || !obs || !out) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL argument");
+  if (numObs == 0 || numObs > BFHIP_COND_MAX_OBS) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "numObs out of range (1 .. %u)", BFHIP_COND_MAX_OBS);
+  uint32_t const k = (uint32_t)numObs;
+  ObsKey *keys = malloc(k * sizeof *keys);
+  if (!keys) return bfhipFail(BFABI_ERROR_MEMORY_ERROR, "out of host memory");
+  for (uint32_t a = 0; a < k; ++a) { keys[a].obs = obs[a]; keys[a].slot = a; }
+  qsort(keys, k, sizeof *keys, obsKeyCmp);
+  int rc = 0, prev = -1;
+  for (uint32_t a = 1; a < k && !rc; ++a)
+    if (keys[a].obs == keys[a - 1].obs) rc = bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "observed index %llu is repeated", (unsigned long long)keys[a].obs);
+  if (noiseVar) for (uint32_t a = 0; a < k && !rc; ++a)
+    if (!(noiseVar[a] >= 0.0) || !isfinite(noiseVar[a])) rc = bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "noiseVar[%u] is negative or not finite", a);
+  if (!rc && keys[k - 1].obs >= op->plan.numRows)
+    rc = bfhipFail(BFABI_ERROR_OUT_OF_RANGE, "observed index %llu is outside the %llu rows", (unsigned long long)keys[k - 1].obs, (unsigned long long)op->plan.numRows);
+  if (!rc && bfDtypeComplex(op->plan.dtype)) rc = bfhipFail(BFABI_ERROR_TYPE_ERROR, "covariance products are defined for real operators (not complex128 / complex64)");
+  if (!rc && !op->hasTplan) rc = bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "operator was not compiled with BFHIP_FLAG_ADJOINT");
+  if (!rc && (op->flags & BFHIP_FLAG_PLAN_ONLY)) rc = bfhipFail(BFABI_ERROR_RUNTIME_ERROR, "operator was compiled with BFHIP_FLAG_PLAN_ONLY: no device operator exists");
+  /* the launch shapes of the per-pass kernels (bfhip_cond.hip): refused here, not in the first sample call after seconds of setup */
+  if (!rc && !bfdevCondFits(op->plan.numCols)) rc = bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "conditioning: %llu columns are more than the contractions' grids take (%llu)",
+                                                              (unsigned long long)op->plan.numCols, (unsigned long long)BF_COND_MAX_COLS);
+  if (rc) { free(keys); return rc; }
+
+  uint64_t const m = op->plan.numRows, n = op->plan.numCols;
+  size_t const es = op->plan.elemSize;
+  uint32_t const dtype = op->plan.dtype, Q = BF_COND_MAX_RHS;
+  uint64_t const chunks = (n + BF_COND_CHUNK - 1) / BF_COND_CHUNK;
+  BfhipCovCond *c = calloc(1, sizeof *c);
+  uint64_t *hRows = malloc(k * sizeof *hRows), *hSorted = malloc(k * sizeof *hSorted);
+  uint32_t *hSlot = malloc(k * sizeof *hSlot);
+  double *hSd = malloc(k * sizeof *hSd);
+  void *dRows = NULL, *dSorted = NULL, *dSlot = NULL, *dFlag = NULL, *dStat = NULL;
+  if (!c || !hRows || !hSorted || !hSlot || !hSd) { rc = bfhipFail(BFABI_ERROR_MEMORY_ERROR, "out of host memory"); goto fail; }
+  c->op = op; c->dGammaLam = dGammaLam; c->dRowPerm = dRowPerm; c->k = k; c->device = op->device;
+  bfdevGetDevice(&prev);
+  if (prev != op->device && (rc = bfdevSetDevice(op->device))) goto fail;
+
+  /* ---- everything a later call needs, for passes of 64 columns ---- */
+  if ((rc = bfdevSync(stream))) goto fail;
+  if ((rc = bfhipOperatorReserveRhs(op, Q))) goto fail;
+  if ((rc = covScratch(op, Q, stream))) goto fail;
+  size_t const bytesBt = n * k * sizeof(double), bytesL = (size_t)k * k * sizeof(double), bytesR = (size_t)k * Q * sizeof(double);
+  size_t const bytesW = n * Q * es, bytesPart = chunks * bytesR;
+  if ((rc = bfdevMalloc((void **)&c->dBt, bytesBt)) || (rc = bfdevMalloc((void **)&c->dL, bytesL)) || (rc = bfdevMalloc((void **)&c->dR, bytesR)) ||
+      (rc = bfdevMalloc((void **)&c->dE, bytesR)) || (rc = bfdevMalloc(&c->dWn, bytesW)) || (rc = bfdevMalloc((void **)&c->dPart, bytesPart)) ||
+      (rc = bfdevMalloc(&dRows, k * 8)) || (rc = bfdevMalloc(&dStat, sizeof(BfCondStat)))) goto fail;
+  c->info.structSize = sizeof c->info; c->info.numObs = k;
+  c->info.factorBytes = bytesBt + bytesL + 2 * bytesR + bytesW + bytesPart;
+  if (noiseVar) {
+    for (uint32_t a = 0; a < k; ++a) hSd[a] = sqrt(noiseVar[a]);
+    if ((rc = bfdevMalloc((void **)&c->dNoiseVar, k * 8)) || (rc = bfdevMalloc((void **)&c->dNoiseSd, k * 8)) ||
+        (rc = bfdevMemcpyH2D(c->dNoiseVar, noiseVar, k * 8)) || (rc = bfdevMemcpyH2D(c->dNoiseSd, hSd, k * 8))) goto fail;
+    c->info.factorBytes += 2 * k * 8;
+  }
+
+  /* ---- phase 1: the rows i_a, then B^T by adjoint panels of <= 64 unit columns ---- */
+  double t0 = nowSeconds();
+  if (dRowPerm) {
+    uint32_t flag = 0;
+    for (uint32_t a = 0; a < k; ++a) { hSorted[a] = keys[a].obs; hSlot[a] = keys[a].slot; hRows[a] = UINT64_MAX; }
+    if ((rc = bfdevMalloc(&dSorted, k * 8)) || (rc = bfdevMalloc(&dSlot, k * 4)) || (rc = bfdevMalloc(&dFlag, 4)) ||
+        (rc = bfdevMemcpyH2D(dSorted, hSorted, k * 8)) || (rc = bfdevMemcpyH2D(dSlot, hSlot, k * 4)) || (rc = bfdevMemcpyH2D(dFlag, &flag, 4)) ||
+        (rc = bfdevMemcpyH2D(dRows, hRows, k * 8))) goto fail;
+    if ((rc = bfdevCondInvertPerm(dRowPerm, m, dSorted, dSlot, k, dRows, dFlag, stream)) || (rc = bfdevSync(stream)) ||
+        (rc = bfdevMemcpyD2H(hRows, dRows, k * 8)) || (rc = bfdevMemcpyD2H(&flag, dFlag, 4))) goto fail;
+    for (uint32_t a = 0; a < k && !flag; ++a) if (hRows[a] >= m) flag = 1;
+    if (flag) { rc = bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "dRowPerm does not hit every observed index exactly once"); goto fail; }
+  } else {
+    if ((rc = bfdevMemcpyH2D(dRows, obs, k * 8))) goto fail;
+  }
+  {
+    uint64_t const big = m > n ? m : n;
+    char *v = op->dCov, *t = (char *)op->dCov + big * Q * es;        /* the scratch's halves: unit panel, adjoint result */
+    for (uint32_t c0 = 0; c0 < k; c0 += Q) {
+      uint32_t const p = k - c0 < Q ? k - c0 : Q;
+      if ((rc = bfdevMemsetAsync(v, 0, m * p * es, stream)) || (rc = bfdevCondUnitPanel(v, m, p, (uint64_t const *)dRows + c0, dtype, stream)) ||
+          (rc = bfhipApplyTransposeDevice(op, v, p, t, stream)) || (rc = bfdevCondPack(c->dBt, n, k, c0, t, p, dGammaLam, dtype, stream))) goto fail;
+      ++c->info.setupApplies;
+    }
+  }
+  if ((rc = bfdevSync(stream))) goto fail;
+  double t1 = nowSeconds();
+  c->info.rowsSeconds = t1 - t0;
+
+  /* ---- phase 2: G + D (lower triangle; the rest stays zero) ---- */
+  if ((rc = bfdevMemsetAsync(c->dL, 0, bytesL, stream)) || (rc = bfdevCondGram(c->dL, c->dBt, n, k, c->dNoiseVar, stream)) || (rc = bfdevSync(stream))) goto fail;
+  t0 = nowSeconds();
+  c->info.gramSeconds = t0 - t1;
+
+  /* ---- phase 3: Cholesky in place; the flag is read once, at the end ---- */
+  BfCondStat st = {0xffffffffu, 0, INFINITY, -INFINITY};
+  if ((rc = bfdevMemcpyH2D(dStat, &st, sizeof st)) || (rc = bfdevCondCholesky(c->dL, k, dStat, stream)) || (rc = bfdevSync(stream)) ||
+      (rc = bfdevMemcpyD2H(&st, dStat, sizeof st))) goto fail;
+  c->info.factorSeconds = nowSeconds() - t0;
+  if (st.failStep != 0xffffffffu) {
+    rc = bfhipFail(BFABI_ERROR_RUNTIME_ERROR, "Cholesky of G + D (%u observations): the pivot at step %u is <= 0 or not finite", k, st.failStep);
+    goto fail;
+  }
+  c->info.minPivot = st.minPivot; c->info.maxPivot = st.maxPivot;
+  *out = c; c = NULL;
+fail:
+  condRelease(c);
+  bfdevFree(dRows); bfdevFree(dSorted); bfdevFree(dSlot); bfdevFree(dFlag); bfdevFree(dStat);
+  free(keys); free(hRows); free(hSorted); free(hSlot); free(hSd);
+  if (prev >= 0 && prev != op->device) bfdevSetDevice(prev);
+  return rc;
+}
+
+/* Work enqueued on any stream may still read Bt, L and the per-pass blocks: the whole device is drained first.  Nothing is read
+ * through c->op (the header asks for the object to go before its operator; the buffers are released correctly either way). */
+void bfhipCovCondFree(BfhipCovCond **c) {
+  if (!c || !*c) return;
+  int prev = -1;
+  int const device = (*c)->device;
+  bfdevGetDevice(&prev);
+  if (prev != device) bfdevSetDevice(device);
+  bfdevCondDeviceSync();
+  condRelease(*c);
+  *c = NULL;
+  if (prev >= 0 && prev != device) bfdevSetDevice(prev);
+}
+
+int bfhipCovCondGetInfo(BfhipCovCond const *c, BfhipCovCondInfo *info) {
+  if (!c || !info || info->structSize < sizeof *info) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL argument / BfhipCovCondInfo.structSize too small");
+  *info = c->info;
+  return 0;
+}
+
+/* One pass of b <= 64 columns: alpha into c->dR, W' (not yet scaled by GammaLam) into the first b columns' worth of the
+ * operator's covariance scratch, where a block sample of b columns starts.  W [n x .] and E [k x .] have leading
+ * dimensions ldw / lde (a pass of a wider block); NULL stands for zeros. */
+static int condPass(BfhipCovCond *c, double const *dY, void const *W, uint64_t ldw, double const *E, uint64_t lde, uint32_t b, void *stream) {
+  BfhipOperator *op = c->op;
+  uint64_t const n = op->plan.numCols;
+  int rc;
+  if ((rc = bfdevCondResidual(c->dR, c->dPart, c->dBt, n, c->k, dY, W, ldw, op->plan.dtype, E, lde, b, stream))) return rc;
+  if ((rc = bfdevCondSolve(c->dL, c->k, c->dR, b, stream))) return rc;
+  return bfdevCondUpdate(op->dCov, c->dBt, n, c->k, c->dR, W, ldw, op->plan.dtype, b, stream);
+}
+
+/* The rest of a pass: the block sample of the b columns of W' that condPass left in the scratch's first half, into columns
+ * s0 .. s0 + b - 1 of dZ [m x nrhs].  The one place that knows the scratch convention: covSampleBlock scales the first half in
+ * place, applies into the second and, with a permutation, scatters from there.  A whole call (b == nrhs) writes dZ directly; a
+ * pass of a wider block lands packed in the half that sequence leaves free and is copied into its columns. */
+static int condFinish(BfhipCovCond *c, uint32_t b, size_t nrhs, size_t s0, void *dZ, void *stream) {
+  BfhipOperator *op = c->op;
+  uint64_t const m = op->plan.numRows, n = op->plan.numCols, big = m > n ? m : n;
+  size_t const es = op->plan.elemSize;
+  if (b == nrhs) return covSampleBlock(op, c->dGammaLam, c->dRowPerm, op->dCov, 0, b, dZ, stream);
+  char *t0 = op->dCov, *t1 = (char *)op->dCov + big * b * es, *packed = c->dRowPerm ? t0 : t1;
+  int rc = covSampleBlock(op, c->dGammaLam, c->dRowPerm, t0, 0, b, packed, stream);
+  if (!rc) rc = bfdevMemcpy2DAsync((char *)dZ + s0 * es, nrhs * es, packed, b * es, b * es, m, stream);
+  return rc;
+}
+
+/* the passes of a block call: W / E NULL = zeros; dZ [m x nrhs], dAlpha [k x nrhs] or NULL */
+static int condBlock(BfhipCovCond *c, double const *dY, void const *dW, double const *dEps, size_t nrhs, void *dZ, double *dAlpha, void *stream) {
+  size_t const es = c->op->plan.elemSize;
+  int rc = 0;
+  for (size_t s0 = 0; s0 < nrhs && !rc; s0 += BF_COND_MAX_RHS) {
+    uint32_t const b = (uint32_t)(nrhs - s0 < BF_COND_MAX_RHS ? nrhs - s0 : BF_COND_MAX_RHS);
+    if ((rc = condPass(c, dY, dW ? (char const *)dW + s0 * es : NULL, nrhs, dEps ? dEps + s0 : NULL, nrhs, b, stream))) break;
+    if (dAlpha) {
+      if (b == nrhs) rc = bfdevMemcpyD2DAsync(dAlpha, c->dR, (size_t)c->k * b * sizeof(double), stream);
+      else rc = bfdevMemcpy2DAsync(dAlpha + s0, nrhs * sizeof(double), c->dR, b * sizeof(double), b * sizeof(double), c->k, stream);
+      if (rc) break;
+    }
+    rc = condFinish(c, b, nrhs, s0, dZ, stream);
+  }
+  return rc;
+}
+
+static int condEnter(BfhipCovCond *c, int *prev) {
+  *prev = -1;
+  bfdevGetDevice(prev);
+  return *prev != c->op->device ? bfdevSetDevice(c->op->device) : 0;
+}
+static void condLeave(BfhipCovCond *c, int prev) { if (prev >= 0 && prev != c->op->device) bfdevSetDevice(prev); }
+
+int bfhipCovCondSampleBlockDevice(BfhipCovCond *c, double const *dY, void const *dW, double const *dEps, size_t nrhs, void *dZ, double *dAlpha, void *stream) {
+  if (!c || !dY || !dW || !dZ) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL argument");
+  if (nrhs == 0 || nrhs > 0xffffu) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "nrhs out of range");
+  int rc, prev;
+  if ((rc = condEnter(c, &prev))) return rc;
+  rc = condBlock(c, dY, dW, dEps, nrhs, dZ, dAlpha, stream);
+  condLeave(c, prev);
+  return rc;
+}
+
+int bfhipCovCondMeanDevice(BfhipCovCond *c, double const *dY, void *dMean, double *dAlpha, void *stream) {
+  if (!c || !dY || !dMean) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL argument");
+  int rc, prev;
+  if ((rc = condEnter(c, &prev))) return rc;
+  rc = condBlock(c, dY, NULL, NULL, 1, dMean, dAlpha, stream);
+  condLeave(c, prev);
+  return rc;
+}
+
+/* the normals of samples first .. first + b - 1 into c->dWn [n x b] and c->dE [k x b] (the latter scaled, in double) */
+static int condFill(BfhipCovCond *c, uint64_t seed, uint64_t noiseSeed, uint64_t first, uint32_t b, void *stream) {
+  int rc = bfdevCovDrawFill(c->dWn, NULL, c->op->plan.numCols, b, c->op->plan.dtype, seed, first, stream);
+  if (!rc && c->dNoiseSd) rc = bfdevCovDrawFill(c->dE, c->dNoiseSd, c->k, b, BFHIP_F64, noiseSeed, first, stream);
+  return rc;
+}
+
+int bfhipCovCondDrawDevice(BfhipCovCond *c, double const *dY, uint64_t seed, uint64_t noiseSeed, uint64_t firstSample, size_t nrhs, void *dZ, void *stream) {
+  if (!c || !dY || !dZ) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL argument");
+  if (nrhs == 0 || nrhs > 0xffffu) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "nrhs out of range");
+  int rc, prev;
+  if ((rc = condEnter(c, &prev))) return rc;
+  for (size_t s0 = 0; s0 < nrhs && !rc; s0 += BF_COND_MAX_RHS) {
+    uint32_t const b = (uint32_t)(nrhs - s0 < BF_COND_MAX_RHS ? nrhs - s0 : BF_COND_MAX_RHS);
+    if ((rc = condFill(c, seed, noiseSeed, firstSample + s0, b, stream))) break;
+    if ((rc = condPass(c, dY, c->dWn, b, c->dNoiseSd ? c->dE : NULL, b, b, stream))) break;
+    rc = condFinish(c, b, nrhs, s0, dZ, stream);
+  }
+  condLeave(c, prev);
+  return rc;
+}
+
+int bfhipCovCondMomentsDevice(BfhipCovCond *c, double const *dY, uint64_t seed, uint64_t noiseSeed, uint64_t firstSample, uint64_t numSamples, uint32_t batch,
+                              double *dSum, double *dSumSq, void *stream) {
+  if (!c || !dY) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL argument");
+  if (!dSum && !dSumSq) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "both moment outputs are NULL");
+  if (batch > BF_COND_MAX_RHS) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "batch out of range (at most 64)");
+  if (numSamples == 0) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "numSamples is zero");
+  if (!batch) batch = BF_COND_MAX_RHS;
+  if (batch > numSamples) batch = (uint32_t)numSamples;
+  int rc, prev;
+  if ((rc = condEnter(c, &prev))) return rc;
+  BfhipOperator *op = c->op;
+  uint64_t const m = op->plan.numRows, n = op->plan.numCols, big = m > n ? m : n;
+  for (uint64_t s0 = 0; s0 < numSamples && !rc; s0 += batch) {
+    uint32_t const b = (uint32_t)(numSamples - s0 < batch ? numSamples - s0 : batch);
+    char *t0 = op->dCov, *t1 = (char *)op->dCov + big * b * op->plan.elemSize;
+    if ((rc = condFill(c, seed, noiseSeed, firstSample + s0, b, stream))) break;
+    if ((rc = condPass(c, dY, c->dWn, b, c->dNoiseSd ? c->dE : NULL, b, b, stream))) break;
+    /* the block sample without its scatter (scale in place, apply into the second half): Z is never written, the un-permuted
+     * result goes straight into the sums of its rows' places */
+    if ((rc = covSampleBlock(op, c->dGammaLam, NULL, t0, 0, b, t1, stream))) break;
+    rc = bfdevCovMoments(t1, m, b, op->plan.dtype, c->dRowPerm, dSum, dSumSq, stream);
+  }
+  condLeave(c, prev);
+  return rc;
+}

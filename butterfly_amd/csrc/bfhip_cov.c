@@ -27,7 +27,7 @@ static int covBlockCheck(BfhipOperator const *op, void const *in, void const *ou
 }
 
 /* z = P A (GammaLam w) on blocks.  `scaled`: the input block is already in the scratch's first half, scaled (the draw) */
-static int covSampleBlock(BfhipOperator *op, void const *dGammaLam, uint64_t const *dRowPerm, void const *dW, int scaled, size_t nrhs, void *dZ, void *stream) {
+int covSampleBlock(BfhipOperator *op, void const *dGammaLam, uint64_t const *dRowPerm, void const *dW, int scaled, size_t nrhs, void *dZ, void *stream) {
   uint64_t const m = op->plan.numRows, n = op->plan.numCols, big = m > n ? m : n;
   size_t const es = op->plan.elemSize;
   char *t0 = op->dCov, *t1 = (char *)op->dCov + big * nrhs * es;

@@ -1,6 +1,6 @@
 /* bfhip_operator.h -- struct BfhipOperator and the few helpers shared by the files that implement it: bfhip_api.c
- * (lifetime, compile, apply), bfhip_file.c (save / load), bfhip_shim.c (BfMat vtable), bfhip_inspect.c (plan inspection) and
- * bfhip_cov.c (batched covariance sampling).  Private to those five: every other file reads an operator through the bfhipOperator* accessors of bfhip_internal.h.
+ * (lifetime, compile, apply), bfhip_file.c (save / load), bfhip_shim.c (BfMat vtable), bfhip_inspect.c (plan inspection),
+ * bfhip_cov.c (batched covariance sampling) and bfhip_cond.c (conditioning on observations).  Private to those six: every other file reads an operator through the bfhipOperator* accessors of bfhip_internal.h.
  */
 #ifndef BFHIP_OPERATOR_H
 #define BFHIP_OPERATOR_H
@@ -67,5 +67,32 @@ BF_HIDDEN void stageLaunchArgs(BfhipOperator const *op, BfPlan const *plan, BfSt
 /* the covariance entries' scratch holds at least `nrhs` columns after this (bfhip_api.c; the batched entries of bfhip_cov.c share it) */
 BF_HIDDEN int covScratch(BfhipOperator *op, size_t nrhs, void *stream);
 BF_HIDDEN int applyHost(BfhipOperator *op, int transpose, void const *X, size_t ldx, size_t nrhs, void *Y, size_t ldy);
+/* z = P A (GammaLam w) on a block (bfhip_cov.c); `scaled`: the input is already in the scratch's first half, scaled.  With scaled = 0, dW may
+ * BE the scratch's first half (it is scaled in place): the conditioned entries of bfhip_cond.c start from there */
+BF_HIDDEN int covSampleBlock(BfhipOperator *op, void const *dGammaLam, uint64_t const *dRowPerm, void const *dW, int scaled, size_t nrhs, void *dZ, void *stream);
+
+/* ---- conditioning on observations: the device entry points of bfhip_cond.c, defined in bfhip_cond.hip ---- */
+#define BF_COND_CHUNK 1024u          /* rows of Bt per partial sum of the two contractions over n */
+#define BF_COND_MAX_RHS 64u          /* columns a pass */
+/* numCols the per-pass kernels take: one grid z per chunk of the first contraction (<= 65535; the second's 2^31 - 1 tiles of 32 rows is the wider limit) */
+#define BF_COND_MAX_COLS (65535ull * BF_COND_CHUNK)
+static inline int bfdevCondFits(uint64_t numCols) { return numCols <= BF_COND_MAX_COLS; }
+typedef struct { uint32_t failStep, pad; double minPivot, maxPivot; } BfCondStat;   /* failStep 0xffffffff: none */
+#ifdef __cplusplus
+extern "C" {
+#endif
+int bfdevCondInvertPerm(uint64_t const *dPerm, uint64_t m, uint64_t const *dObsSorted, uint32_t const *dObsSlot, uint32_t k, uint64_t *dRows, uint32_t *dFlag, void *stream);
+int bfdevCondUnitPanel(void *V, uint64_t m, uint32_t p, uint64_t const *dRows, uint32_t dtype, void *stream);
+int bfdevCondPack(double *Bt, uint64_t n, uint32_t k, uint32_t c0, void const *T, uint32_t p, void const *gamma, uint32_t dtype, void *stream);
+int bfdevCondGram(double *G, double const *Bt, uint64_t n, uint32_t k, double const *dNoiseVar, void *stream);
+int bfdevCondCholesky(double *G, uint32_t k, BfCondStat *dStat, void *stream);
+int bfdevCondResidual(double *R, double *part, double const *Bt, uint64_t n, uint32_t k, double const *dY, void const *W, uint64_t ldw, uint32_t dtype,
+                      double const *E, uint64_t lde, uint32_t b, void *stream);
+int bfdevCondSolve(double const *L, uint32_t k, double *R, uint32_t b, void *stream);
+int bfdevCondDeviceSync(void);       /* drains every stream of the current device */
+int bfdevCondUpdate(void *Wout, double const *Bt, uint64_t n, uint32_t k, double const *alpha, void const *W, uint64_t ldw, uint32_t dtype, uint32_t b, void *stream);
+#ifdef __cplusplus
+}
+#endif
 
 #endif

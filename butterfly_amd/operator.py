@@ -184,6 +184,8 @@ class HipOperator:
 
     def close(self):
         if self._h:
+            for cond in list(getattr(self, "_conds", ())):      # conditioning objects reference the operator: they go first
+                cond.close()
             self._lib.bfhipFree(C.byref(self._h))
             self._h = C.c_void_p()
 
@@ -635,6 +637,13 @@ class HipOperator:
             check(self._lib.bfhipFillNormalDevice(self._ptr(tensor), tensor.numel(), int(first_idx), dt, int(seed), C.c_void_p(s.cuda_stream)))
         return tensor
 
+    def cov_condition(self, gamma_lam, row_perm, obs, noise_var=None):
+        """A CovCondition: the field z = P A diag(gamma_lam) w conditioned on noisy values at the output indices `obs`
+        (bfhipCovCondCreate: observed rows by adjoint panels, Gram matrix, Cholesky factor, all on the device).  gamma_lam /
+        row_perm are device tensors (or None) that the object references: keep them unchanged while it lives.  obs: distinct
+        indices < numRows (host); noise_var: their noise variances (host, >= 0; None: zeros)."""
+        return CovCondition(self, gamma_lam, row_perm, obs, noise_var)
+
     def set_profile_sampling(self, every):
         """Bracket one apply in `every` with events (bfhipSetProfileSampling)."""
         check(self._lib.bfhipSetProfileSampling(self._h, int(every)))
@@ -740,3 +749,109 @@ def lstsq_truncated(problems, device=-1, qr_min=None, gram_min=None, force_globa
         xo += me * n
         so += me
     return out
+
+
+class CovCondition:
+    """Kriging means and posterior samples given observations (bfhipCovCond*, include/bfhip.h "conditioning on
+    observations").  y: float64 [numObs] device tensor; blocks are contiguous [rows, nrhs] device tensors."""
+
+    def __init__(self, op, gamma_lam, row_perm, obs, noise_var=None):
+        import torch
+        import weakref
+        self._op, self._lib, self._h = op, op._lib, C.c_void_p()
+        self._gamma, self._perm = gamma_lam, row_perm          # referenced by the C object
+        obs = np.ascontiguousarray(np.asarray(obs, dtype=np.uint64))
+        nv = None if noise_var is None else np.ascontiguousarray(np.asarray(noise_var, dtype=np.float64))
+        if obs.ndim != 1 or (nv is not None and nv.shape != obs.shape):
+            raise ValueError("obs and noise_var are one-dimensional and of one length")
+        for name, t in (("gamma_lam", gamma_lam), ("row_perm", row_perm)):
+            if t is not None and t.device.type != "cuda":
+                raise ValueError(f"{name} must be a tensor on the operator's GPU (it is on {t.device})")
+        self._dev = HipOperator._cov_device(gamma_lam, row_perm)
+        s = torch.cuda.current_stream(self._dev)
+        check(self._lib.bfhipCovCondCreate(op.handle, HipOperator._ptr(gamma_lam), HipOperator._ptr(row_perm), obs.ctypes.data, obs.size,
+                                           nv.ctypes.data if nv is not None else None, C.byref(self._h), C.c_void_p(s.cuda_stream)))
+        self.num_obs = int(obs.size)
+        if not hasattr(op, "_conds"):
+            op._conds = weakref.WeakSet()
+        op._conds.add(self)
+
+    def close(self):
+        if self._h:
+            self._lib.bfhipCovCondFree(C.byref(self._h))
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def info(self):
+        i = _capi.BfhipCovCondInfo()
+        i.structSize = C.sizeof(i)
+        check(self._lib.bfhipCovCondGetInfo(self._h, C.byref(i)))
+        return i.as_dict()
+
+    def _stream(self):
+        import torch
+        return C.c_void_p(torch.cuda.current_stream(self._dev).cuda_stream)
+
+    def _check_y(self, y):
+        import torch
+        if y.dtype != torch.float64 or y.numel() != self.num_obs or not y.is_contiguous():
+            raise ValueError("y is a contiguous float64 [numObs] tensor")
+
+    def sample_block(self, y, W, eps=None, return_alpha=False):
+        """Z [numRows, nrhs] = P A Gamma (W + B^T alpha), alpha = (G + D)^-1 (y 1^T - B W - eps); eps float64 [numObs, nrhs]
+        or None (zeros).  With return_alpha: (Z, alpha [numObs, nrhs] float64)."""
+        import torch
+        self._check_y(y)
+        if W.dim() != 2 or not W.is_contiguous() or W.dtype != self._op._torch_dtype():
+            raise ValueError("W must be a contiguous [numCols, nrhs] tensor of the operator's element type")
+        q = W.shape[1]
+        if eps is not None and (eps.dtype != torch.float64 or tuple(eps.shape) != (self.num_obs, q) or not eps.is_contiguous()):
+            raise ValueError("eps is a contiguous float64 [numObs, nrhs] tensor")
+        z = torch.empty((self._op.shape[0], q), dtype=W.dtype, device=W.device)
+        alpha = torch.empty((self.num_obs, q), dtype=torch.float64, device=W.device) if return_alpha else None
+        ptr = HipOperator._ptr
+        check(self._lib.bfhipCovCondSampleBlockDevice(self._h, ptr(y), ptr(W), ptr(eps), q, ptr(z), ptr(alpha), self._stream()))
+        return (z, alpha) if return_alpha else z
+
+    def mean(self, y, return_alpha=False):
+        """The posterior mean [numRows] (W = 0, eps = 0).  With return_alpha: (mean, alpha [numObs])."""
+        import torch
+        self._check_y(y)
+        z = torch.empty(self._op.shape[0], dtype=self._op._torch_dtype(), device=y.device)
+        alpha = torch.empty(self.num_obs, dtype=torch.float64, device=y.device) if return_alpha else None
+        ptr = HipOperator._ptr
+        check(self._lib.bfhipCovCondMeanDevice(self._h, ptr(y), ptr(z), ptr(alpha), self._stream()))
+        return (z, alpha) if return_alpha else z
+
+    def draw(self, y, seed, noise_seed, first, nrhs):
+        """Posterior samples first .. first + nrhs - 1, [numRows, nrhs], from normals generated on the device:
+        W[j, s] = N(seed, (first + s) numCols + j), eps[a, s] = sqrt(noise_var[a]) N(noise_seed, (first + s) numObs + a)."""
+        import torch
+        self._check_y(y)
+        z = torch.empty((self._op.shape[0], int(nrhs)), dtype=self._op._torch_dtype(), device=y.device)
+        check(self._lib.bfhipCovCondDrawDevice(self._h, HipOperator._ptr(y), int(seed), int(noise_seed), int(first), int(nrhs),
+                                               HipOperator._ptr(z), self._stream()))
+        return z
+
+    def moments(self, y, seed, noise_seed, first, num, batch=64, sum=None, sumsq=None):
+        """Adds the sum and the sum of squares of posterior samples first .. first + num - 1, per point, to the float64
+        [numRows] tensors `sum` / `sumsq` (None: not formed; one is needed).  The samples are not stored."""
+        import torch
+        self._check_y(y)
+        for t in (sum, sumsq):
+            if t is not None and (t.dtype != torch.float64 or t.numel() != self._op.shape[0] or not t.is_contiguous()):
+                raise ValueError("moments are contiguous float64 [numRows] tensors")
+        ptr = HipOperator._ptr
+        check(self._lib.bfhipCovCondMomentsDevice(self._h, ptr(y), int(seed), int(noise_seed), int(first), int(num), int(batch),
+                                                  ptr(sum), ptr(sumsq), self._stream()))
+        return sum, sumsq

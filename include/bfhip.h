@@ -629,6 +629,72 @@ int bfhipCovDrawDevice(BfhipOperator *op, const void *dGammaLam, const uint64_t 
 int bfhipCovMomentsDevice(BfhipOperator *op, const void *dGammaLam, const uint64_t *dRowPerm, uint64_t seed, uint64_t firstSample,
                           uint64_t numSamples, uint32_t batch, double *dSum, double *dSumSq, void *stream);
 
+/* ---- conditioning on observations ------------------------------------------------ */
+/* Kriging means and posterior samples of the field z = P A GammaLam w given k <= BFHIP_COND_MAX_OBS noisy point values
+ * y_a = z[obs[a]] + e_a, e_a ~ N(0, noiseVar[a]), by a direct solve (Matheron's rule in coefficient space).  With
+ *   B [k x n]   the observed rows of P A GammaLam:  B[a, j] = A[i_a, j] * gamma[j],  dRowPerm[i_a] = obs[a]  (no perm: i_a = obs[a])
+ *   G = B B^T,  D = diag(noiseVar),  L L^T = G + D  (Cholesky, double)
+ * a block of q samples is
+ *   R  = y 1^T - B W - E            [k x q], double; y is shared by the columns
+ *   alpha = (G + D)^-1 R            two triangular solves with L
+ *   W' = W + B^T alpha              [n x q]: summed in double, rounded once to the operator's element type
+ *   Z  = P A GammaLam W'            bfhipCovSampleBlockDevice's sequence: one apply a pass
+ * Z[:, s] is a posterior sample when W[:, s] is standard normal and E[a, s] = sqrt(noiseVar[a]) N(0, 1); W = 0, E = 0 gives
+ * the posterior mean.
+ *
+ * Create: real operators with BFHIP_FLAG_ADJOINT.  `op`, dGammaLam (operator dtype, [numCols], NULL: ones) and dRowPerm
+ * (NULL: identity) are referenced, not copied: the caller keeps them alive and unchanged, as for every covariance entry.
+ * obs [numObs] (host) index the output z, distinct, < numRows; noiseVar [numObs] (host, >= 0, finite; NULL: zeros).  B^T is
+ * formed by bfhipApplyTransposeDevice on panels of <= 64 unit columns (the adjoint switch of the operator decides the
+ * kernels), widened exactly, multiplied by gamma in double and kept as an n x k double matrix, also for F32 operators.
+ * dRowPerm is inverted on the device and must hit every observed index exactly once (INVALID_ARGUMENTS otherwise).
+ * Everything a later call needs is allocated here for passes of 64 columns (the operator's covariance scratch and vector
+ * arena are grown to 64 columns too): a later call only enqueues work on `stream`.  Create is synchronous: it returns after
+ * the factorization.  A Cholesky pivot (the value under the root) that is <= 0 or not finite gives RUNTIME_ERROR naming
+ * the step (the index of the pivot); *out stays NULL and everything is released.
+ * Free: drains the whole device first (work enqueued on any stream may still read the object's matrices), then releases what
+ * the object holds.  Free it BEFORE its operator: every other entry reads the operator through the object, and an object whose
+ * operator is gone may only be freed.
+ *
+ * SampleBlock: dY [k] double, dW [n x nrhs] operator dtype, dEps [k x nrhs] double (NULL: zeros), dZ [m x nrhs] operator
+ * dtype, dAlpha [k x nrhs] double (NULL: not wanted); all device, row-major, densely packed.  nrhs > 64 runs in passes of 64
+ * columns.  Mean: the same with W = 0, E = 0, one column, bit for bit.
+ * Draw: W[j, s] = N(seed, (firstSample + s) n + j) (not scaled: the block sample applies GammaLam) and
+ * E[a, s] = sqrt(noiseVar[a]) N(noiseSeed, (firstSample + s) k + a), the product formed in double: bit for bit SampleBlock
+ * on the blocks bfhipFillNormalDevice makes with those indices.  The normals of a sample do not depend on the call or batch
+ * it is drawn in.
+ * Moments: bfhipCovMomentsDevice's loop over conditioned draws (batch 0 -> 64, at most 64), added to dSum / dSumSq.
+ *
+ * Errors, raised before the device is touched, in this order: INVALID_ARGUMENTS (NULL operator / object, output or dY;
+ * numObs == 0 or > BFHIP_COND_MAX_OBS; a repeated observed index; a noiseVar entry negative or not finite; nrhs == 0 or
+ * > 65535; both moment outputs NULL; batch > 64; numSamples == 0), OUT_OF_RANGE (an observed index >= numRows), TYPE_ERROR
+ * (a complex operator), INVALID_ARGUMENTS (no BFHIP_FLAG_ADJOINT; more than 65535 x 1024 columns, the per-pass kernels' grid),
+ * RUNTIME_ERROR (a BFHIP_FLAG_PLAN_ONLY operator).  The
+ * entries that take a BfhipCovCond read nothing through it before their own arguments are checked.  Sharded operators are
+ * not supported. */
+typedef struct BfhipCovCond BfhipCovCond;
+#define BFHIP_COND_MAX_OBS 2048u
+typedef struct BfhipCovCondInfo {
+  uint32_t structSize;            /* in: sizeof(BfhipCovCondInfo) */
+  uint32_t numObs;
+  double minPivot, maxPivot;      /* smallest and largest Cholesky pivot: the values under the roots */
+  uint64_t setupApplies;          /* adjoint panel applies of Create */
+  uint64_t factorBytes;           /* device bytes the object holds: B^T, L and the per-pass blocks */
+  double rowsSeconds, gramSeconds, factorSeconds;   /* setup phases: rows of B (inverse permutation, panels, pack), Gram, Cholesky */
+} BfhipCovCondInfo;
+
+int bfhipCovCondCreate(BfhipOperator *op, const void *dGammaLam, const uint64_t *dRowPerm, const uint64_t *obs, size_t numObs,
+                       const double *noiseVar, BfhipCovCond **out, void *stream);
+void bfhipCovCondFree(BfhipCovCond **c);
+int bfhipCovCondGetInfo(const BfhipCovCond *c, BfhipCovCondInfo *info);
+int bfhipCovCondSampleBlockDevice(BfhipCovCond *c, const double *dY, const void *dW, const double *dEps, size_t nrhs, void *dZ,
+                                  double *dAlpha, void *stream);
+int bfhipCovCondMeanDevice(BfhipCovCond *c, const double *dY, void *dMean, double *dAlpha, void *stream);
+int bfhipCovCondDrawDevice(BfhipCovCond *c, const double *dY, uint64_t seed, uint64_t noiseSeed, uint64_t firstSample, size_t nrhs,
+                           void *dZ, void *stream);
+int bfhipCovCondMomentsDevice(BfhipCovCond *c, const double *dY, uint64_t seed, uint64_t noiseSeed, uint64_t firstSample,
+                              uint64_t numSamples, uint32_t batch, double *dSum, double *dSumSq, void *stream);
+
 /* ---- plan inspection (no device needed) ---------------------------------- */
 /* The flattened per-stage layout, as the kernels see it.  Valid only for an
  * operator compiled with BFHIP_FLAG_PLAN_ONLY (the host mirrors are dropped
