@@ -147,6 +147,10 @@ class BfhipCovCondInfo(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_ if n != "structSize"}
 
 
+class BfhipCovCondLikOptions(C.Structure):
+    _fields_ = [("structSize", C.c_uint32), ("reserved", C.c_uint32), ("workspaceBytes", C.c_uint64)]
+
+
 def _pts(rec, spec):
     if spec[0] in ("node", "tnode"):
         rec["kind"], rec["first"], rec["count"] = (PTS_TREE if spec[0] == "node" else PTS_TREE_TGT), spec[1], spec[2] - spec[1]
@@ -526,6 +530,10 @@ def load():
     lib.bfhipCovCondDrawDevice.restype = C.c_int
     lib.bfhipCovCondMomentsDevice.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, vp, vp, vp]
     lib.bfhipCovCondMomentsDevice.restype = C.c_int
+    lib.bfhipCovCondLogLikelihoodDevice.argtypes = [vp, vp, vp, vp, vp, C.POINTER(BfhipCovCondLikOptions), vp]
+    lib.bfhipCovCondLogLikelihoodDevice.restype = C.c_int
+    lib.bfhipCovCondVarianceDevice.argtypes = [vp, vp, C.c_size_t, vp, vp, vp]
+    lib.bfhipCovCondVarianceDevice.restype = C.c_int
     lib.bfhipSetProfileSampling.argtypes = [vp, C.c_uint32]
     lib.bfhipSetProfileSampling.restype = C.c_int
     lib.bfhipPlanGetInfo.argtypes = [vp, C.POINTER(BfhipPlanInfo)]

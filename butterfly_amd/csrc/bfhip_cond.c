@@ -10,25 +10,8 @@
 #include <string.h>
 #include <time.h>
 
-#include "bfhip_operator.h"
-#include "../../include/bfhip.h"
+#include "bfhip_cond.h"
 #include "../../include/bfhip_abi.h"
-
-struct BfhipCovCond {
-  BfhipOperator *op;             /* referenced, like dGammaLam and dRowPerm */
-  void const *dGammaLam;
-  uint64_t const *dRowPerm;
-  int device;                    /* the operator's, kept so that Free reads nothing through op */
-  uint32_t k;
-  double *dBt;                   /* [n x k] */
-  double *dL;                    /* [k x k]: G + D, then L */
-  double *dNoiseVar, *dNoiseSd;  /* [k] each; NULL without noise */
-  double *dR;                    /* [k x 64]: R, solved in place into alpha */
-  double *dE;                    /* [k x 64]: the draw's noise block */
-  void *dWn;                     /* [n x 64], operator dtype: the draw's normals */
-  double *dPart;                 /* [chunks x k x 64]: partial sums of R */
-  BfhipCovCondInfo info;
-};
 
 static double nowSeconds(void) {
   struct timespec t;
@@ -45,6 +28,7 @@ static int obsKeyCmp(void const *a, void const *b) {
 static void condRelease(BfhipCovCond *c) {
   if (!c) return;
   bfdevFree(c->dBt); bfdevFree(c->dL); bfdevFree(c->dNoiseVar); bfdevFree(c->dNoiseSd); bfdevFree(c->dR); bfdevFree(c->dE); bfdevFree(c->dWn); bfdevFree(c->dPart);
+  condLikRelease(c);
   free(c);
 }
 

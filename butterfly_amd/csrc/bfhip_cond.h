@@ -1,0 +1,67 @@
+/* bfhip_cond.h -- struct BfhipCovCond, shared by the two host files that implement it: bfhip_cond.c (create, free, samples,
+ * moments) and bfhip_condlik.c (log-likelihood with gradients, kriging variances), and the device entry points of the latter
+ * (bfhip_condlik.hip).  Private to those files.
+ */
+#ifndef BFHIP_COND_H
+#define BFHIP_COND_H
+
+#include "bfhip_operator.h"
+#include "../../include/bfhip.h"
+
+struct BfhipCovCond {
+  BfhipOperator *op;             /* referenced, like dGammaLam and dRowPerm */
+  void const *dGammaLam;
+  uint64_t const *dRowPerm;
+  int device;                    /* the operator's, kept so that Free reads nothing through op */
+  uint32_t k;
+  double *dBt;                   /* [n x k] */
+  double *dL;                    /* [k x k]: G + D, then L */
+  double *dNoiseVar, *dNoiseSd;  /* [k] each; NULL without noise */
+  double *dR;                    /* [k x 64]: R, solved in place into alpha */
+  double *dE;                    /* [k x 64]: the draw's noise block */
+  void *dWn;                     /* [n x 64], operator dtype: the draw's normals */
+  double *dPart;                 /* [chunks x k x 64]: partial sums of R */
+  BfhipCovCondInfo info;
+  /* bfhip_condlik.c: allocated by the first likelihood / variance call, not counted in info.factorBytes */
+  double *dStrips;               /* [likSlots x k x 64]: the strips of the wide solve, one per workgroup */
+  uint64_t likSlots;             /* strips dStrips holds */
+  double *dLinv;                 /* [ceil(k / 64) x 64 x 64]: the inverses of the diagonal tiles of L */
+  double *dColSq;                /* [n + k]: ||L^-1 b_j||^2, then ||L^-1 e_a||^2 */
+  double *dVarBlk;               /* [n x 64]: a panel of rows of P A GammaLam, transposed (variance) */
+  double *dVarPart;              /* [chunks x 64] partial sums of its columns' squares, then [64] ||L^-1 Bt^T r||^2, then [k] zeros */
+};
+
+/* releases what bfhip_condlik.c allocated (the device is drained by the caller) */
+BF_HIDDEN void condLikRelease(BfhipCovCond *c);
+
+/* ---- the device entry points of bfhip_condlik.c, defined in bfhip_condlik.hip ---- */
+#define BF_LIK_STRIP 64u             /* columns of a strip of the wide solve */
+#define BF_LIK_NB 64u                /* its block rows: the diagonal tiles of L whose inverses are kept */
+enum { BF_LIK_SRC_BT_ROWS = 0, BF_LIK_SRC_IDENTITY = 1, BF_LIK_SRC_BLOCK = 2 };
+#ifdef __cplusplus
+extern "C" {
+#endif
+/* Linv [ceil(k / 64)][64][64] = the inverses of the diagonal tiles of L (identity beyond row k) */
+int bfdevLikInvDiag(double *Linv, double const *L, uint32_t k, void *stream);
+/* out[s] = sum_a X[a, s]^2, L X = S, for the numCols columns of S [k x numCols] (never stored):
+ *   BT_ROWS:  S[a, s] = src[s * k + a]  (src = Bt: its rows are the columns)
+ *   IDENTITY: S = I (numCols = k; src unused)
+ *   BLOCK:    S[a, s] = src[a * ld + s]
+ * strips [slots x k x 64] is scratch: workgroup g owns strips[g] and the columns of strips g, g + slots, ... of S */
+int bfdevLikStripSolve(double const *L, double const *Linv, uint32_t k, int kind, double const *src, uint64_t ld, uint64_t numCols, double *strips, uint64_t slots, double *out,
+                       void *stream);
+/* value[3] = { logLik, quad = sum_a y[a] alpha[a], logDet = 2 sum_a log L[a, a] } */
+int bfdevLikValue(double *value, double const *L, uint32_t k, double const *y, double const *alpha, void *stream);
+/* grad[j] = (sum_a Bt[j, a] alpha[a])^2 - colSq[j] */
+int bfdevLikGradGamma(double *grad, double const *Bt, uint64_t n, uint32_t k, double const *alpha, double const *colSq, void *stream);
+/* grad[a] = (alpha[a]^2 - colSq[a]) / 2 */
+int bfdevLikGradNoise(double *grad, double const *alpha, double const *colSq, uint32_t k, void *stream);
+/* part[c][s] = sum over the rows j of chunk c (BF_COND_CHUNK rows) of blk[j, s]^2, blk [n x p], p <= 64 */
+int bfdevVarPriorPart(double *part, double const *blk, uint64_t n, uint32_t p, void *stream);
+/* prior[s] = sum_c part[c][s] in chunk order (NULL: not stored), post[s] = that - solved[s] (NULL: not stored), s < p */
+int bfdevVarAssemble(double *prior, double *post, double const *part, uint64_t chunks, double const *solved, uint32_t p, void *stream);
+#ifdef __cplusplus
+}
+#endif
+
+#endif

@@ -1,6 +1,6 @@
 /* bfhip_operator.h -- struct BfhipOperator and the few helpers shared by the files that implement it: bfhip_api.c
  * (lifetime, compile, apply), bfhip_file.c (save / load), bfhip_shim.c (BfMat vtable), bfhip_inspect.c (plan inspection),
- * bfhip_cov.c (batched covariance sampling) and bfhip_cond.c (conditioning on observations).  Private to those six: every other file reads an operator through the bfhipOperator* accessors of bfhip_internal.h.
+ * bfhip_cov.c (batched covariance sampling) and bfhip_cond.c / bfhip_condlik.c (conditioning on observations; their object is bfhip_cond.h's).  Private to those seven: every other file reads an operator through the bfhipOperator* accessors of bfhip_internal.h.
  */
 #ifndef BFHIP_OPERATOR_H
 #define BFHIP_OPERATOR_H

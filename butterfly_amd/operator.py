@@ -855,3 +855,33 @@ class CovCondition:
         check(self._lib.bfhipCovCondMomentsDevice(self._h, ptr(y), int(seed), int(noise_seed), int(first), int(num), int(batch),
                                                   ptr(sum), ptr(sumsq), self._stream()))
         return sum, sumsq
+
+    def log_likelihood(self, y, grad_log_gamma=False, grad_noise=False, workspace_bytes=0):
+        """The log marginal likelihood of y ~ N(0, G + D): a float64 [3] device tensor (logLik, quad = y^T K^-1 y, logDet).
+        With a gradient asked for: (value, d logLik / d log gamma [numCols] or None, d logLik / d noise_var [numObs] or None),
+        float64 device tensors.  workspace_bytes: scratch of the wide triangular solve (0: the default, at most 256 MiB)."""
+        import torch
+        self._check_y(y)
+        value = torch.empty(3, dtype=torch.float64, device=y.device)
+        g = torch.empty(self._op.shape[1], dtype=torch.float64, device=y.device) if grad_log_gamma else None
+        h = torch.empty(self.num_obs, dtype=torch.float64, device=y.device) if grad_noise else None
+        opt = _capi.BfhipCovCondLikOptions()
+        opt.structSize, opt.workspaceBytes = C.sizeof(opt), int(workspace_bytes)
+        ptr = HipOperator._ptr
+        check(self._lib.bfhipCovCondLogLikelihoodDevice(self._h, ptr(y), ptr(value), ptr(g), ptr(h), C.byref(opt), self._stream()))
+        return (value, g, h) if (grad_log_gamma or grad_noise) else value
+
+    def variance(self, query, prior=False, post=True):
+        """Exact kriging variances of the latent field at the output indices `query` (distinct, any order): the posterior
+        variance [numQuery] float64; with prior=True (posterior, prior); with post=False the prior variance alone."""
+        import torch
+        q = np.ascontiguousarray(np.asarray(query, dtype=np.uint64))
+        if q.ndim != 1:
+            raise ValueError("query is one-dimensional")
+        if not (prior or post):
+            raise ValueError("one of prior / post is needed")
+        vpost = torch.empty(q.size, dtype=torch.float64, device=self._dev) if post else None
+        vprior = torch.empty(q.size, dtype=torch.float64, device=self._dev) if prior else None
+        ptr = HipOperator._ptr
+        check(self._lib.bfhipCovCondVarianceDevice(self._h, q.ctypes.data if q.size else None, q.size, ptr(vprior), ptr(vpost), self._stream()))
+        return (vpost, vprior) if (prior and post) else (vpost if post else vprior)

@@ -695,6 +695,52 @@ int bfhipCovCondDrawDevice(BfhipCovCond *c, const double *dY, uint64_t seed, uin
 int bfhipCovCondMomentsDevice(BfhipCovCond *c, const double *dY, uint64_t seed, uint64_t noiseSeed, uint64_t firstSample,
                               uint64_t numSamples, uint32_t batch, double *dSum, double *dSumSq, void *stream);
 
+/* Log marginal likelihood of the observations with its gradients, and exact kriging variances.  Both come from what the
+ * object already holds (B^T and L) and from one kernel: the column sums of squares of L^-1 S for a wide S that is never
+ * stored, a workgroup running the whole forward substitution for a strip of 64 columns in a k x 64 strip of scratch of its
+ * own.  Everything is double, for F32 operators too (rows widened exactly and multiplied by gamma in double, as in Create).
+ * One owner per output, every sum in a fixed order that depends on (n, k) alone, no atomics: a second call gives the same
+ * bits, whatever the workspace.
+ *
+ * LogLikelihood: y ~ N(0, K), K = G + D.  dValue[3] = { logLik, quad, logDet }.  The gradients are with respect to the
+ * log of every spectral weight and to every noise variance, at fixed observed rows: a caller with a parametric
+ * gamma(lambda; theta) finishes by the chain rule.  A zero weight gives exactly +0.  workspaceBytes (0: as many strips as
+ * S = B^T has, at most 256 MiB) sets how many workgroups run at once: workspaceBytes / (numObs * 64 * 8).  The first call
+ * and a call with a larger workspace allocate; that is not stream-ordered and drains `stream` first; a later call with the
+ * same or a smaller workspace only enqueues work.
+ * Variance: of the latent field at the output indices query[] (the noise of a new measurement is not added), in panels of
+ * <= 64 indices: bfhipApplyTransposeDevice on unit columns (the operator's adjoint switch decides the kernels, as in
+ * Create), the pack into double, B r and the strip solve.  The call uploads the indices, inverts dRowPerm for them on the
+ * device (a permutation that does not hit every query index exactly once: INVALID_ARGUMENTS) and returns after its work on
+ * `stream` is done.
+ * A re-fit at new weights means a new bfhipCovCondCreate: the stored rows are pre-scaled.
+ *
+ * Errors, raised before the device is touched, in this order: INVALID_ARGUMENTS (NULL object, dY or dValue; NULL query,
+ * numQuery == 0, both variance outputs NULL, a repeated query index; a structSize that is not the struct's; a non-zero
+ * workspaceBytes below one strip, numObs * 64 * 8), OUT_OF_RANGE (a query index >= numRows).  Nothing is read through the
+ * object before the checks that need only the arguments (all but the last two).  bfhipCovCondFree releases the workspaces;
+ * BfhipCovCondInfo.factorBytes keeps reporting what Create allocated. */
+typedef struct BfhipCovCondLikOptions {
+  uint32_t structSize;      /* = sizeof(BfhipCovCondLikOptions) */
+  uint32_t reserved;
+  uint64_t workspaceBytes;  /* strip scratch of the wide solve; 0 -> default */
+} BfhipCovCondLikOptions;
+
+/* dValue[3] (device, double) = { logLik, quad = y^T K^-1 y, logDet = 2 sum_a log L[a,a] },
+ * logLik = -quad/2 - logDet/2 - (k/2) log(2 pi).
+ * dGradLogGamma [numCols] (device, double, may be NULL): d logLik / d log gamma_j = u_j^2 - ||L^-1 b_j||^2,
+ *   u = Bt alpha, alpha = K^-1 y, b_j = row j of Bt (= gamma_j * Phi[obs rows, j]).
+ * dGradNoise [numObs] (device, double, may be NULL): d logLik / d noiseVar[a] = (alpha_a^2 - ||L^-1 e_a||^2) / 2. */
+int bfhipCovCondLogLikelihoodDevice(BfhipCovCond *c, const double *dY, double *dValue, double *dGradLogGamma,
+                                    double *dGradNoise, const BfhipCovCondLikOptions *opt, void *stream);
+
+/* query [numQuery] (HOST): indices of the output z, distinct, < numRows, any order.
+ * dPrior / dPost [numQuery] (device, double, either may be NULL, not both):
+ *   dPrior[t] = ||r||^2, dPost[t] = ||r||^2 - ||L^-1 (Bt^T r)||^2,  r = row of P A GammaLam at query[t]
+ * (latent field: the noise of a new measurement is not added). */
+int bfhipCovCondVarianceDevice(BfhipCovCond *c, const uint64_t *query, size_t numQuery, double *dPrior, double *dPost,
+                               void *stream);
+
 /* ---- plan inspection (no device needed) ---------------------------------- */
 /* The flattened per-stage layout, as the kernels see it.  Valid only for an
  * operator compiled with BFHIP_FLAG_PLAN_ONLY (the host mirrors are dropped
