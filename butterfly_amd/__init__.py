@@ -1,0 +1,1 @@
+from .cheb import ChebCovariance, cheb_eval, cheb_fit, matern_density, trimesh_lbo_fem  # noqa: F401

@@ -151,6 +151,17 @@ class BfhipCovCondLikOptions(C.Structure):
     _fields_ = [("structSize", C.c_uint32), ("reserved", C.c_uint32), ("workspaceBytes", C.c_uint64)]
 
 
+class BfhipChebCovInfo(C.Structure):
+    _fields_ = [("structSize", C.c_uint32), ("reserved", C.c_uint32), ("n", C.c_uint64), ("nnz", C.c_uint64), ("lamMax", C.c_double),
+                ("order", C.c_uint64), ("deviceBytes", C.c_uint64), ("workspaceBytes", C.c_uint64), ("errorEstimate", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n not in ("structSize", "reserved")}
+
+
+CHEB_DENSITY_FN = C.CFUNCTYPE(C.c_double, C.c_double, C.c_void_p)      # double (*f)(double, void *)
+
+
 def _pts(rec, spec):
     if spec[0] in ("node", "tnode"):
         rec["kind"], rec["first"], rec["count"] = (PTS_TREE if spec[0] == "node" else PTS_TREE_TGT), spec[1], spec[2] - spec[1]
@@ -534,6 +545,30 @@ def load():
     lib.bfhipCovCondLogLikelihoodDevice.restype = C.c_int
     lib.bfhipCovCondVarianceDevice.argtypes = [vp, vp, C.c_size_t, vp, vp, vp]
     lib.bfhipCovCondVarianceDevice.restype = C.c_int
+    lib.bfhipChebCovCreate.argtypes = [C.c_int, C.c_uint64, vp, vp, vp, vp, C.c_double, C.POINTER(vp)]
+    lib.bfhipChebCovCreate.restype = C.c_int
+    lib.bfhipChebCovSetCoefficients.argtypes = [vp, vp, C.c_size_t]
+    lib.bfhipChebCovSetCoefficients.restype = C.c_int
+    lib.bfhipChebCovFree.argtypes = [C.POINTER(vp)]
+    lib.bfhipChebCovFree.restype = None
+    lib.bfhipChebCovGetInfo.argtypes = [vp, C.POINTER(BfhipChebCovInfo)]
+    lib.bfhipChebCovGetInfo.restype = C.c_int
+    lib.bfhipChebFit.argtypes = [C.c_size_t, C.c_double, C.c_double, CHEB_DENSITY_FN, vp, vp]
+    lib.bfhipChebFit.restype = C.c_int
+    lib.bfhipChebEval.argtypes = [C.c_size_t, C.c_double, C.c_double, vp, C.c_double]
+    lib.bfhipChebEval.restype = C.c_double
+    lib.bfhipTrimeshLboFemCount.argtypes = [C.c_uint64, C.c_uint64, vp, C.POINTER(C.c_uint64)]
+    lib.bfhipTrimeshLboFemCount.restype = C.c_int
+    lib.bfhipTrimeshLboFem.argtypes = [C.c_uint64, vp, C.c_uint64, vp, vp, vp, vp, vp]
+    lib.bfhipTrimeshLboFem.restype = C.c_int
+    for name in ("Apply", "Sample", "Matvec"):
+        fn = getattr(lib, f"bfhipChebCov{name}BlockDevice")
+        fn.argtypes = [vp, vp, C.c_size_t, vp, vp]
+        fn.restype = C.c_int
+    lib.bfhipChebCovDrawDevice.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_size_t, vp, vp]
+    lib.bfhipChebCovDrawDevice.restype = C.c_int
+    lib.bfhipChebCovMomentsDevice.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, vp, vp, vp]
+    lib.bfhipChebCovMomentsDevice.restype = C.c_int
     lib.bfhipSetProfileSampling.argtypes = [vp, C.c_uint32]
     lib.bfhipSetProfileSampling.restype = C.c_int
     lib.bfhipPlanGetInfo.argtypes = [vp, C.POINTER(BfhipPlanInfo)]

@@ -1,0 +1,176 @@
+"""Matrix-free Chebyshev covariance on a sparse FEM operator (bfhipChebCov*, include/bfhip.h): from a triangle mesh
+(or any CSR stiffness matrix with a lumped mass) to samples z = D p(S) w and covariance products C v = D p(S)^2 D v on the
+GPU, with no eigenpairs and no butterfly.  Blocks are contiguous float64 [n, q] device tensors, in mesh order."""
+import ctypes as C
+
+import numpy as np
+
+from . import _capi
+from ._capi import check
+
+
+def cheb_fit(f, order, a, b):
+    """Coefficients of the Chebyshev interpolant of the Python callable f on [a, b] at `order` points (bfhipChebFit)."""
+    lib = _capi.load()
+    coef = np.zeros(int(order), dtype=np.float64)
+    cb = _capi.CHEB_DENSITY_FN(lambda x, _ctx: float(f(x)))
+    check(lib.bfhipChebFit(int(order), float(a), float(b), cb, None, coef.ctypes.data))
+    return coef
+
+
+def cheb_eval(coef, a, b, x):
+    """The interpolant with coefficients `coef` on [a, b] at x, scalar or array (bfhipChebEval: Clenshaw)."""
+    lib = _capi.load()
+    coef = np.ascontiguousarray(coef, dtype=np.float64)
+    xs = np.asarray(x, dtype=np.float64)
+    out = np.array([lib.bfhipChebEval(coef.size, float(a), float(b), coef.ctypes.data, float(v)) for v in xs.ravel()])
+    return float(out[0]) if xs.ndim == 0 else out.reshape(xs.shape)
+
+
+def matern_density(kappa, nu):
+    """The spectral density of the reference's covariance examples: exp(-kappa lambda^2) for nu == 0 (squared
+    exponential), else the Matern density |1 + kappa^2 lambda|^(-nu / 4 - 1 / 2), normalised to 1 at lambda = 0."""
+    kappa, nu = float(kappa), float(nu)
+    if nu == 0:
+        return lambda lam: np.exp(-kappa * lam * lam)
+    return lambda lam: np.abs(1 + kappa * kappa * lam) ** (-nu / 4 - 0.5)
+
+
+def trimesh_lbo_fem(verts, faces):
+    """(rowptr, colind, L, mass_lumped) of the P1 stiffness matrix of a triangle mesh (bfhipTrimeshLboFem), host arrays."""
+    lib = _capi.load()
+    verts = np.ascontiguousarray(verts, dtype=np.float64)
+    faces = np.ascontiguousarray(faces, dtype=np.uint64)
+    if verts.ndim != 2 or verts.shape[1] != 3 or faces.ndim != 2 or faces.shape[1] != 3:
+        raise ValueError("verts is [numVerts, 3], faces is [numFaces, 3]")
+    nv, nf = verts.shape[0], faces.shape[0]
+    nnz = C.c_uint64()
+    check(lib.bfhipTrimeshLboFemCount(nv, nf, faces.ctypes.data, C.byref(nnz)))
+    rowptr = np.zeros(nv + 1, dtype=np.uint64)
+    colind = np.zeros(nnz.value, dtype=np.uint64)
+    data = np.zeros(nnz.value, dtype=np.float64)
+    mass = np.zeros(nv, dtype=np.float64)
+    check(lib.bfhipTrimeshLboFem(nv, verts.ctypes.data, nf, faces.ctypes.data, rowptr.ctypes.data, colind.ctypes.data, data.ctypes.data,
+                                 mass.ctypes.data))
+    return rowptr, colind, data, mass
+
+
+class ChebCovariance:
+    """S = D L D on the device and a Chebyshev polynomial p of it (include/bfhip.h, "matrix-free Chebyshev covariance")."""
+
+    def __init__(self, handle, n, device):
+        self._lib, self._h, self.n, self._dev = _capi.load(), handle, int(n), int(device)
+
+    @classmethod
+    def from_csr(cls, rowptr, colind, data, mass_lumped=None, lam_max=None, device=0):
+        """rowptr [n + 1], colind, data: host CSR arrays of the stiffness matrix L; mass_lumped [n] positive (None: ones);
+        lam_max: an upper bound of the spectrum of S (None: the Gershgorin bound)."""
+        lib = _capi.load()
+        rowptr = np.ascontiguousarray(rowptr, dtype=np.uint64)
+        colind = np.ascontiguousarray(colind, dtype=np.uint64)
+        data = np.ascontiguousarray(data, dtype=np.float64)
+        if rowptr.ndim != 1 or rowptr.size < 1 or colind.ndim != 1 or data.shape != colind.shape or (rowptr.size > 1 and int(rowptr[-1]) != colind.size):
+            raise ValueError("rowptr [n + 1], colind [nnz], data [nnz] with rowptr[-1] == nnz")
+        n = rowptr.size - 1
+        mass = None if mass_lumped is None else np.ascontiguousarray(mass_lumped, dtype=np.float64)
+        if mass is not None and mass.shape != (n,):
+            raise ValueError("mass_lumped is [n]")
+        h = C.c_void_p()
+        check(lib.bfhipChebCovCreate(int(device), n, rowptr.ctypes.data, colind.ctypes.data, data.ctypes.data,
+                                     mass.ctypes.data if mass is not None else None, 0.0 if lam_max is None else float(lam_max), C.byref(h)))
+        return cls(h, n, device)
+
+    @classmethod
+    def from_trimesh(cls, verts, faces, lam_max=None, device=0):
+        rowptr, colind, data, mass = trimesh_lbo_fem(verts, faces)
+        return cls.from_csr(rowptr, colind, data, mass, lam_max=lam_max, device=device)
+
+    def close(self):
+        if self._h:
+            self._lib.bfhipChebCovFree(C.byref(self._h))
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def handle(self):
+        return self._h
+
+    def info(self):
+        i = _capi.BfhipChebCovInfo()
+        i.structSize = C.sizeof(i)
+        check(self._lib.bfhipChebCovGetInfo(self._h, C.byref(i)))
+        return i.as_dict()
+
+    def set_coefficients(self, coef):
+        coef = np.ascontiguousarray(coef, dtype=np.float64)
+        if coef.ndim != 1:
+            raise ValueError("coef is one-dimensional")
+        check(self._lib.bfhipChebCovSetCoefficients(self._h, coef.ctypes.data, coef.size))
+
+    def set_density(self, f, order):
+        """Fit the spectral density f (a Python callable of lambda) on [0, lamMax] at `order` points in numpy and set it.
+        Returns the coefficients."""
+        order = int(order)
+        lam_max = self.info()["lamMax"]
+        j = np.arange(order)
+        x = np.sin(np.pi * (2 * j + 1 - order) / (2 * order))
+        y = np.array([float(f(lam_max * (t + 1) / 2)) for t in x])
+        k = np.arange(order)[:, None]
+        coef = (2.0 / order) * (np.cos(k * np.arccos(x)[None, :]) @ y)
+        coef[0] /= 2
+        self.set_coefficients(coef)
+        return coef
+
+    # ---- device entries: contiguous float64 [n, q] tensors on the object's GPU ----
+    def _stream(self):
+        import torch
+        return C.c_void_p(torch.cuda.current_stream(self._dev).cuda_stream)
+
+    def _block(self, t, name):
+        import torch
+        if t.dim() != 2 or t.shape[0] != self.n or t.dtype != torch.float64 or not t.is_contiguous() or t.device.type != "cuda":
+            raise ValueError(f"{name} must be a contiguous float64 [n, q] tensor on the GPU")
+        return t
+
+    def _product(self, fn, x):
+        import torch
+        x = self._block(x, "the input")
+        z = torch.empty_like(x)
+        check(fn(self._h, C.c_void_p(x.data_ptr()), x.shape[1], C.c_void_p(z.data_ptr()), self._stream()))
+        return z
+
+    def apply_block_device(self, W):
+        """X = p(S) W (bfhipChebCovApplyBlockDevice)."""
+        return self._product(self._lib.bfhipChebCovApplyBlockDevice, W)
+
+    def sample_block_device(self, W):
+        """Z = D p(S) W (bfhipChebCovSampleBlockDevice): a sample per standard normal column of W."""
+        return self._product(self._lib.bfhipChebCovSampleBlockDevice, W)
+
+    def matvec_block_device(self, V):
+        """Z = D p(S) p(S) D V (bfhipChebCovMatvecBlockDevice): the covariance applied to the columns of V."""
+        return self._product(self._lib.bfhipChebCovMatvecBlockDevice, V)
+
+    def draw_device(self, seed, first, q):
+        """Z [n, q]: samples first .. first + q - 1 from normals generated on the device (bfhipChebCovDrawDevice):
+        w_s[j] = N(seed, (first + s) * n + j), whatever the split into calls."""
+        import torch
+        z = torch.empty((self.n, int(q)), dtype=torch.float64, device=torch.device("cuda", self._dev))
+        check(self._lib.bfhipChebCovDrawDevice(self._h, int(seed), int(first), int(q), C.c_void_p(z.data_ptr()), self._stream()))
+        return z
+
+    def moments_device(self, seed, first, num, batch=64, sum=None, sumsq=None):
+        """Adds the sum and the sum of squares over samples first .. first + num - 1, per point, to the float64 [n] tensors
+        `sum` / `sumsq` (bfhipChebCovMomentsDevice; None: that moment is not formed).  Returns (sum, sumsq)."""
+        import torch
+        for t in (sum, sumsq):
+            if t is not None and (t.dtype != torch.float64 or t.numel() != self.n or not t.is_contiguous()):
+                raise ValueError("moments are contiguous float64 [n] tensors")
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        check(self._lib.bfhipChebCovMomentsDevice(self._h, int(seed), int(first), int(num), int(batch), ptr(sum), ptr(sumsq), self._stream()))
+        return sum, sumsq

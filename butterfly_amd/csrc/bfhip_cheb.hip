@@ -1,0 +1,111 @@
+// bfhip_cheb.hip -- the one kernel of the matrix-free Chebyshev covariance (bfhipChebCov*, include/bfhip.h; host side:
+// bfhip_cheb.c).  Not a stage kernel: there is no plan and no arena, the operator is a CSR matrix S in HBM and the
+// vectors are row-major n x q blocks of doubles, densely packed.
+//
+// One launch is one degree of Clenshaw's recurrence for all q columns:
+//   out[i, :] = ck * (wScale ? wScale[i] : 1) * w[i, :] + alpha * sum_j S[i][j] * b1[col_j, :] + beta * b1[i, :] - b2[i, :]
+// (then * outScale[i] at the last step).  The gather needs every row of b1, hence one launch per degree; w and b2 are
+// streamed, out is written over b2.  Per degree the kernel moves three block streams (w, b2, out), the matrix once and
+// the gathered rows of b1 (about 7 per row on a triangle mesh, found in L2 when the mesh is ordered with any locality).
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "bfhip_internal.h"
+#include "../../include/bfhip_abi.h"
+
+#define BF_CHEB_MAX_GRID (1u << 20)     // workgroups per launch; the rest is walked with a grid stride
+#ifndef BF_CHEB_GATHERS
+#define BF_CHEB_GATHERS 8               // gathered rows in flight per output row, a power of two (tools/cheb_cov_rate.py)
+#endif
+static_assert(BF_CHEB_GATHERS >= 1 && BF_CHEB_GATHERS <= 64 && (BF_CHEB_GATHERS & (BF_CHEB_GATHERS - 1)) == 0, "BF_CHEB_GATHERS: a power of two <= 64");
+
+// Threads: lanes = min(64, next power of two >= q) neighbouring lanes own row i, so a wavefront covers 64 / lanes rows and
+// a workgroup of 256 covers 256 / lanes.  A lane owns columns lane, lane + lanes, ... : at q <= 64 one column, beyond
+// that one column of every panel of 64; at q = 64 a wavefront reads a gathered row as one contiguous 512-byte request.
+//
+// The sum of a row runs over its nonzeros in CSR order by fma, in groups of BF_CHEB_GATHERS whose gathers are all issued
+// before the first is used; the rest of the step is the same sequence for every q -- column j of a result does not
+// depend on q, on the panel or on the launch.  One owner per output element and out == b2 only through the element's
+// owner: no atomics, no LDS memory.  All indices are 64 bits.
+//
+// The (col, value) pairs of a group are loaded once per row: lane t of the row's lanes loads pair t (two vector memory
+// instructions instead of 2 x BF_CHEB_GATHERS; a lane past the row's end re-reads its last pair, so every load stays
+// inside the row) and every lane reads pair t from lane t by a shuffle.  Measured at q = 64 on a mesh of 7 nonzeros per
+// row: with every lane loading the pairs for itself a row costs 30 vector memory instructions and
+// the kernel moved 2.5 TB/s of algorithmic bytes, with 4 or with 8 gathers in flight; with 16 instructions per row 3.0.
+// Rows owned by fewer lanes than a group has pairs (q <= BF_CHEB_GATHERS / 2) load them per lane: there a wavefront
+// covers 16 rows or more and the instructions are shared by all of them.
+__global__ __launch_bounds__(256) void bfChebStepKernel(BfChebStep a, uint32_t lanesLog2) {
+  constexpr int G = BF_CHEB_GATHERS;
+  uint32_t const lanes = 1u << lanesLog2, lane = threadIdx.x & (lanes - 1), rowsPerWg = 256u >> lanesLog2;
+  uint64_t const q = a.q;
+  bool const shared = lanes >= (uint32_t)G;
+  for (uint64_t i = (uint64_t)blockIdx.x * rowsPerWg + (threadIdx.x >> lanesLog2); i < a.n; i += (uint64_t)gridDim.x * rowsPerWg) {
+    uint64_t const beg = a.rowptr[i], end = a.rowptr[i + 1];
+    double const ws = a.wScale ? a.wScale[i] : 1.0, os = a.outScale ? a.outScale[i] : 1.0;
+    // every lane of the row walks every panel (the shuffles below need them all); one past the block's width computes nothing
+    for (uint64_t c0 = 0; c0 < q; c0 += lanes) {
+      uint64_t const c = c0 + lane;
+      bool const live = c < q;
+      // the three streamed values first: their loads are in flight while the row's pairs and the gather arrive
+      double r = 0, own = 0, old = 0;
+      if (live) {
+        r = a.w[i * q + c];
+        if (a.b1) own = a.b1[i * q + c];
+        if (a.b2) old = a.b2[i * q + c];
+      }
+      if (a.wScale) r *= ws;
+      r *= a.ck;
+      if (a.b1) {
+        double acc = 0;
+        for (uint64_t j = beg; j < end; j += G) {
+          double v[G];
+          uint32_t col[G];
+          if (shared) {
+            uint64_t const mine = j + (lane & (G - 1)) < end ? j + (lane & (G - 1)) : end - 1;
+            double const pv = a.val[mine];
+            uint32_t const pc = a.colind[mine];
+#pragma unroll
+            for (int t = 0; t < G; ++t) {
+              v[t] = __shfl(pv, t, (int)lanes);
+              col[t] = __shfl(pc, t, (int)lanes);
+            }
+          } else {
+#pragma unroll
+            for (int t = 0; t < G; ++t) {
+              uint64_t const jj = j + t < end ? j + t : end - 1;
+              v[t] = a.val[jj];
+              col[t] = a.colind[jj];
+            }
+          }
+          if (live) {
+            double x[G];
+#pragma unroll
+            for (int t = 0; t < G; ++t) x[t] = j + t < end ? a.b1[(uint64_t)col[t] * q + c] : 0.0;
+#pragma unroll
+            for (int t = 0; t < G; ++t)
+              if (j + t < end) acc = fma(v[t], x[t], acc);
+          }
+        }
+        r = fma(a.alpha, acc, r);
+        r = fma(a.beta, own, r);
+      }
+      if (a.b2) r -= old;
+      if (a.outScale) r *= os;
+      if (live) a.out[i * q + c] = r;
+    }
+  }
+}
+
+int bfdevChebStep(BfChebStep const *s, void *stream) {
+  if (!s->n || !s->q) return 0;
+  uint32_t lg = 0;
+  while ((1u << lg) < s->q && lg < 6) ++lg;
+  uint64_t const perWg = 256u >> lg, need = (s->n + perWg - 1) / perWg;
+  dim3 const grid((uint32_t)(need < BF_CHEB_MAX_GRID ? need : BF_CHEB_MAX_GRID)), block(256);
+  hipLaunchKernelGGL(bfChebStepKernel, grid, block, 0, (hipStream_t)stream, *s, lg);
+  hipError_t const e = hipGetLastError();
+  if (e == hipSuccess) return 0;
+  return bfhipFail(e == hipErrorOutOfMemory ? BFABI_ERROR_MEMORY_ERROR : BFABI_ERROR_RUNTIME_ERROR, "Chebyshev step launch: %s", hipGetErrorString(e));
+}

@@ -464,6 +464,23 @@ int bfdevCovDrawFill(void *w, void const *gamma, uint64_t cols, uint32_t nrhs, u
 /* sum[perm ? perm[i] : i] += sum_q t[i, q], sumSq[...] += sum_q t[i, q]^2 over the b columns of t (rows x b); either output may be NULL */
 int bfdevCovMoments(void const *t, uint64_t rows, uint32_t b, uint32_t dtype, uint64_t const *perm, double *sum, double *sumSq, void *stream);
 
+/* one Clenshaw step of the Chebyshev covariance (bfhip_cheb.hip; driven by bfhip_cheb.c): on blocks of n x q doubles
+ *   out[i, :] = ck * (wScale ? wScale[i] : 1) * w[i, :] + alpha * sum_j S[i][j] * b1[col_j, :] + beta * b1[i, :] - b2[i, :]
+ * and then out[i, :] *= outScale[i] when outScale is given.  b1 == NULL drops the two b1 terms, b2 == NULL the last one;
+ * out may be b2 (a row's owner is the only reader of its b2 row) and nothing else it reads.  S is CSR on the device:
+ * rowptr uint64 [n + 1], colind uint32, values double */
+typedef struct BfChebStep {
+  uint64_t const *rowptr;
+  uint32_t const *colind;
+  double const *val;
+  uint64_t n;
+  uint32_t q;
+  double const *w, *wScale, *b1, *b2, *outScale;
+  double *out;
+  double ck, alpha, beta;
+} BfChebStep;
+int bfdevChebStep(BfChebStep const *s, void *stream);
+
 /* device-resident GMRES building blocks (bfhip_gmres.hip; complex128; bfhip_gmres.c drives them).
  * Vectors are n x nrhs row-major; reductions are per RHS column, two-stage and
  * in fixed order (per-block partials, then a tree over the partials), so a

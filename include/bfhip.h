@@ -741,6 +741,86 @@ int bfhipCovCondLogLikelihoodDevice(BfhipCovCond *c, const double *dY, double *d
 int bfhipCovCondVarianceDevice(BfhipCovCond *c, const uint64_t *query, size_t numQuery, double *dPrior, double *dPost,
                                void *stream);
 
+/* ---- matrix-free Chebyshev covariance on a sparse operator ------------------------ */
+/* examples/covariance/cheb_cov.c reaches the covariance of the butterfly route without eigenpairs: with the P1 stiffness
+ * matrix L of a triangle mesh and its lumped mass, S = D L D, D = diag(massLumped)^-1/2, and a Chebyshev interpolant p of
+ * the spectral density on [0, lamMax],
+ *   chebmul:     x = p(S) w
+ *   sample_z:    z = D p(S) w
+ *   cov_matvec:  z = D p(S) p(S) D v
+ * These entries keep S (CSR, folded once on the host) and everything else on one device and work on blocks: vectors are
+ * row-major n x q, densely packed, double; the output is in mesh order (no permutation).  Real double precision only.
+ *
+ * The device evaluates p(S) W by Clenshaw's recurrence, one launch of one kernel per degree (bfChebStepKernel):
+ *   b_k = c_k W + (4 / lamMax) S b_{k+1} - 2 b_{k+1} - b_{k+2},  k = order - 1 .. 1,  b_order = b_{order+1} = 0
+ *   x   = c_0 W + (2 / lamMax) S b_1 - b_1 - b_2
+ * with b_k written over b_{k+2}; D on either side is fused into the first / last step.  A row's sum runs over its
+ * nonzeros in CSR order by fma and every output row has one owner: column j of a result does not depend on q, and a
+ * second call gives the same bits.  Workspace: two blocks of n x q doubles (apply, sample), three (matvec, draw,
+ * moments); it grows on demand, which is not stream-ordered and drains `stream` first; a call that grows nothing only
+ * enqueues work and can be captured in a graph.
+ *
+ * Create (host CSR arrays of the symmetric positive semidefinite L; massLumped [n] positive, NULL: ones): the scaling is
+ * folded as S[i][j] = (d[i] * L[i][j]) * d[j], d[i] = 1 / sqrt(massLumped[i]).  lamMax must be an UPPER BOUND of the
+ * spectrum of S (an underestimate makes the recurrence diverge); lamMax <= 0 asks for the Gershgorin bound
+ * max_i sum_j |S[i][j]|, summed in row order.  Empty rows are legal.  Raised before the device is touched, all
+ * INVALID_ARGUMENTS: a NULL pointer, n == 0 or n >= 2^32, rowptr[0] != 0, rowptr not monotone, a column index >= n, a
+ * massLumped entry that is not finite or <= 0, lamMax NaN or infinite (and a bound that is not positive: S == 0).
+ * SetCoefficients: coef[0 .. order - 1] of p in the Chebyshev basis of [0, lamMax] (bfhipChebFit with a = 0, b = lamMax),
+ * copied; order >= 1, every coefficient finite.  GetInfo: errorEstimate = |coef[order - 1]| (bfChebStdGetErrorEstimate).
+ * Free drains the device, then releases everything. */
+typedef struct BfhipChebCov BfhipChebCov;
+typedef struct BfhipChebCovInfo {
+  uint32_t structSize;            /* in: sizeof(BfhipChebCovInfo) */
+  uint32_t reserved;
+  uint64_t n, nnz;
+  double lamMax;                  /* as given, or the Gershgorin bound */
+  uint64_t order;                 /* 0 before bfhipChebCovSetCoefficients */
+  uint64_t deviceBytes;           /* rowptr, colind, values of S and d */
+  uint64_t workspaceBytes;        /* the blocks of the recurrence, as grown so far */
+  double errorEstimate;           /* |coef[order - 1]|; 0 before bfhipChebCovSetCoefficients */
+} BfhipChebCovInfo;
+
+int bfhipChebCovCreate(int device, uint64_t n, const uint64_t *rowptr, const uint64_t *colind, const double *data,
+                       const double *massLumped, double lamMax, BfhipChebCov **out);
+int bfhipChebCovSetCoefficients(BfhipChebCov *c, const double *coef, size_t order);
+void bfhipChebCovFree(BfhipChebCov **c);
+int bfhipChebCovGetInfo(const BfhipChebCov *c, BfhipChebCovInfo *info);
+
+/* Chebyshev interpolation on [a, b], host only: coef[0 .. order - 1] of the interpolant of f at the `order` points
+ * t_i = (b - a) (x_i + 1) / 2 + a, x_i = sin(pi (2 i + 1 - order) / (2 order)):  c_0 = (1 / order) sum_j y_j,
+ * c_k = (2 / order) sum_j T_k(x_j) y_j.  Eval: Clenshaw at (2 x - a - b) / (b - a); NaN for order == 0 or NULL coef.
+ * INVALID_ARGUMENTS: order == 0, NULL f or coef, a or b not finite, a == b. */
+int bfhipChebFit(size_t order, double a, double b, double (*f)(double, void *), void *ctx, double *coef);
+double bfhipChebEval(size_t order, double a, double b, const double *coef, double x);
+
+/* The P1 (cotangent) stiffness matrix of a triangle mesh in CSR and its lumped mass, host only.  verts [numVerts x 3],
+ * faces [numFaces x 3] vertex indices.  A row holds the vertex's neighbours in increasing order with the vertex itself
+ * inserted at its place (the layout of bfTrimeshGetLboFemDiscretization): nnz = numVerts + 2 x (number of edges), which
+ * Count reports.  L[i][j] = -(cot a + cot b) / 2 over the angles opposite edge (i, j), L[i][i] = -sum_j L[i][j];
+ * massLumped[i] = a third of the area of the triangles at i.  rowptr [numVerts + 1], colind and Ldata [nnz], massLumped
+ * [numVerts] (may be NULL).  INVALID_ARGUMENTS: a NULL pointer, numVerts == 0, a face index >= numVerts, a face with a
+ * repeated vertex or zero area. */
+int bfhipTrimeshLboFemCount(uint64_t numVerts, uint64_t numFaces, const uint64_t *faces, uint64_t *nnz);
+int bfhipTrimeshLboFem(uint64_t numVerts, const double *verts, uint64_t numFaces, const uint64_t *faces, uint64_t *rowptr,
+                       uint64_t *colind, double *Ldata, double *massLumped);
+
+/* The products, on blocks of 1 <= q <= 65535 columns; device pointers on the object's GPU; dW, dV, dX, dZ are n x q
+ * doubles.  In-place use (output == input) is refused: the input is read at every step.
+ *   Apply:   X = p(S) W                    Sample: Z = D p(S) W                    Matvec: Z = D p(S) p(S) D V
+ *   Draw:    the sample of W[j, s] = N(seed, (firstSample + s) n + j), the normal stream of bfhipCovDrawDevice
+ *   Moments: samples firstSample .. firstSample + numSamples - 1, `batch` at a time (0 -> 64, at most 64), never stored:
+ *            their sums and sums of squares per point are ADDED to dSum / dSumSq (double [n], either may be NULL, not both)
+ *            as bfhipCovMomentsDevice does.
+ * Errors, raised before the device is touched: INVALID_ARGUMENTS (a NULL object, input or output; q == 0 or > 65535;
+ * output == input; batch > 64; numSamples == 0; both moment outputs NULL; no coefficients set). */
+int bfhipChebCovApplyBlockDevice(BfhipChebCov *c, const double *dW, size_t q, double *dX, void *stream);
+int bfhipChebCovSampleBlockDevice(BfhipChebCov *c, const double *dW, size_t q, double *dZ, void *stream);
+int bfhipChebCovMatvecBlockDevice(BfhipChebCov *c, const double *dV, size_t q, double *dZ, void *stream);
+int bfhipChebCovDrawDevice(BfhipChebCov *c, uint64_t seed, uint64_t firstSample, size_t q, double *dZ, void *stream);
+int bfhipChebCovMomentsDevice(BfhipChebCov *c, uint64_t seed, uint64_t firstSample, uint64_t numSamples, uint32_t batch,
+                              double *dSum, double *dSumSq, void *stream);
+
 /* ---- plan inspection (no device needed) ---------------------------------- */
 /* The flattened per-stage layout, as the kernels see it.  Valid only for an
  * operator compiled with BFHIP_FLAG_PLAN_ONLY (the host mirrors are dropped
