@@ -80,13 +80,16 @@ __device__ __forceinline__ double2 bfHelm2Sp(double k, double dx, double dy, dou
 }
 
 // Kapur-Rokhlin end-point corrections of the punctured trapezoid rule for a log-singular kernel
-// (Kapur & Rokhlin, SIAM J. Numer. Anal. 34, 1997); the values are the tables the reference applies
-// (src/quadrature.c:12-41, order 10 as printed there).
+// (Kapur & Rokhlin, SIAM J. Numer. Anal. 34, 1997, Table 6).  Orders 2 and 6 are the tables the reference
+// applies (src/quadrature.c:12-26).  Order 10 departs from it on purpose: the reference's printing
+// (src/quadrature.c:29-40) lost the decimal exponents of the paper's table, sums to -4.48 instead of 1/2 and
+// converges at order 1; the values here are the paper's (sum 0.49999999999982, observed order 10: DESIGN.md
+// section 23).
 __constant__ double bfKrWeights[18] = {
     1.825748064736159, -1.325748064736159,
     4.967362978287758, -16.20501504859126, 25.85153761832639, -22.22599466791883, 9.930104998037539, -1.817995878141594,
-    7.832432020568779, -4.565161670374749, 1.452168846354677, -2.901348302886379, 3.870862162579900, -3.523821383570681,
-    2.172421547519342, -8.707796087382991, 2.053584266072635, -2.166984103403823};
+    7.832432020568779e+00, -4.565161670374749e+01, 1.452168846354677e+02, -2.901348302886379e+02, 3.870862162579900e+02,
+    -3.523821383570681e+02, 2.172421547519342e+02, -8.707796087382991e+01, 2.053584266072635e+01, -2.166984103403823e+00};
 
 struct EvalEnvDev {
   double const *pts, *normals, *colWeights, *tpts, *tnormals;

@@ -104,7 +104,13 @@ typedef struct BfhipHelm2Problem {
    * helm2_bie.c:113): entry (i, j) of the layer potential is multiplied by 1 + w_KR[d-1] when the
    * points are d = 1..krOrder apart along the curve (cyclic distance of their ORIGINAL indices).
    * Folded into the dense near-field leaves; the build fails if such a pair lies in a butterflied
-   * block.  krOrder: 0 (none), 2, 6 or 10; origIndex[t] = original index of tree position t. */
+   * block.  krOrder: 0 (none), 2, 6 or 10; origIndex[t] = original index of tree position t.
+   * Orders 2 and 6 use the reference's tables.  Order 10 departs from the reference ON PURPOSE: its table
+   * (src/quadrature.c:29-40) lost the decimal exponents of Kapur & Rokhlin's Table 6 (SIAM J. Numer. Anal. 34,
+   * 1997) -- it sums to -4.48 where every KR table sums to 1/2, and on the unit circle (k = 2, n = 48, 96, 192) its
+   * error is 8.2e-1, 4.2e-1, 1.7e-1 (order 1).  The table here is the paper's: sum 0.49999999999982, errors
+   * 1.5e-5, 1.3e-8, 9.4e-12 (order 10).  An operator built with krOrder = 10 therefore differs from what the
+   * reference's bfQuadKrApplyCorrectionTree(10) makes, in the first digit. */
   const uint64_t *origIndex; /* [numPoints] or NULL (needed iff krOrder != 0) */
   uint32_t krOrder;
   uint32_t outDtype;         /* storage of the operator built: 0 = BFHIP_C128 (the default), or BFHIP_C64 -- the operator

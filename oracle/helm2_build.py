@@ -123,12 +123,15 @@ def reexpansion_matrix(k, src_orig, src_equiv, tgt):
     return lstsq_truncated(z_equiv, z_orig)
 
 
-# Kapur-Rokhlin weights as the reference tabulates them (src/quadrature.c:12-41)
+# Kapur-Rokhlin weights (Kapur & Rokhlin, SIAM J. Numer. Anal. 34, 1997, Table 6).  Orders 2 and 6 as the reference
+# tabulates them (src/quadrature.c:12-26); order 10 with the decimal exponents that the reference's printing
+# (src/quadrature.c:29-40) lost -- as printed there the table sums to -4.48, not 1/2, and converges at order 1
+# (DESIGN.md section 23).
 KR_WEIGHTS = {
     2: [1.825748064736159, -1.325748064736159],
     6: [4.967362978287758, -16.20501504859126, 25.85153761832639, -22.22599466791883, 9.930104998037539, -1.817995878141594],
-    10: [7.832432020568779, -4.565161670374749, 1.452168846354677, -2.901348302886379, 3.870862162579900, -3.523821383570681,
-         2.172421547519342, -8.707796087382991, 2.053584266072635, -2.166984103403823],
+    10: [7.832432020568779e+00, -4.565161670374749e+01, 1.452168846354677e+02, -2.901348302886379e+02, 3.870862162579900e+02,
+         -3.523821383570681e+02, 2.172421547519342e+02, -8.707796087382991e+01, 2.053584266072635e+01, -2.166984103403823e+00],
 }
 
 
