@@ -65,11 +65,8 @@ static void freeDevicePlan(BfhipOperator *op) {
 void bfhipFree(BfhipOperator **pop) {
   if (!pop || !*pop) return;
   BfhipOperator *op = *pop;
-  int prev = -1;
-  if (!(op->flags & BFHIP_FLAG_PLAN_ONLY)) {
-    bfdevGetDevice(&prev);
-    bfdevSetDevice(op->device);
-  }
+  BfDevScope ds;
+  bfDevEnter(&ds, (op->flags & BFHIP_FLAG_PLAN_ONLY) ? -1 : op->device);      /* a plan-only operator never touched a device */
   if (op->extractRelease) op->extractRelease(op->extract);
   if (op->evStart && op->evStop) for (uint64_t s = 0; s < BF_EV_POOL * op->plan.numStages; ++s) { bfdevEventDestroy(op->evStart[s]); bfdevEventDestroy(op->evStop[s]); }
   free(op->evStart); free(op->evStop); free(op->stageMs); free(op->stageLaunches);
@@ -89,10 +86,9 @@ void bfhipFree(BfhipOperator **pop) {
   bfPlanFree(&op->tplan);
   if (op->ir) { bfIrFree(op->ir); free(op->ir); }
   if (op->irT) { bfIrFree(op->irT); free(op->irT); }
-  int const touchedDevice = !(op->flags & BFHIP_FLAG_PLAN_ONLY);
   free(op);
   *pop = NULL;
-  if (touchedDevice && prev >= 0) bfdevSetDevice(prev);
+  bfDevLeave(&ds);
 }
 
 static int uploadArray(void **d, void const *h, size_t bytes, uint64_t *meta) {
@@ -428,7 +424,7 @@ int bfhipCompileIrFill(BfIr *ir, BfhipOptions const *opts, BfFillFn fill, void *
   BfhipOperator *op = calloc(1, sizeof *op);
   if (!op) { bfIrFree(ir); return bfhipFail(BFABI_ERROR_MEMORY_ERROR, "host OOM"); }
   int rc = 0;
-  int prevDev = -1;
+  BfDevScope ds = {0};
   int const planOnly = (o.flags & BFHIP_FLAG_PLAN_ONLY) != 0;
   BfIr irT;                      /* the transposed expression of a packed adjoint plan: released under `done` on every path */
   memset(&irT, 0, sizeof irT);
@@ -441,9 +437,8 @@ int bfhipCompileIrFill(BfIr *ir, BfhipOptions const *opts, BfFillFn fill, void *
   }
 #endif
   if (!planOnly) {
-    bfdevGetDevice(&prevDev);
-    if ((rc = bfdevSetDevice(o.device))) goto done;
-    if ((rc = bfdevGetDevice(&op->device))) goto done;
+    if ((rc = bfDevEnter(&ds, o.device))) goto done;
+    if ((rc = bfdevGetDevice(&op->device))) goto done;      /* o.device may be -1: the operator lives on the current device */
   }
   op->srcDtype = ir->dtype;
   BfPlanOptions po;
@@ -548,8 +543,9 @@ int bfhipCompileIrFill(BfIr *ir, BfhipOptions const *opts, BfFillFn fill, void *
 done:
   bfIrFree(ir);
   bfIrFree(&irT);
-  if (rc) { bfhipFree(&op); if (prevDev >= 0) bfdevSetDevice(prevDev); return rc; }
-  if (prevDev >= 0 && o.device >= 0) bfdevSetDevice(prevDev);
+  if (rc) bfhipFree(&op);
+  bfDevLeave(&ds);
+  if (rc) return rc;
   *out = op;
   return 0;
 }
@@ -689,14 +685,31 @@ void stageLaunchArgs(BfhipOperator const *op, BfPlan const *plan, BfStage const 
   a->exactComplex = (op->flags & BFHIP_FLAG_EXACT_COMPLEX) != 0; a->rhsBlocks = plan == &op->plan ? op->rhsBlocks : op->adjointRhsBlocks;      /* the adjoint's plans (shared or packed) have a switch of their own */
 }
 
+/* the reduce passes of a stage, BF_REDUCE_BATCH to a launch; `allIntoY`: every destination is y (the one-launch flow path) */
+static int launchReduces(BfhipOperator *op, BfPlan const *plan, BfStage const *st, uint32_t nrhs, void *dY, int allIntoY, void *stream) {
+  for (uint64_t r0 = 0; r0 < st->numReduce; r0 += BF_REDUCE_BATCH) {
+    BfReduceArgs ra[BF_REDUCE_BATCH];
+    uint32_t const cnt = (uint32_t)(st->numReduce - r0 < BF_REDUCE_BATCH ? st->numReduce - r0 : BF_REDUCE_BATCH);
+    for (uint32_t r = 0; r < cnt; ++r) {
+      BfReduce *rd = &st->reduce[r0 + r];
+      ra[r].rowInterval = rd->dRowInterval; ra[r].ivBegin = rd->dIvBegin; ra[r].srcBias = rd->dSrcBias;
+      ra[r].numRows = rd->numRows; ra[r].temp = op->dTemp; ra[r].nrhs = nrhs; ra[r].dtype = plan->dtype;
+      ra[r].longLists = rd->maxSrc >= 64; ra[r].pad = 0;
+      ra[r].dest = allIntoY || rd->destSpace == BF_SPACE_Y ? dY : (void *)((char *)op->dTemp + rd->destOff * nrhs * plan->elemSize);
+    }
+    int const rc = bfdevLaunchReduce(ra, cnt, stream);
+    if (rc) return rc;
+  }
+  return 0;
+}
+
 static int runPlan(BfhipOperator *op, BfPlan *plan, void const *dX, size_t nrhs, void *dY, void *stream) {
   if (!op || !dX || !dY) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL argument");
   if (nrhs == 0 || nrhs > 0xffffu) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "nrhs out of range");
   if (op->flags & BFHIP_FLAG_PLAN_ONLY) return bfhipFail(BFABI_ERROR_RUNTIME_ERROR, "operator was compiled with BFHIP_FLAG_PLAN_ONLY: no device operator exists");
-  int rc = 0;
-  int prev = -1;
-  bfdevGetDevice(&prev);
-  if (prev != op->device && (rc = bfdevSetDevice(op->device))) return rc;
+  int rc;
+  BfDevScope ds;
+  if ((rc = bfDevEnter(&ds, op->device))) return rc;
   if (op->tempRhs < nrhs) {
     /* growing the vector arena is not stream-ordered: drain first */
     if ((rc = bfdevSync(stream))) goto out;
@@ -739,21 +752,8 @@ static int runPlan(BfhipOperator *op, BfPlan *plan, void const *dX, size_t nrhs,
         free(c); free(w);
       }
     }
-    for (uint64_t s = 0; s < plan->numStages; ++s) {
-      BfStage *st = &plan->stages[s];
-      for (uint64_t r0 = 0; r0 < st->numReduce; r0 += 16) {
-        BfReduceArgs ra[16];
-        uint32_t const cnt = (uint32_t)(st->numReduce - r0 < 16 ? st->numReduce - r0 : 16);
-        for (uint32_t r = 0; r < cnt; ++r) {
-          BfReduce *rd = &st->reduce[r0 + r];
-          ra[r].rowInterval = rd->dRowInterval; ra[r].ivBegin = rd->dIvBegin; ra[r].srcBias = rd->dSrcBias;
-          ra[r].numRows = rd->numRows; ra[r].temp = op->dTemp; ra[r].nrhs = (uint32_t)nrhs; ra[r].dtype = plan->dtype;
-          ra[r].longLists = rd->maxSrc >= 64; ra[r].pad = 0;
-          ra[r].dest = dY;          /* flowOk: every reduce sums into y */
-        }
-        if ((rc = bfdevLaunchReduce(ra, cnt, stream))) goto out;
-      }
-    }
+    for (uint64_t s = 0; s < plan->numStages; ++s)
+      if ((rc = launchReduces(op, plan, &plan->stages[s], (uint32_t)nrhs, dY, 1, stream))) goto out;      /* flowOk: every reduce sums into y */
     if (prof) { ++op->evIssued; op->lastNrhs = (uint32_t)nrhs; }
     goto out;
   }
@@ -767,23 +767,11 @@ static int runPlan(BfhipOperator *op, BfPlan *plan, void const *dX, size_t nrhs,
     if (prof && (rc = bfdevEventRecord(op->evStart[evBase + s], stream))) goto out;
     if ((rc = bfdevLaunchStage(&a, stream))) goto out;
     if (prof && (rc = bfdevEventRecord(op->evStop[evBase + s], stream))) goto out;
-    for (uint64_t r0 = 0; r0 < st->numReduce; r0 += 16) {
-      BfReduceArgs ra[16];
-      uint32_t const cnt = (uint32_t)(st->numReduce - r0 < 16 ? st->numReduce - r0 : 16);
-      for (uint32_t r = 0; r < cnt; ++r) {
-        BfReduce *rd = &st->reduce[r0 + r];
-        ra[r].rowInterval = rd->dRowInterval; ra[r].ivBegin = rd->dIvBegin; ra[r].srcBias = rd->dSrcBias;
-        ra[r].numRows = rd->numRows; ra[r].temp = op->dTemp; ra[r].nrhs = (uint32_t)nrhs; ra[r].dtype = plan->dtype;
-        ra[r].longLists = rd->maxSrc >= 64; ra[r].pad = 0;
-        ra[r].dest = rd->destSpace == BF_SPACE_Y ? dY : (void *)((char *)op->dTemp + rd->destOff * nrhs * plan->elemSize);
-      }
-      if ((rc = bfdevLaunchReduce(ra, cnt, stream))) goto out;
-    }
+    if ((rc = launchReduces(op, plan, st, (uint32_t)nrhs, dY, 0, stream))) goto out;
   }
   if (prof) { ++op->evIssued; op->lastNrhs = (uint32_t)nrhs; }
 out:
-  /* every path hands the caller's device back */
-  if (prev >= 0 && prev != op->device) bfdevSetDevice(prev);
+  bfDevLeave(&ds);      /* every path hands the caller's device back */
   return rc;
 }
 
@@ -793,12 +781,12 @@ int bfhipOperatorReserveRhs(BfhipOperator *op, uint32_t nrhs) {
   if (!op || !nrhs) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL operator / zero nrhs");
   if (op->flags & BFHIP_FLAG_PLAN_ONLY) return bfhipFail(BFABI_ERROR_RUNTIME_ERROR, "operator was compiled with BFHIP_FLAG_PLAN_ONLY: no device operator exists");
   if (op->tempRhs >= nrhs) return 0;
-  int prev = -1, rc;
-  bfdevGetDevice(&prev);
-  if (prev != op->device && (rc = bfdevSetDevice(op->device))) return rc;
+  int rc;
+  BfDevScope ds;
+  if ((rc = bfDevEnter(&ds, op->device))) return rc;
   rc = bfdevSync(NULL);
   if (!rc) rc = ensureTemp(op, nrhs);
-  if (prev >= 0 && prev != op->device) bfdevSetDevice(prev);
+  bfDevLeave(&ds);
   return rc;
 }
 
@@ -812,11 +800,11 @@ int bfhipFlowStatus(BfhipOperator *op, uint32_t *enabled, uint32_t *waitGaveUp) 
     *waitGaveUp = 0;
     if (op->flow && !(op->flags & BFHIP_FLAG_PLAN_ONLY)) {
       uint32_t two[2] = {0, 0};
-      int prev = -1, rc;
-      bfdevGetDevice(&prev);
-      if (prev != op->device && (rc = bfdevSetDevice(op->device))) return rc;
+      int rc;
+      BfDevScope ds;
+      if ((rc = bfDevEnter(&ds, op->device))) return rc;
       rc = bfdevMemcpyD2H(two, op->dFlowCounters, sizeof two);       /* [0] ticket queue, [1] error flag */
-      if (prev >= 0 && prev != op->device) bfdevSetDevice(prev);
+      bfDevLeave(&ds);
       if (rc) return rc;
       *waitGaveUp = two[1];
     }
@@ -853,36 +841,31 @@ int covScratch(BfhipOperator *op, size_t nrhs, void *stream) {
 
 int bfhipCovSampleDevice(BfhipOperator *op, void const *dGammaLam, uint64_t const *dRowPerm, void const *dW, void *dZ, void *stream) {
   if (!op || !dW || !dZ) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL argument");
-  if (bfDtypeComplex(op->plan.dtype)) return bfhipFail(BFABI_ERROR_TYPE_ERROR, "covariance products are defined for real operators (not complex128 / complex64)");
-  if (op->flags & BFHIP_FLAG_PLAN_ONLY) return bfhipFail(BFABI_ERROR_RUNTIME_ERROR, "operator was compiled with BFHIP_FLAG_PLAN_ONLY: no device operator exists");
-  int rc, prev = -1;
-  bfdevGetDevice(&prev);
-  if (prev != op->device && (rc = bfdevSetDevice(op->device))) return rc;
-  uint64_t const m = op->plan.numRows, n = op->plan.numCols, big = m > n ? m : n;
-  size_t const es = op->plan.elemSize;
+  int rc;
+  BfDevScope ds;
+  if ((rc = bfCovCheckOperator(op, 0)) || (rc = bfDevEnter(&ds, op->device))) return rc;
+  uint64_t const m = op->plan.numRows, n = op->plan.numCols;
   if ((rc = covScratch(op, 1, stream))) goto out;
-  char *t0 = op->dCov, *t1 = (char *)op->dCov + big * es;
+  char *t0, *t1;
+  bfCovHalves(op, 1, &t0, &t1);
   void const *xin = dW;
   if (dGammaLam) { if ((rc = bfdevScalePermute(t0, dW, dGammaLam, 1, NULL, n, op->plan.dtype, stream))) goto out; xin = t0; }
   if ((rc = runPlan(op, &op->plan, xin, 1, dRowPerm ? (void *)t1 : dZ, stream))) goto out;
   if (dRowPerm) rc = bfdevScalePermute(dZ, t1, NULL, 0, dRowPerm, m, op->plan.dtype, stream);
 out:
-  if (prev >= 0 && prev != op->device) bfdevSetDevice(prev);
+  bfDevLeave(&ds);
   return rc;
 }
 
 int bfhipCovMatvecDevice(BfhipOperator *op, void const *dGammaLam, uint64_t const *dRowPerm, uint64_t const *dRevRowPerm, void const *dV, void *dZ, void *stream) {
   if (!op || !dV || !dZ) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL argument");
-  if (bfDtypeComplex(op->plan.dtype)) return bfhipFail(BFABI_ERROR_TYPE_ERROR, "covariance products are defined for real operators (not complex128 / complex64)");
-  if (!op->hasTplan) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "operator was not compiled with BFHIP_FLAG_ADJOINT");
-  if (op->flags & BFHIP_FLAG_PLAN_ONLY) return bfhipFail(BFABI_ERROR_RUNTIME_ERROR, "operator was compiled with BFHIP_FLAG_PLAN_ONLY: no device operator exists");
-  int rc, prev = -1;
-  bfdevGetDevice(&prev);
-  if (prev != op->device && (rc = bfdevSetDevice(op->device))) return rc;
-  uint64_t const m = op->plan.numRows, n = op->plan.numCols, big = m > n ? m : n;
-  size_t const es = op->plan.elemSize;
+  int rc;
+  BfDevScope ds;
+  if ((rc = bfCovCheckOperator(op, 1)) || (rc = bfDevEnter(&ds, op->device))) return rc;
+  uint64_t const m = op->plan.numRows, n = op->plan.numCols;
   if ((rc = covScratch(op, 1, stream))) goto out;
-  char *t0 = op->dCov, *t1 = (char *)op->dCov + big * es;
+  char *t0, *t1;
+  bfCovHalves(op, 1, &t0, &t1);
   void const *vin = dV;
   if (dRevRowPerm) { if ((rc = bfdevScalePermute(t0, dV, NULL, 0, dRevRowPerm, m, op->plan.dtype, stream))) goto out; vin = t0; }
   if ((rc = runPlan(op, &op->tplan, vin, 1, t1, stream))) goto out;                 /* tmp2 = Phi^T v */
@@ -890,7 +873,7 @@ int bfhipCovMatvecDevice(BfhipOperator *op, void const *dGammaLam, uint64_t cons
   if ((rc = runPlan(op, &op->plan, t1, 1, dRowPerm ? (void *)t0 : dZ, stream))) goto out;
   if (dRowPerm) rc = bfdevScalePermute(dZ, t0, NULL, 0, dRowPerm, m, op->plan.dtype, stream);
 out:
-  if (prev >= 0 && prev != op->device) bfdevSetDevice(prev);
+  bfDevLeave(&ds);
   return rc;
 }
 
@@ -1033,9 +1016,8 @@ int applyHost(BfhipOperator *op, int transpose, void const *X, size_t ldx, size_
   if (nrhs == 0 || ldx < nrhs || ldy < nrhs) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "bad nrhs / leading dimension");
   if (op->flags & BFHIP_FLAG_PLAN_ONLY) return bfhipFail(BFABI_ERROR_RUNTIME_ERROR, "operator was compiled with BFHIP_FLAG_PLAN_ONLY: no device operator exists");
   int rc;
-  int prev = -1;
-  bfdevGetDevice(&prev);
-  if ((rc = bfdevSetDevice(op->device))) return rc;
+  BfDevScope ds;
+  if ((rc = bfDevEnter(&ds, op->device))) return rc;
   uint64_t width = nrhs;
   if ((rc = hostApplyWidth(op, transpose, X, Y, nrhs, &width))) goto out;
   if (width >= nrhs) rc = applyHostPiece(op, transpose, X, ldx, nrhs, Y, ldy);
@@ -1048,7 +1030,7 @@ int applyHost(BfhipOperator *op, int transpose, void const *X, size_t ldx, size_
     }
   }
 out:
-  if (prev >= 0 && prev != op->device) bfdevSetDevice(prev);
+  bfDevLeave(&ds);
   return rc;
 }
 

@@ -13,19 +13,12 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <time.h>
 
 #include "bfhip_internal.h"
 #include "../../include/bfhip_abi.h"
 #include "../../include/bfhip_build.h"
 
 #define DEFAULT_WORKSPACE ((uint64_t)8 << 30)
-
-static double nowSeconds(void) {
-  struct timespec ts;
-  clock_gettime(CLOCK_MONOTONIC, &ts);
-  return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
-}
 
 static BfBuildPts toPts(BfhipPointSet const *p) {
   BfBuildPts q;
@@ -226,8 +219,8 @@ static int lstsqSolve(BfLsJob const *jobs, uint64_t count, BfLstSqOpts const *op
   uint64_t *qrOf = malloc((count + 1) * sizeof *qrOf);          /* least-squares problem of the k-th QR problem */
   uint32_t *qrRank = malloc((count + 1) * sizeof *qrRank);
   uint64_t nq = 0;
-  double tp = profile ? nowSeconds() : 0;
-#define BF_PHASE(name) do { if (profile) { double const t = nowSeconds(); fprintf(stderr, "[build] %-12s %.3f s\n", name, t - tp); tp = t; } } while (0)
+  double tp = profile ? bfNowSeconds() : 0;
+#define BF_PHASE(name) do { if (profile) { double const t = bfNowSeconds(); fprintf(stderr, "[build] %-12s %.3f s\n", name, t - tp); tp = t; } } while (0)
   if (!probs || !g1 || !g2 || !qr || !qrOf || !qrRank) { rc = bfhipFail(BFABI_ERROR_MEMORY_ERROR, "host OOM (least squares)"); goto done; }
   for (uint64_t i = 0; i < count; ++i) {
     BfLsJob const *J = &jobs[i];
@@ -303,7 +296,7 @@ static int buildBatch(BfhipHelm2Problem const *prob, uint64_t const *idx, uint64
     wsOff[i] = wsElems;
     if (r->kind == BFHIP_LEAF_REEXP) { wsElems += reexpWs(r, qrMin).total; ++numReexp; }
   }
-  double const tAlloc = nowSeconds();
+  double const tAlloc = bfNowSeconds();
   if ((rc = batchBufsReserve(bufs, storeElems, wsElems))) goto done;
   *dStore = bufs->store; dWs = bufs->ws;
   char *store = (char *)*dStore, *ws = (char *)dWs;
@@ -342,10 +335,10 @@ static int buildBatch(BfhipHelm2Problem const *prob, uint64_t const *idx, uint64
   }
   char const *penv = getenv("BFHIP_JACOBI_PROFILE");
   int const profile = penv && penv[0] == '1';
-  if (profile) fprintf(stderr, "[build] %-12s %.3f s\n", "alloc + lists", nowSeconds() - tAlloc);
-  double const tEval = nowSeconds();
+  if (profile) fprintf(stderr, "[build] %-12s %.3f s\n", "alloc + lists", bfNowSeconds() - tAlloc);
+  double const tEval = bfNowSeconds();
   if ((rc = bfdevBuildEval(mats, prefix, nm, env))) goto done;
-  if (profile) fprintf(stderr, "[build] %-12s %.3f s\n", "kernel eval", nowSeconds() - tEval);
+  if (profile) fprintf(stderr, "[build] %-12s %.3f s\n", "kernel eval", bfNowSeconds() - tEval);
   if ((rc = lstsqSolve(jobs, np, NULL, st, NULL, NULL, profile))) goto done;
   st->numBatches += 1;
 done:
@@ -484,7 +477,7 @@ static int buildAndPack(BuildCtx *ctx) {
 
   char const *penv = getenv("BFHIP_JACOBI_PROFILE");
   int const profile = penv && penv[0] == '1';
-  double tph = nowSeconds();
+  double tph = bfNowSeconds();
   if ((rc = envUpload(prob, &dev))) goto done;
 
   /* default workspace: half of what is free once the arena is allocated, at least 8 GiB asked for --
@@ -529,9 +522,9 @@ static int buildAndPack(BuildCtx *ctx) {
     }
     if (!nb) break;
     void *dStore = NULL;
-    if (profile) { double const t = nowSeconds(); fprintf(stderr, "[build] host before batch %.3f s\n", t - tph); tph = t; }
+    if (profile) { double const t = bfNowSeconds(); fprintf(stderr, "[build] host before batch %.3f s\n", t - tph); tph = t; }
     if ((rc = buildBatch(prob, batch, nb, &dev.env, &bufs, &dStore, storeOff, st))) break;
-    if (profile) { double const t = nowSeconds(); fprintf(stderr, "[build] batch total %.3f s (%llu recipes)\n", t - tph, (unsigned long long)nb); tph = t; }
+    if (profile) { double const t = bfNowSeconds(); fprintf(stderr, "[build] batch total %.3f s (%llu recipes)\n", t - tph, (unsigned long long)nb); tph = t; }
     for (uint32_t t = 0; t < ctx->numTargets && !rc; ++t) {
       PackTarget const *T = &ctx->tgt[t];
       uint64_t packCount = 0, q = 0;
@@ -553,7 +546,7 @@ static int buildAndPack(BuildCtx *ctx) {
       rc = bfdevBuildPack(T->dArena, T->dtype, dStore, pack, q);
       free(pack); pack = NULL;
     }
-    if (profile) { double const t = nowSeconds(); fprintf(stderr, "[build] pack + free  %.3f s\n", t - tph); tph = t; }
+    if (profile) { double const t = bfNowSeconds(); fprintf(stderr, "[build] pack + free  %.3f s\n", t - tph); tph = t; }
   }
   /* every KR pair must have been met exactly once by a dense near-field leaf; a pair inside a
    * butterflied block cannot be corrected through the values */
@@ -641,10 +634,10 @@ int bfhipBuildHelm2(BfhipDesc const *desc, BfhipHelm2Problem const *prob, BfhipO
   ctx.prob = prob; ctx.stats = &local; ctx.wanted = 1;
   BfIr ir;
   if ((rc = bfIrFromDesc(desc, &ir))) return rc;
-  double const t0 = nowSeconds();
+  double const t0 = bfNowSeconds();
   rc = bfhipCompileIrFill(&ir, opts, fillArena, &ctx, out);
   buildCtxFree(&ctx);
-  local.seconds = nowSeconds() - t0;
+  local.seconds = bfNowSeconds() - t0;
   int const rc2 = finishBuild(rc, &local, stats);
   if (rc2 && !rc) bfhipFree(out);
   return rc2;
@@ -671,13 +664,13 @@ int bfhipBuildHelm2Pair(BfhipDesc const *desc, BfhipHelm2Problem const *prob, Bf
   BuildCtx ctx;
   memset(&ctx, 0, sizeof ctx);
   ctx.prob = prob; ctx.stats = &local; ctx.wanted = 2;
-  double const t0 = nowSeconds();
+  double const t0 = bfNowSeconds();
   /* the first compile only collects its pieces (fillArena); its arena is written while the second one fills its own */
   BfIr ir;
   if (!(rc = bfIrFromDesc(desc, &ir))) rc = bfhipCompileIrFill(&ir, opts, fillArena, &ctx, out);
   if (!rc && !(rc = bfIrFromDesc(desc, &ir))) rc = bfhipCompileIrFill(&ir, &low, fillArena, &ctx, outLow);
   buildCtxFree(&ctx);
-  local.seconds = nowSeconds() - t0;
+  local.seconds = bfNowSeconds() - t0;
   rc = finishBuild(rc, &local, stats);
   if (rc) { bfhipFree(out); bfhipFree(outLow); }      /* neither is returned: the first one's arena may be unwritten */
   return rc;
@@ -688,9 +681,8 @@ int bfhipHelm2BuildLeaf(BfhipHelm2Problem const *prob, uint64_t recipeIndex, int
   if (rc) return rc;
   if (!out || recipeIndex >= prob->numRecipes) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "bad recipe index / NULL output");
   if ((rc = checkRecipe(prob, recipeIndex))) return rc;
-  int prev = -1;
-  bfdevGetDevice(&prev);
-  if ((rc = bfdevSetDevice(device))) return rc;
+  BfDevScope ds;
+  if ((rc = bfDevEnter(&ds, device))) return rc;
   BfhipHelm2Recipe const *r = &prob->recipes[recipeIndex];
   uint64_t const m = leafRows(r), n = r->src.count;
   void *dStore = NULL;
@@ -712,7 +704,7 @@ int bfhipHelm2BuildLeaf(BfhipHelm2Problem const *prob, uint64_t recipeIndex, int
       for (uint64_t j = 0; j < n; ++j) { o[2 * (i * n + j)] = tmp[2 * (j * m + i)]; o[2 * (i * n + j) + 1] = tmp[2 * (j * m + i) + 1]; }
   }
   batchBufsFree(&bufs); envFree(&dev); free(tmp);
-  if (prev >= 0) bfdevSetDevice(prev);
+  bfDevLeave(&ds);
   return rc;
 }
 
@@ -720,16 +712,15 @@ int bfhipHelm2DenseApplyDevice(BfhipHelm2Problem const *prob, int device, void c
   int rc = checkProblem(prob);
   if (rc) return rc;
   if (!dX || !dY) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL argument");
-  int prev = -1;
-  bfdevGetDevice(&prev);
-  if ((rc = bfdevSetDevice(device))) return rc;
+  BfDevScope ds;
+  if ((rc = bfDevEnter(&ds, device))) return rc;
   DevEnv dev;
   rc = envUpload(prob, &dev);
   if (!rc && prob->tgtPoints && prob->layerPot == BFHIP_LAYER_POTENTIAL_PV_NORMAL_DERIV_SINGLE && !prob->tgtNormals)
     rc = bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "S' on a separate target tree needs tgtNormals");
   if (!rc) rc = bfdevHelm2Dense(&dev.env, leafPotCode(prob->layerPot), prob->numPoints, prob->tgtPoints ? prob->numTgtPoints : 0, dX, dY, stream);
   envFree(&dev);
-  if (prev >= 0) bfdevSetDevice(prev);
+  bfDevLeave(&ds);
   return rc;
 }
 
@@ -737,9 +728,8 @@ int bfhipHelm2DenseApply(BfhipHelm2Problem const *prob, int device, void const *
   int rc = checkProblem(prob);
   if (rc) return rc;
   if (!X || !Y) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL argument");
-  int prev = -1;
-  bfdevGetDevice(&prev);
-  if ((rc = bfdevSetDevice(device))) return rc;
+  BfDevScope ds;
+  if ((rc = bfDevEnter(&ds, device))) return rc;
   void *dX = NULL, *dY = NULL;
   uint64_t const m = prob->tgtPoints ? prob->numTgtPoints : prob->numPoints;
   rc = bfdevMalloc(&dX, (size_t)(prob->numPoints ? prob->numPoints : 1) * 16);
@@ -748,7 +738,7 @@ int bfhipHelm2DenseApply(BfhipHelm2Problem const *prob, int device, void const *
   if (!rc) rc = bfhipHelm2DenseApplyDevice(prob, -1, dX, dY, NULL);
   if (!rc) rc = bfdevMemcpyD2H(Y, dY, (size_t)m * 16);
   bfdevFree(dX); bfdevFree(dY);
-  if (prev >= 0) bfdevSetDevice(prev);
+  bfDevLeave(&ds);
   return rc;
 }
 
@@ -826,9 +816,8 @@ int bfhipLstSqTruncated(uint64_t count, uint32_t const *shapes, void const *A, v
   }
   uint64_t const *tot = off + 8 * count;
   void *dA = NULL, *dB = NULL, *dX = NULL, *dV = NULL, *dQ = NULL, *dT = NULL, *dS = NULL, *dI = NULL;
-  int prev = -1;
-  bfdevGetDevice(&prev);
-  if ((rc = bfdevSetDevice(device))) goto done;
+  BfDevScope ds = {0};
+  if ((rc = bfDevEnter(&ds, device))) goto done;
   if ((rc = bfdevMalloc(&dA, tot[OA] * 16)) || (rc = bfdevMalloc(&dB, tot[OB] * 16)) || (rc = bfdevMalloc(&dX, tot[OX] * 16)) ||
       (rc = bfdevMalloc(&dV, tot[OV] * 16)) || (rc = bfdevMalloc(&dQ, (tot[OQ] ? tot[OQ] : 1) * 16)) || (rc = bfdevMalloc(&dT, tot[OT] * 16)) ||
       (rc = bfdevMalloc(&dS, tot[OS] * 8)) || (rc = bfdevMalloc(&dI, tot[OI] * 4)))
@@ -871,7 +860,7 @@ int bfhipLstSqTruncated(uint64_t count, uint32_t const *shapes, void const *A, v
   }
 done:
   bfdevFree(dA); bfdevFree(dB); bfdevFree(dX); bfdevFree(dV); bfdevFree(dQ); bfdevFree(dT); bfdevFree(dS); bfdevFree(dI);
-  if (prev >= 0) bfdevSetDevice(prev);
+  bfDevLeave(&ds);
   free(off); free(jobs); free(qrOut); free(routes); free(hInfo);
   return rc;
 }

@@ -29,19 +29,14 @@
 
 #include "bfhip_internal.h"
 #include "../../include/bfhip_abi.h"
+#include "bfhip_hip.h"
 #include "../../include/bfhip_build.h"
-
-static int hipFailB(hipError_t e, char const *what) {
-  if (e == hipSuccess) return 0;
-  int code = (e == hipErrorOutOfMemory) ? BFABI_ERROR_MEMORY_ERROR : BFABI_ERROR_RUNTIME_ERROR;
-  return bfhipFail(code, "%s: %s", what, hipGetErrorString(e));
-}
 
 template <typename T> static int uploadArrayB(T **d, T const *h, uint64_t count, char const *what) {
   *d = NULL;
-  int rc = hipFailB(hipMalloc((void **)d, count * sizeof(T)), what);
+  int rc = bfHipFail(hipMalloc((void **)d, count * sizeof(T)), what);
   if (rc) return rc;
-  return hipFailB(hipMemcpy(*d, h, count * sizeof(T), hipMemcpyHostToDevice), what);
+  return bfHipFail(hipMemcpy(*d, h, count * sizeof(T), hipMemcpyHostToDevice), what);
 }
 
 // ---------------------------------------------------------------------------
@@ -207,10 +202,10 @@ int bfdevBuildEval(BfEvalMat const *hostMats, uint64_t const *hostTilePrefix, ui
   for (uint64_t done = 0; done < tiles && !rc;) {
     uint32_t const n = (uint32_t)(tiles - done > (1u << 30) ? (1u << 30) : tiles - done);
     hipLaunchKernelGGL(bfEvalKernel, dim3(n), dim3(256), 0, 0, dM, dP, (uint32_t)numMats, toDev(env), done);
-    rc = hipFailB(hipGetLastError(), "kernel-matrix evaluation launch");
+    rc = bfHipFail(hipGetLastError(), "kernel-matrix evaluation launch");
     done += n;
   }
-  if (!rc) rc = hipFailB(hipDeviceSynchronize(), "kernel-matrix evaluation");
+  if (!rc) rc = bfHipFail(hipDeviceSynchronize(), "kernel-matrix evaluation");
   (void)hipFree(dM);
   (void)hipFree(dP);
   return rc;
@@ -1017,17 +1012,17 @@ int bfdevBuildQrcp(BfQrProb const *hostProbs, uint64_t numProbs, uint32_t *hostR
   BfQrProb *dP = NULL;
   uint32_t *dR = NULL;
   if (!rc) rc = uploadArrayB(&dP, sorted, numProbs, "qr problems");
-  if (!rc) rc = hipFailB(hipMalloc((void **)&dR, numProbs * sizeof(uint32_t)), "qr ranks");
-  if (!rc) rc = hipFailB(hipFuncSetAttribute((void const *)bfQrcpKernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bfQrcpLdsCap(NC - 1)), "hipFuncSetAttribute(QR LDS)");
+  if (!rc) rc = bfHipFail(hipMalloc((void **)&dR, numProbs * sizeof(uint32_t)), "qr ranks");
+  if (!rc) rc = bfHipFail(hipFuncSetAttribute((void const *)bfQrcpKernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bfQrcpLdsCap(NC - 1)), "hipFuncSetAttribute(QR LDS)");
   for (int c = NC - 1; c >= 0 && !rc; --c) {              /* the big ones first */
     uint64_t const nc = count[c + 1] - count[c];
     if (!nc) continue;
     uint32_t const threads = c >= 2 ? 512 : 256;          /* LDS class ~ rows: short columns need few lane groups */
     hipLaunchKernelGGL(bfQrcpKernel, dim3((uint32_t)nc), dim3(threads), bfQrcpLdsCap(c), 0, dP + count[c], dR + count[c]);
-    rc = hipFailB(hipGetLastError(), "QR preconditioner launch");
+    rc = bfHipFail(hipGetLastError(), "QR preconditioner launch");
   }
-  if (!rc) rc = hipFailB(hipDeviceSynchronize(), "QR preconditioner");
-  if (!rc) rc = hipFailB(hipMemcpy(ranks, dR, numProbs * sizeof(uint32_t), hipMemcpyDeviceToHost), "qr ranks");
+  if (!rc) rc = bfHipFail(hipDeviceSynchronize(), "QR preconditioner");
+  if (!rc) rc = bfHipFail(hipMemcpy(ranks, dR, numProbs * sizeof(uint32_t), hipMemcpyDeviceToHost), "qr ranks");
   for (uint64_t i = 0; i < numProbs && !rc; ++i) hostRanks[i] = ranks[order[i]];
   (void)hipFree(dP); (void)hipFree(dR);
   free(order); free(sorted); free(ranks);
@@ -1041,11 +1036,11 @@ int bfdevBuildQrcp(BfQrProb const *hostProbs, uint64_t numProbs, uint32_t *hostR
 static uint32_t const kJacobiLds[4] = {16u << 10, 32u << 10, 64u << 10, BF_JACOBI_LDS_MAX};
 
 template <int W> static int jacobiLaunch(uint32_t count, uint32_t threads, uint32_t lds, BfSvdProb const *dP, uint32_t const *dL, BfSvdStats *dS) {
-  int rc = hipFailB(hipFuncSetAttribute((void const *)bfJacobiKernel<W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BF_JACOBI_LDS_MAX),
+  int rc = bfHipFail(hipFuncSetAttribute((void const *)bfJacobiKernel<W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BF_JACOBI_LDS_MAX),
                     "hipFuncSetAttribute(Jacobi LDS)");
   if (rc) return rc;
   hipLaunchKernelGGL(bfJacobiKernel<W>, dim3(count), dim3(threads), lds, 0, dP, dL, dS, lds);
-  return hipFailB(hipGetLastError(), "Jacobi SVD launch");
+  return bfHipFail(hipGetLastError(), "Jacobi SVD launch");
 }
 
 typedef struct JacobiOrder { double cost; uint32_t idx; } JacobiOrder;
@@ -1124,7 +1119,7 @@ int bfdevBuildJacobi(BfSvdProb const *hostProbs, uint64_t numProbs, BfLstSqOpts 
   // stream; a non-blocking stream does not order with it) fill the CUs their tail leaves idle
   uint32_t *dGram = NULL;
   hipStream_t sGram = NULL;
-  if (!rc && numGram) rc = hipFailB(hipStreamCreateWithFlags(&sGram, hipStreamNonBlocking), "hipStreamCreate");
+  if (!rc && numGram) rc = bfHipFail(hipStreamCreateWithFlags(&sGram, hipStreamNonBlocking), "hipStreamCreate");
   if (!rc && numGram) {
     qsort(gramList, numGram, sizeof(JacobiOrder), jacobiCostDescending);
     uint32_t *ids = (uint32_t *)malloc(numGram * sizeof(uint32_t));
@@ -1137,7 +1132,7 @@ int bfdevBuildJacobi(BfSvdProb const *hostProbs, uint64_t numProbs, BfLstSqOpts 
     if (profile && !rc) { (void)hipDeviceSynchronize(); (void)hipMemcpy(&before, dS, sizeof before, hipMemcpyDeviceToHost); clock_gettime(CLOCK_MONOTONIC, &t0); }
     if (!rc) {
       hipLaunchKernelGGL(bfJacobiGramKernel, dim3((uint32_t)numGram), dim3(BF_GRAM_THREADS), 0, sGram, dP, dGram, dS);
-      rc = hipFailB(hipGetLastError(), "Jacobi SVD (block form) launch");
+      rc = bfHipFail(hipGetLastError(), "Jacobi SVD (block form) launch");
     }
     if (profile && !rc) {
       (void)hipDeviceSynchronize();
@@ -1192,17 +1187,17 @@ int bfdevBuildJacobi(BfSvdProb const *hostProbs, uint64_t numProbs, BfLstSqOpts 
     rc = uploadArrayB(&dG, globalList, numGlobal, "svd fallback list");
     if (!rc) {
       hipLaunchKernelGGL(bfJacobiGlobalKernel, dim3((uint32_t)numGlobal), dim3(1024), 0, 0, dP, dG, dS);
-      rc = hipFailB(hipGetLastError(), "Jacobi SVD (global-memory fallback) launch");
+      rc = bfHipFail(hipGetLastError(), "Jacobi SVD (global-memory fallback) launch");
     }
   }
-  if (!rc) rc = hipFailB(hipDeviceSynchronize(), "Jacobi SVD");
+  if (!rc) rc = bfHipFail(hipDeviceSynchronize(), "Jacobi SVD");
   (void)hipFree(dG); (void)hipFree(dGram);
   if (sGram) (void)hipStreamDestroy(sGram);
   free(globalList); free(gramList);
   for (int c = 0; c < NCLS; ++c) (void)hipFree(dL[c]);
   if (!rc && stats) {
     BfSvdStats got;
-    rc = hipFailB(hipMemcpy(&got, dS, sizeof got, hipMemcpyDeviceToHost), "svd stats");
+    rc = bfHipFail(hipMemcpy(&got, dS, sizeof got, hipMemcpyDeviceToHost), "svd stats");
     if (!rc) {
       if (got.maxSweeps > stats->maxSweeps) stats->maxSweeps = got.maxSweeps;
       stats->notConverged += got.notConverged;
@@ -1303,10 +1298,10 @@ int bfdevBuildGemm(BfGemmJob const *hostJobs, uint64_t numJobs) {
   for (uint64_t done = 0; done < tiles && !rc;) {
     uint32_t const n = (uint32_t)(tiles - done > (1u << 30) ? (1u << 30) : tiles - done);
     hipLaunchKernelGGL(bfGemmKernel, dim3(n), dim3(256), 0, 0, dJ, dP, (uint32_t)numJobs, done);
-    rc = hipFailB(hipGetLastError(), "builder gemm launch");
+    rc = bfHipFail(hipGetLastError(), "builder gemm launch");
     done += n;
   }
-  if (!rc) rc = hipFailB(hipDeviceSynchronize(), "builder gemm");
+  if (!rc) rc = bfHipFail(hipDeviceSynchronize(), "builder gemm");
   (void)hipFree(dJ);
   (void)hipFree(dP);
   free(prefix);
@@ -1357,10 +1352,10 @@ int bfdevBuildPack(void *arena, uint32_t outDtype, void const *store, BfPackPiec
       hipLaunchKernelGGL(bfPackKernel<float2>, dim3(n), dim3(256), 0, 0, (float2 *)arena, (double2 const *)store, d, done);
     else
       hipLaunchKernelGGL(bfPackKernel<double2>, dim3(n), dim3(256), 0, 0, (double2 *)arena, (double2 const *)store, d, done);
-    rc = hipFailB(hipGetLastError(), "pack launch");
+    rc = bfHipFail(hipGetLastError(), "pack launch");
     done += n;
   }
-  if (!rc) rc = hipFailB(hipDeviceSynchronize(), "pack");
+  if (!rc) rc = bfHipFail(hipDeviceSynchronize(), "pack");
   (void)hipFree(d);
   return rc;
 }
@@ -1429,7 +1424,7 @@ __global__ __launch_bounds__(256) void bfSliceSumKernel(double2 const *partial, 
 
 int bfdevMemFree(uint64_t *freeBytes) {
   size_t f = 0, t = 0;
-  int rc = hipFailB(hipMemGetInfo(&f, &t), "hipMemGetInfo");
+  int rc = bfHipFail(hipMemGetInfo(&f, &t), "hipMemGetInfo");
   *freeBytes = f;
   return rc;
 }
@@ -1446,15 +1441,15 @@ int bfdevHelm2Dense(BfEvalEnv const *env, uint32_t pot, uint64_t n, uint64_t num
   uint64_t const sliceLen = ((n + slices - 1) / slices + 255) / 256 * 256;
   slices = (uint32_t)((n + sliceLen - 1) / sliceLen);
   double2 *partial = NULL;
-  int rc = hipFailB(hipMalloc((void **)&partial, (size_t)slices * m * sizeof(double2)), "hipMalloc(dense apply partials)");
+  int rc = bfHipFail(hipMalloc((void **)&partial, (size_t)slices * m * sizeof(double2)), "hipMalloc(dense apply partials)");
   if (rc) return rc;
   hipLaunchKernelGGL(bfHelm2DenseKernel, dim3(tb, slices), dim3(256), 0, s, toDev(env), pot, n, m, square, (double2 const *)dX, partial, sliceLen);
-  rc = hipFailB(hipGetLastError(), "dense apply launch");
+  rc = bfHipFail(hipGetLastError(), "dense apply launch");
   if (!rc) {
     hipLaunchKernelGGL(bfSliceSumKernel, dim3(tb), dim3(256), 0, s, partial, m, slices, (double2 *)dY);
-    rc = hipFailB(hipGetLastError(), "dense apply sum launch");
+    rc = bfHipFail(hipGetLastError(), "dense apply sum launch");
   }
-  if (!rc) rc = hipFailB(hipStreamSynchronize(s), "dense apply");
+  if (!rc) rc = bfHipFail(hipStreamSynchronize(s), "dense apply");
   (void)hipFree(partial);
   return rc;
 }

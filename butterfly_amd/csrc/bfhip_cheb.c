@@ -172,13 +172,12 @@ struct BfhipChebCov {
 void bfhipChebCovFree(BfhipChebCov **pc) {
   if (!pc || !*pc) return;
   BfhipChebCov *c = *pc;
-  int prev = -1;
   if (c->dRowptr || c->dWork) {
-    bfdevGetDevice(&prev);
-    if (prev != c->device) bfdevSetDevice(c->device);
+    BfDevScope ds;
+    bfDevEnter(&ds, c->device);      /* a release cannot fail: errors are ignored on purpose */
     bfdevSync(NULL);
     bfdevFree(c->dRowptr); bfdevFree(c->dColind); bfdevFree(c->dVal); bfdevFree(c->dD); bfdevFree(c->dWork);
-    if (prev >= 0 && prev != c->device) bfdevSetDevice(prev);
+    bfDevLeave(&ds);
   }
   free(c->coef);
   free(c);
@@ -202,7 +201,8 @@ int bfhipChebCovCreate(int device, uint64_t n, uint64_t const *rowptr, uint64_t 
       if (!isfinite(massLumped[i]) || !(massLumped[i] > 0)) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "massLumped[%llu] is not a positive finite number", (unsigned long long)i);
   if (!isfinite(lamMax)) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "lamMax is not finite");
 
-  int rc = 0, prev = -1;
+  int rc = 0;
+  BfDevScope ds = {0};
   BfhipChebCov *c = calloc(1, sizeof *c);
   double *d = malloc(n * sizeof *d), *val = malloc((nnz ? nnz : 1) * sizeof *val);
   uint32_t *col32 = malloc((nnz ? nnz : 1) * sizeof *col32);
@@ -222,23 +222,19 @@ int bfhipChebCovCreate(int device, uint64_t n, uint64_t const *rowptr, uint64_t 
   if (!(lamMax > 0) || !isfinite(lamMax)) { rc = bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "the Gershgorin bound of S is %g: no interval [0, lamMax]", lamMax); goto fail; }
   c->n = n; c->nnz = nnz; c->lamMax = lamMax;
 
-  bfdevGetDevice(&prev);
-  if (device < 0) device = prev;
+  if ((rc = bfDevEnter(&ds, device))) goto fail;
+  if (device < 0) bfdevGetDevice(&device);      /* -1: the object lives on the current device */
   c->device = device;
-  if (prev != device && (rc = bfdevSetDevice(device))) goto fail;
   if ((rc = bfdevMalloc(&c->dRowptr, (n + 1) * 8)) || (rc = bfdevMalloc(&c->dColind, (nnz ? nnz : 1) * 4)) ||
       (rc = bfdevMalloc(&c->dVal, (nnz ? nnz : 1) * 8)) || (rc = bfdevMalloc(&c->dD, n * 8))) goto fail;
   if ((rc = bfdevMemcpyH2D(c->dRowptr, rowptr, (n + 1) * 8)) || (nnz && (rc = bfdevMemcpyH2D(c->dColind, col32, nnz * 4))) ||
       (nnz && (rc = bfdevMemcpyH2D(c->dVal, val, nnz * 8))) || (rc = bfdevMemcpyH2D(c->dD, d, n * 8))) goto fail;
   c->deviceBytes = (n + 1) * 8 + nnz * 4 + nnz * 8 + n * 8;
-  if (prev >= 0 && prev != device) bfdevSetDevice(prev);
-  free(d); free(val); free(col32);
-  *out = c;
-  return 0;
+  *out = c; c = NULL;
 fail:
   free(d); free(val); free(col32);
   if (c) bfhipChebCovFree(&c);             /* touches the device only for what was allocated there */
-  if (prev >= 0 && prev != device) bfdevSetDevice(prev);
+  bfDevLeave(&ds);
   return rc;
 }
 
@@ -313,11 +309,11 @@ static int chebBlockCheck(BfhipChebCov const *c, void const *in, void const *out
 }
 
 static int chebProduct(BfhipChebCov *c, double const *in, int scaleIn, int scaleOut, size_t q, double *out, void *stream) {
-  int rc, prev = -1;
-  bfdevGetDevice(&prev);
-  if (prev != c->device && (rc = bfdevSetDevice(c->device))) return rc;
+  int rc;
+  BfDevScope ds;
+  if ((rc = bfDevEnter(&ds, c->device))) return rc;
   if (!(rc = chebWork(c, 2, q, stream))) rc = chebMul(c, in, scaleIn, scaleOut, q, out, NULL, stream);
-  if (prev >= 0 && prev != c->device) bfdevSetDevice(prev);
+  bfDevLeave(&ds);
   return rc;
 }
 
@@ -332,36 +328,35 @@ int bfhipChebCovSampleBlockDevice(BfhipChebCov *c, double const *dW, size_t q, d
 }
 
 int bfhipChebCovMatvecBlockDevice(BfhipChebCov *c, double const *dV, size_t q, double *dZ, void *stream) {
-  int rc, prev = -1;
-  if ((rc = chebBlockCheck(c, dV, dZ, q))) return rc;
-  bfdevGetDevice(&prev);
-  if (prev != c->device && (rc = bfdevSetDevice(c->device))) return rc;
+  int rc;
+  BfDevScope ds;
+  if ((rc = chebBlockCheck(c, dV, dZ, q)) || (rc = bfDevEnter(&ds, c->device))) return rc;
   if ((rc = chebWork(c, 3, q, stream))) goto out;
   double *t = chebBlock(c, 2, q);
   if ((rc = chebMul(c, dV, 1, 0, q, t, NULL, stream))) goto out;          /* T = p(S) D V */
   rc = chebMul(c, t, 0, 1, q, dZ, NULL, stream);                          /* Z = D p(S) T */
 out:
-  if (prev >= 0 && prev != c->device) bfdevSetDevice(prev);
+  bfDevLeave(&ds);
   return rc;
 }
 
 int bfhipChebCovDrawDevice(BfhipChebCov *c, uint64_t seed, uint64_t firstSample, size_t q, double *dZ, void *stream) {
-  int rc, prev = -1;
-  if ((rc = chebBlockCheck(c, c, dZ, q))) return rc;
-  bfdevGetDevice(&prev);
-  if (prev != c->device && (rc = bfdevSetDevice(c->device))) return rc;
+  int rc;
+  BfDevScope ds;
+  if ((rc = chebBlockCheck(c, c, dZ, q)) || (rc = bfDevEnter(&ds, c->device))) return rc;
   if ((rc = chebWork(c, 3, q, stream))) goto out;
   double *w = chebBlock(c, 2, q);
   if ((rc = bfdevCovDrawFill(w, NULL, c->n, (uint32_t)q, BFHIP_F64, seed, firstSample, stream))) goto out;
   rc = chebMul(c, w, 0, 1, q, dZ, NULL, stream);
 out:
-  if (prev >= 0 && prev != c->device) bfdevSetDevice(prev);
+  bfDevLeave(&ds);
   return rc;
 }
 
 int bfhipChebCovMomentsDevice(BfhipChebCov *c, uint64_t seed, uint64_t firstSample, uint64_t numSamples, uint32_t batch, double *dSum,
                               double *dSumSq, void *stream) {
-  int rc, prev = -1;
+  int rc;
+  BfDevScope ds;
   if (!c) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL argument");
   if (!dSum && !dSumSq) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "both moment outputs are NULL");
   if (batch > 64) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "batch out of range (at most 64)");
@@ -369,8 +364,7 @@ int bfhipChebCovMomentsDevice(BfhipChebCov *c, uint64_t seed, uint64_t firstSamp
   if (!c->order) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "no coefficients: call bfhipChebCovSetCoefficients first");
   if (!batch) batch = 64;
   if (batch > numSamples) batch = (uint32_t)numSamples;
-  bfdevGetDevice(&prev);
-  if (prev != c->device && (rc = bfdevSetDevice(c->device))) return rc;
+  if ((rc = bfDevEnter(&ds, c->device))) return rc;
   if ((rc = chebWork(c, 3, batch, stream))) goto out;
   for (uint64_t s0 = 0; s0 < numSamples; s0 += batch) {
     uint32_t const b = (uint32_t)(numSamples - s0 < batch ? numSamples - s0 : batch);
@@ -381,6 +375,6 @@ int bfhipChebCovMomentsDevice(BfhipChebCov *c, uint64_t seed, uint64_t firstSamp
     if ((rc = bfdevCovMoments(z, c->n, b, BFHIP_F64, NULL, dSum, dSumSq, stream))) goto out;
   }
 out:
-  if (prev >= 0 && prev != c->device) bfdevSetDevice(prev);
+  bfDevLeave(&ds);
   return rc;
 }

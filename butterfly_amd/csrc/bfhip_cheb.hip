@@ -13,6 +13,7 @@
 
 #include "bfhip_internal.h"
 #include "../../include/bfhip_abi.h"
+#include "bfhip_hip.h"
 
 #define BF_CHEB_MAX_GRID (1u << 20)     // workgroups per launch; the rest is walked with a grid stride
 #ifndef BF_CHEB_GATHERS
@@ -105,7 +106,5 @@ int bfdevChebStep(BfChebStep const *s, void *stream) {
   uint64_t const perWg = 256u >> lg, need = (s->n + perWg - 1) / perWg;
   dim3 const grid((uint32_t)(need < BF_CHEB_MAX_GRID ? need : BF_CHEB_MAX_GRID)), block(256);
   hipLaunchKernelGGL(bfChebStepKernel, grid, block, 0, (hipStream_t)stream, *s, lg);
-  hipError_t const e = hipGetLastError();
-  if (e == hipSuccess) return 0;
-  return bfhipFail(e == hipErrorOutOfMemory ? BFABI_ERROR_MEMORY_ERROR : BFABI_ERROR_RUNTIME_ERROR, "Chebyshev step launch: %s", hipGetErrorString(e));
+  return bfHipFail(hipGetLastError(), "Chebyshev step launch");
 }

@@ -8,21 +8,66 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
-#include <time.h>
 
 #include "bfhip_cond.h"
 #include "../../include/bfhip_abi.h"
 
-static double nowSeconds(void) {
-  struct timespec t;
-  clock_gettime(CLOCK_MONOTONIC, &t);
-  return (double)t.tv_sec + 1e-9 * (double)t.tv_nsec;
+static int condKeyCmp(void const *a, void const *b) {
+  uint64_t const x = ((BfCondKey const *)a)->idx, y = ((BfCondKey const *)b)->idx;
+  return x < y ? -1 : x > y;
 }
 
-typedef struct { uint64_t obs; uint32_t slot; } ObsKey;
-static int obsKeyCmp(void const *a, void const *b) {
-  uint64_t const x = ((ObsKey const *)a)->obs, y = ((ObsKey const *)b)->obs;
-  return x < y ? -1 : x > y;
+int condLookupSort(uint64_t const *idx, uint32_t count, char const *what, BfCondKey **keys) {
+  BfCondKey *s = *keys = malloc(count * sizeof *s);
+  if (!s) return bfhipFail(BFABI_ERROR_MEMORY_ERROR, "out of host memory");
+  for (uint32_t t = 0; t < count; ++t) { s[t].idx = idx[t]; s[t].slot = t; }
+  qsort(s, count, sizeof *s, condKeyCmp);
+  for (uint32_t t = 1; t < count; ++t)
+    if (s[t].idx == s[t - 1].idx) {
+      int const rc = bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "%s index %llu is repeated", what, (unsigned long long)s[t].idx);
+      free(s); *keys = NULL;
+      return rc;
+    }
+  return 0;
+}
+
+int condLookupRange(BfCondKey const *keys, uint32_t count, char const *what, uint64_t numRows) {
+  if (keys[count - 1].idx < numRows) return 0;
+  return bfhipFail(BFABI_ERROR_OUT_OF_RANGE, "%s index %llu is outside the %llu rows", what, (unsigned long long)keys[count - 1].idx, (unsigned long long)numRows);
+}
+
+int condLookupRows(BfCondKey const *keys, uint64_t const *idx, uint32_t count, char const *what, uint64_t const *dRowPerm, uint64_t numRows, void *dRows,
+                   void *stream) {
+  if (!dRowPerm) return bfdevMemcpyH2D(dRows, idx, (size_t)count * 8);
+  int rc;
+  uint32_t flag = 0;
+  uint64_t *hRows = malloc(count * sizeof *hRows), *hSorted = malloc(count * sizeof *hSorted);
+  uint32_t *hSlot = malloc(count * sizeof *hSlot);
+  void *dSorted = NULL, *dSlot = NULL, *dFlag = NULL;
+  if (!hRows || !hSorted || !hSlot) { rc = bfhipFail(BFABI_ERROR_MEMORY_ERROR, "out of host memory"); goto out; }
+  for (uint32_t t = 0; t < count; ++t) { hSorted[t] = keys[t].idx; hSlot[t] = keys[t].slot; hRows[t] = UINT64_MAX; }
+  if ((rc = bfdevMalloc(&dSorted, (size_t)count * 8)) || (rc = bfdevMalloc(&dSlot, (size_t)count * 4)) || (rc = bfdevMalloc(&dFlag, 4)) ||
+      (rc = bfdevMemcpyH2D(dSorted, hSorted, (size_t)count * 8)) || (rc = bfdevMemcpyH2D(dSlot, hSlot, (size_t)count * 4)) || (rc = bfdevMemcpyH2D(dFlag, &flag, 4)) ||
+      (rc = bfdevMemcpyH2D(dRows, hRows, (size_t)count * 8))) goto out;
+  if ((rc = bfdevCondInvertPerm(dRowPerm, numRows, dSorted, dSlot, count, dRows, dFlag, stream)) || (rc = bfdevSync(stream)) ||
+      (rc = bfdevMemcpyD2H(hRows, dRows, (size_t)count * 8)) || (rc = bfdevMemcpyD2H(&flag, dFlag, 4))) goto out;
+  for (uint32_t t = 0; t < count && !flag; ++t) if (hRows[t] >= numRows) flag = 1;
+  if (flag) rc = bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "dRowPerm does not hit every %s index exactly once", what);
+out:
+  bfdevFree(dSorted); bfdevFree(dSlot); bfdevFree(dFlag);
+  free(hRows); free(hSorted); free(hSlot);
+  return rc;
+}
+
+int condAdjointPanel(BfhipOperator *op, void const *dGammaLam, uint64_t const *dRows, uint32_t p, double *Bt, uint32_t k, uint32_t c0, void *stream) {
+  uint64_t const m = op->plan.numRows, n = op->plan.numCols;
+  uint32_t const dtype = op->plan.dtype;
+  char *v, *t;                              /* the scratch's halves: unit panel, adjoint result */
+  bfCovHalves(op, BF_COND_MAX_RHS, &v, &t);
+  int rc;
+  if ((rc = bfdevMemsetAsync(v, 0, m * p * op->plan.elemSize, stream)) || (rc = bfdevCondUnitPanel(v, m, p, dRows, dtype, stream)) ||
+      (rc = bfhipApplyTransposeDevice(op, v, p, t, stream))) return rc;
+  return bfdevCondPack(Bt, n, k, c0, t, p, dGammaLam, dtype, stream);
 }
 
 static void condRelease(BfhipCovCond *c) {
@@ -38,20 +83,14 @@ int bfhipCovCondCreate(BfhipOperator *op, void const *dGammaLam, uint64_t const 
   if (!op || !obs || !out) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL argument");
   if (numObs == 0 || numObs > BFHIP_COND_MAX_OBS) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "numObs out of range (1 .. %u)", BFHIP_COND_MAX_OBS);
   uint32_t const k = (uint32_t)numObs;
-  ObsKey *keys = malloc(k * sizeof *keys);
-  if (!keys) return bfhipFail(BFABI_ERROR_MEMORY_ERROR, "out of host memory");
-  for (uint32_t a = 0; a < k; ++a) { keys[a].obs = obs[a]; keys[a].slot = a; }
-  qsort(keys, k, sizeof *keys, obsKeyCmp);
-  int rc = 0, prev = -1;
-  for (uint32_t a = 1; a < k && !rc; ++a)
-    if (keys[a].obs == keys[a - 1].obs) rc = bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "observed index %llu is repeated", (unsigned long long)keys[a].obs);
+  BfCondKey *keys = NULL;
+  BfDevScope ds = {0};
+  int rc = condLookupSort(obs, k, "observed", &keys);
+  if (rc) return rc;
   if (noiseVar) for (uint32_t a = 0; a < k && !rc; ++a)
     if (!(noiseVar[a] >= 0.0) || !isfinite(noiseVar[a])) rc = bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "noiseVar[%u] is negative or not finite", a);
-  if (!rc && keys[k - 1].obs >= op->plan.numRows)
-    rc = bfhipFail(BFABI_ERROR_OUT_OF_RANGE, "observed index %llu is outside the %llu rows", (unsigned long long)keys[k - 1].obs, (unsigned long long)op->plan.numRows);
-  if (!rc && bfDtypeComplex(op->plan.dtype)) rc = bfhipFail(BFABI_ERROR_TYPE_ERROR, "covariance products are defined for real operators (not complex128 / complex64)");
-  if (!rc && !op->hasTplan) rc = bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "operator was not compiled with BFHIP_FLAG_ADJOINT");
-  if (!rc && (op->flags & BFHIP_FLAG_PLAN_ONLY)) rc = bfhipFail(BFABI_ERROR_RUNTIME_ERROR, "operator was compiled with BFHIP_FLAG_PLAN_ONLY: no device operator exists");
+  if (!rc) rc = condLookupRange(keys, k, "observed", op->plan.numRows);
+  if (!rc) rc = bfCovCheckOperator(op, 1);
   /* the launch shapes of the per-pass kernels (bfhip_cond.hip): refused here, not in the first sample call after seconds of setup */
   if (!rc && !bfdevCondFits(op->plan.numCols)) rc = bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "conditioning: %llu columns are more than the contractions' grids take (%llu)",
                                                               (unsigned long long)op->plan.numCols, (unsigned long long)BF_COND_MAX_COLS);
@@ -59,17 +98,14 @@ int bfhipCovCondCreate(BfhipOperator *op, void const *dGammaLam, uint64_t const 
 
   uint64_t const m = op->plan.numRows, n = op->plan.numCols;
   size_t const es = op->plan.elemSize;
-  uint32_t const dtype = op->plan.dtype, Q = BF_COND_MAX_RHS;
+  uint32_t const Q = BF_COND_MAX_RHS;
   uint64_t const chunks = (n + BF_COND_CHUNK - 1) / BF_COND_CHUNK;
   BfhipCovCond *c = calloc(1, sizeof *c);
-  uint64_t *hRows = malloc(k * sizeof *hRows), *hSorted = malloc(k * sizeof *hSorted);
-  uint32_t *hSlot = malloc(k * sizeof *hSlot);
   double *hSd = malloc(k * sizeof *hSd);
-  void *dRows = NULL, *dSorted = NULL, *dSlot = NULL, *dFlag = NULL, *dStat = NULL;
-  if (!c || !hRows || !hSorted || !hSlot || !hSd) { rc = bfhipFail(BFABI_ERROR_MEMORY_ERROR, "out of host memory"); goto fail; }
+  void *dRows = NULL, *dStat = NULL;
+  if (!c || !hSd) { rc = bfhipFail(BFABI_ERROR_MEMORY_ERROR, "out of host memory"); goto fail; }
   c->op = op; c->dGammaLam = dGammaLam; c->dRowPerm = dRowPerm; c->k = k; c->device = op->device;
-  bfdevGetDevice(&prev);
-  if (prev != op->device && (rc = bfdevSetDevice(op->device))) goto fail;
+  if ((rc = bfDevEnter(&ds, op->device))) goto fail;
 
   /* ---- everything a later call needs, for passes of 64 columns ---- */
   if ((rc = bfdevSync(stream))) goto fail;
@@ -90,44 +126,27 @@ int bfhipCovCondCreate(BfhipOperator *op, void const *dGammaLam, uint64_t const 
   }
 
   /* ---- phase 1: the rows i_a, then B^T by adjoint panels of <= 64 unit columns ---- */
-  double t0 = nowSeconds();
-  if (dRowPerm) {
-    uint32_t flag = 0;
-    for (uint32_t a = 0; a < k; ++a) { hSorted[a] = keys[a].obs; hSlot[a] = keys[a].slot; hRows[a] = UINT64_MAX; }
-    if ((rc = bfdevMalloc(&dSorted, k * 8)) || (rc = bfdevMalloc(&dSlot, k * 4)) || (rc = bfdevMalloc(&dFlag, 4)) ||
-        (rc = bfdevMemcpyH2D(dSorted, hSorted, k * 8)) || (rc = bfdevMemcpyH2D(dSlot, hSlot, k * 4)) || (rc = bfdevMemcpyH2D(dFlag, &flag, 4)) ||
-        (rc = bfdevMemcpyH2D(dRows, hRows, k * 8))) goto fail;
-    if ((rc = bfdevCondInvertPerm(dRowPerm, m, dSorted, dSlot, k, dRows, dFlag, stream)) || (rc = bfdevSync(stream)) ||
-        (rc = bfdevMemcpyD2H(hRows, dRows, k * 8)) || (rc = bfdevMemcpyD2H(&flag, dFlag, 4))) goto fail;
-    for (uint32_t a = 0; a < k && !flag; ++a) if (hRows[a] >= m) flag = 1;
-    if (flag) { rc = bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "dRowPerm does not hit every observed index exactly once"); goto fail; }
-  } else {
-    if ((rc = bfdevMemcpyH2D(dRows, obs, k * 8))) goto fail;
-  }
-  {
-    uint64_t const big = m > n ? m : n;
-    char *v = op->dCov, *t = (char *)op->dCov + big * Q * es;        /* the scratch's halves: unit panel, adjoint result */
-    for (uint32_t c0 = 0; c0 < k; c0 += Q) {
-      uint32_t const p = k - c0 < Q ? k - c0 : Q;
-      if ((rc = bfdevMemsetAsync(v, 0, m * p * es, stream)) || (rc = bfdevCondUnitPanel(v, m, p, (uint64_t const *)dRows + c0, dtype, stream)) ||
-          (rc = bfhipApplyTransposeDevice(op, v, p, t, stream)) || (rc = bfdevCondPack(c->dBt, n, k, c0, t, p, dGammaLam, dtype, stream))) goto fail;
-      ++c->info.setupApplies;
-    }
+  double t0 = bfNowSeconds();
+  if ((rc = condLookupRows(keys, obs, k, "observed", dRowPerm, m, dRows, stream))) goto fail;
+  for (uint32_t c0 = 0; c0 < k; c0 += Q) {
+    uint32_t const p = k - c0 < Q ? k - c0 : Q;
+    if ((rc = condAdjointPanel(op, dGammaLam, (uint64_t const *)dRows + c0, p, c->dBt, k, c0, stream))) goto fail;
+    ++c->info.setupApplies;
   }
   if ((rc = bfdevSync(stream))) goto fail;
-  double t1 = nowSeconds();
+  double t1 = bfNowSeconds();
   c->info.rowsSeconds = t1 - t0;
 
   /* ---- phase 2: G + D (lower triangle; the rest stays zero) ---- */
   if ((rc = bfdevMemsetAsync(c->dL, 0, bytesL, stream)) || (rc = bfdevCondGram(c->dL, c->dBt, n, k, c->dNoiseVar, stream)) || (rc = bfdevSync(stream))) goto fail;
-  t0 = nowSeconds();
+  t0 = bfNowSeconds();
   c->info.gramSeconds = t0 - t1;
 
   /* ---- phase 3: Cholesky in place; the flag is read once, at the end ---- */
   BfCondStat st = {0xffffffffu, 0, INFINITY, -INFINITY};
   if ((rc = bfdevMemcpyH2D(dStat, &st, sizeof st)) || (rc = bfdevCondCholesky(c->dL, k, dStat, stream)) || (rc = bfdevSync(stream)) ||
       (rc = bfdevMemcpyD2H(&st, dStat, sizeof st))) goto fail;
-  c->info.factorSeconds = nowSeconds() - t0;
+  c->info.factorSeconds = bfNowSeconds() - t0;
   if (st.failStep != 0xffffffffu) {
     rc = bfhipFail(BFABI_ERROR_RUNTIME_ERROR, "Cholesky of G + D (%u observations): the pivot at step %u is <= 0 or not finite", k, st.failStep);
     goto fail;
@@ -136,9 +155,9 @@ int bfhipCovCondCreate(BfhipOperator *op, void const *dGammaLam, uint64_t const 
   *out = c; c = NULL;
 fail:
   condRelease(c);
-  bfdevFree(dRows); bfdevFree(dSorted); bfdevFree(dSlot); bfdevFree(dFlag); bfdevFree(dStat);
-  free(keys); free(hRows); free(hSorted); free(hSlot); free(hSd);
-  if (prev >= 0 && prev != op->device) bfdevSetDevice(prev);
+  bfdevFree(dRows); bfdevFree(dStat);
+  free(keys); free(hSd);
+  bfDevLeave(&ds);
   return rc;
 }
 
@@ -146,14 +165,12 @@ fail:
  * through c->op (the header asks for the object to go before its operator; the buffers are released correctly either way). */
 void bfhipCovCondFree(BfhipCovCond **c) {
   if (!c || !*c) return;
-  int prev = -1;
-  int const device = (*c)->device;
-  bfdevGetDevice(&prev);
-  if (prev != device) bfdevSetDevice(device);
+  BfDevScope ds;
+  bfDevEnter(&ds, (*c)->device);      /* a release cannot fail: errors are ignored on purpose */
   bfdevCondDeviceSync();
   condRelease(*c);
   *c = NULL;
-  if (prev >= 0 && prev != device) bfdevSetDevice(prev);
+  bfDevLeave(&ds);
 }
 
 int bfhipCovCondGetInfo(BfhipCovCond const *c, BfhipCovCondInfo *info) {
@@ -175,15 +192,17 @@ static int condPass(BfhipCovCond *c, double const *dY, void const *W, uint64_t l
 }
 
 /* The rest of a pass: the block sample of the b columns of W' that condPass left in the scratch's first half, into columns
- * s0 .. s0 + b - 1 of dZ [m x nrhs].  The one place that knows the scratch convention: covSampleBlock scales the first half in
- * place, applies into the second and, with a permutation, scatters from there.  A whole call (b == nrhs) writes dZ directly; a
- * pass of a wider block lands packed in the half that sequence leaves free and is copied into its columns. */
+ * s0 .. s0 + b - 1 of dZ [m x nrhs].  covSampleBlock scales the first half (bfCovHalves) in place, applies into the second and,
+ * with a permutation, scatters from there.  A whole call (b == nrhs) writes dZ directly; a pass of a wider block lands packed in
+ * the half that sequence leaves free and is copied into its columns. */
 static int condFinish(BfhipCovCond *c, uint32_t b, size_t nrhs, size_t s0, void *dZ, void *stream) {
   BfhipOperator *op = c->op;
-  uint64_t const m = op->plan.numRows, n = op->plan.numCols, big = m > n ? m : n;
+  uint64_t const m = op->plan.numRows;
   size_t const es = op->plan.elemSize;
   if (b == nrhs) return covSampleBlock(op, c->dGammaLam, c->dRowPerm, op->dCov, 0, b, dZ, stream);
-  char *t0 = op->dCov, *t1 = (char *)op->dCov + big * b * es, *packed = c->dRowPerm ? t0 : t1;
+  char *t0, *t1;
+  bfCovHalves(op, b, &t0, &t1);
+  char *const packed = c->dRowPerm ? t0 : t1;
   int rc = covSampleBlock(op, c->dGammaLam, c->dRowPerm, t0, 0, b, packed, stream);
   if (!rc) rc = bfdevMemcpy2DAsync((char *)dZ + s0 * es, nrhs * es, packed, b * es, b * es, m, stream);
   return rc;
@@ -206,29 +225,24 @@ static int condBlock(BfhipCovCond *c, double const *dY, void const *dW, double c
   return rc;
 }
 
-static int condEnter(BfhipCovCond *c, int *prev) {
-  *prev = -1;
-  bfdevGetDevice(prev);
-  return *prev != c->op->device ? bfdevSetDevice(c->op->device) : 0;
-}
-static void condLeave(BfhipCovCond *c, int prev) { if (prev >= 0 && prev != c->op->device) bfdevSetDevice(prev); }
-
 int bfhipCovCondSampleBlockDevice(BfhipCovCond *c, double const *dY, void const *dW, double const *dEps, size_t nrhs, void *dZ, double *dAlpha, void *stream) {
   if (!c || !dY || !dW || !dZ) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL argument");
   if (nrhs == 0 || nrhs > 0xffffu) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "nrhs out of range");
-  int rc, prev;
-  if ((rc = condEnter(c, &prev))) return rc;
+  int rc;
+  BfDevScope ds;
+  if ((rc = bfDevEnter(&ds, c->device))) return rc;
   rc = condBlock(c, dY, dW, dEps, nrhs, dZ, dAlpha, stream);
-  condLeave(c, prev);
+  bfDevLeave(&ds);
   return rc;
 }
 
 int bfhipCovCondMeanDevice(BfhipCovCond *c, double const *dY, void *dMean, double *dAlpha, void *stream) {
   if (!c || !dY || !dMean) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL argument");
-  int rc, prev;
-  if ((rc = condEnter(c, &prev))) return rc;
+  int rc;
+  BfDevScope ds;
+  if ((rc = bfDevEnter(&ds, c->device))) return rc;
   rc = condBlock(c, dY, NULL, NULL, 1, dMean, dAlpha, stream);
-  condLeave(c, prev);
+  bfDevLeave(&ds);
   return rc;
 }
 
@@ -242,15 +256,16 @@ static int condFill(BfhipCovCond *c, uint64_t seed, uint64_t noiseSeed, uint64_t
 int bfhipCovCondDrawDevice(BfhipCovCond *c, double const *dY, uint64_t seed, uint64_t noiseSeed, uint64_t firstSample, size_t nrhs, void *dZ, void *stream) {
   if (!c || !dY || !dZ) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL argument");
   if (nrhs == 0 || nrhs > 0xffffu) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "nrhs out of range");
-  int rc, prev;
-  if ((rc = condEnter(c, &prev))) return rc;
+  int rc;
+  BfDevScope ds;
+  if ((rc = bfDevEnter(&ds, c->device))) return rc;
   for (size_t s0 = 0; s0 < nrhs && !rc; s0 += BF_COND_MAX_RHS) {
     uint32_t const b = (uint32_t)(nrhs - s0 < BF_COND_MAX_RHS ? nrhs - s0 : BF_COND_MAX_RHS);
     if ((rc = condFill(c, seed, noiseSeed, firstSample + s0, b, stream))) break;
     if ((rc = condPass(c, dY, c->dWn, b, c->dNoiseSd ? c->dE : NULL, b, b, stream))) break;
     rc = condFinish(c, b, nrhs, s0, dZ, stream);
   }
-  condLeave(c, prev);
+  bfDevLeave(&ds);
   return rc;
 }
 
@@ -262,13 +277,15 @@ int bfhipCovCondMomentsDevice(BfhipCovCond *c, double const *dY, uint64_t seed, 
   if (numSamples == 0) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "numSamples is zero");
   if (!batch) batch = BF_COND_MAX_RHS;
   if (batch > numSamples) batch = (uint32_t)numSamples;
-  int rc, prev;
-  if ((rc = condEnter(c, &prev))) return rc;
+  int rc;
+  BfDevScope ds;
+  if ((rc = bfDevEnter(&ds, c->device))) return rc;
   BfhipOperator *op = c->op;
-  uint64_t const m = op->plan.numRows, n = op->plan.numCols, big = m > n ? m : n;
+  uint64_t const m = op->plan.numRows;
   for (uint64_t s0 = 0; s0 < numSamples && !rc; s0 += batch) {
     uint32_t const b = (uint32_t)(numSamples - s0 < batch ? numSamples - s0 : batch);
-    char *t0 = op->dCov, *t1 = (char *)op->dCov + big * b * op->plan.elemSize;
+    char *t0, *t1;
+    bfCovHalves(op, b, &t0, &t1);
     if ((rc = condFill(c, seed, noiseSeed, firstSample + s0, b, stream))) break;
     if ((rc = condPass(c, dY, c->dWn, b, c->dNoiseSd ? c->dE : NULL, b, b, stream))) break;
     /* the block sample without its scatter (scale in place, apply into the second half): Z is never written, the un-permuted
@@ -276,6 +293,6 @@ int bfhipCovCondMomentsDevice(BfhipCovCond *c, double const *dY, uint64_t seed, 
     if ((rc = covSampleBlock(op, c->dGammaLam, NULL, t0, 0, b, t1, stream))) break;
     rc = bfdevCovMoments(t1, m, b, op->plan.dtype, c->dRowPerm, dSum, dSumSq, stream);
   }
-  condLeave(c, prev);
+  bfDevLeave(&ds);
   return rc;
 }

@@ -34,6 +34,22 @@ struct BfhipCovCond {
 /* releases what bfhip_condlik.c allocated (the device is drained by the caller) */
 BF_HIDDEN void condLikRelease(BfhipCovCond *c);
 
+/* The rows i_t with dRowPerm[i_t] = idx[t], t < count (bfhip_cond.c): Create looks up its observed indices with it, the variance its
+ * queries; `what` ("observed" / "query") is the word the refusals use.  In steps, because each caller has refusals and device work
+ * of its own between them (Create validates its noise between the first two):
+ *   condLookupSort   *keys = the indices sorted, each with the place it came from (free() it); a repeated index is refused
+ *   condLookupRange  an index >= numRows is refused
+ *   condLookupRows   dRows [count], allocated by the caller on the current device: dRowPerm inverted there (refused unless every
+ *                    index is hit exactly once; drains `stream`), or idx itself without a permutation */
+typedef struct BfCondKey { uint64_t idx; uint32_t slot; } BfCondKey;
+BF_HIDDEN int condLookupSort(uint64_t const *idx, uint32_t count, char const *what, BfCondKey **keys);
+BF_HIDDEN int condLookupRange(BfCondKey const *keys, uint32_t count, char const *what, uint64_t numRows);
+BF_HIDDEN int condLookupRows(BfCondKey const *keys, uint64_t const *idx, uint32_t count, char const *what, uint64_t const *dRowPerm, uint64_t numRows, void *dRows,
+                             void *stream);
+/* One panel of p <= 64 rows of P A GammaLam, transposed, into columns c0 .. c0 + p - 1 of Bt [n x k]: unit columns at dRows[0 .. p)
+ * in the first half of the operator's covariance scratch (taken at 64 columns), A^T of them into the second, packed with GammaLam */
+BF_HIDDEN int condAdjointPanel(BfhipOperator *op, void const *dGammaLam, uint64_t const *dRows, uint32_t p, double *Bt, uint32_t k, uint32_t c0, void *stream);
+
 /* ---- the device entry points of bfhip_condlik.c, defined in bfhip_condlik.hip ---- */
 #define BF_LIK_STRIP 64u             /* columns of a strip of the wide solve */
 #define BF_LIK_NB 64u                /* its block rows: the diagonal tiles of L whose inverses are kept */

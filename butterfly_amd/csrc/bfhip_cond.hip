@@ -21,11 +21,7 @@
 
 #include "bfhip_operator.h"
 #include "../../include/bfhip_abi.h"
-
-static int hipFailD(hipError_t e, char const *what) {
-  if (e == hipSuccess) return 0;
-  return bfhipFail(e == hipErrorOutOfMemory ? BFABI_ERROR_MEMORY_ERROR : BFABI_ERROR_RUNTIME_ERROR, "%s: %s", what, hipGetErrorString(e));
-}
+#include "bfhip_hip.h"
 
 #define BF_COND_TI 32u           // tile rows
 #define BF_COND_TS 64u           // tile columns
@@ -99,14 +95,14 @@ __global__ __launch_bounds__(256) void bfCondInvertPermKernel(uint64_t const *pe
   }
 }
 
-int bfdevCondDeviceSync(void) { return hipFailD(hipDeviceSynchronize(), "hipDeviceSynchronize"); }
+int bfdevCondDeviceSync(void) { return bfHipFail(hipDeviceSynchronize(), "hipDeviceSynchronize"); }
 
 int bfdevCondInvertPerm(uint64_t const *dPerm, uint64_t m, uint64_t const *dObsSorted, uint32_t const *dObsSlot, uint32_t k, uint64_t *dRows, uint32_t *dFlag, void *stream) {
   uint64_t const need = (m + 255) / 256;
   dim3 const grid((uint32_t)(need < 65536 ? need : 65536)), block(256);
   for (int verify = 0; verify < 2; ++verify)
     hipLaunchKernelGGL(bfCondInvertPermKernel, grid, block, 0, (hipStream_t)stream, dPerm, m, dObsSorted, dObsSlot, k, dRows, dFlag, verify);
-  return hipFailD(hipGetLastError(), "permutation inverse launch");
+  return bfHipFail(hipGetLastError(), "permutation inverse launch");
 }
 
 // ---------------------------------------------------------------------------
@@ -124,7 +120,7 @@ int bfdevCondUnitPanel(void *V, uint64_t m, uint32_t p, uint64_t const *dRows, u
   if (dtype == BFHIP_F64) hipLaunchKernelGGL(bfCondUnitKernel<double>, dim3((p + 63) / 64), dim3(64), 0, (hipStream_t)stream, (double *)V, m, p, dRows);
   else if (dtype == BFHIP_F32) hipLaunchKernelGGL(bfCondUnitKernel<float>, dim3((p + 63) / 64), dim3(64), 0, (hipStream_t)stream, (float *)V, m, p, dRows);
   else return bfhipFail(BFABI_ERROR_TYPE_ERROR, "unit panel: real element types only");
-  return hipFailD(hipGetLastError(), "unit panel launch");
+  return bfHipFail(hipGetLastError(), "unit panel launch");
 }
 
 // Bt[j, c0 + c] = double(T[j, c]) * double(gamma[j]) for the adjoint panel T [n x p]: both factors widened exactly, one
@@ -147,7 +143,7 @@ int bfdevCondPack(double *Bt, uint64_t n, uint32_t k, uint32_t c0, void const *T
   if (dtype == BFHIP_F64) hipLaunchKernelGGL(bfCondPackKernel<double>, grid, block, 0, (hipStream_t)stream, Bt, n, k, c0, (double const *)T, p, (double const *)gamma);
   else if (dtype == BFHIP_F32) hipLaunchKernelGGL(bfCondPackKernel<float>, grid, block, 0, (hipStream_t)stream, Bt, n, k, c0, (float const *)T, p, (float const *)gamma);
   else return bfhipFail(BFABI_ERROR_TYPE_ERROR, "pack: real element types only");
-  return hipFailD(hipGetLastError(), "pack launch");
+  return bfHipFail(hipGetLastError(), "pack launch");
 }
 
 // ---------------------------------------------------------------------------
@@ -175,7 +171,7 @@ __global__ __launch_bounds__(256) void bfCondGramKernel(double *G, double const 
 int bfdevCondGram(double *G, double const *Bt, uint64_t n, uint32_t k, double const *dNoiseVar, void *stream) {
   dim3 const grid((k + BF_COND_TI - 1) / BF_COND_TI, (k + BF_COND_TS - 1) / BF_COND_TS), block(256);
   hipLaunchKernelGGL(bfCondGramKernel, grid, block, 0, (hipStream_t)stream, G, Bt, n, k, dNoiseVar);
-  return hipFailD(hipGetLastError(), "Gram launch");
+  return bfHipFail(hipGetLastError(), "Gram launch");
 }
 
 // ---------------------------------------------------------------------------
@@ -198,7 +194,7 @@ static int condSub(double *C, uint64_t ldc, double const *A, uint64_t sAi, uint6
   if (!M || !Nn || !P) return 0;
   dim3 const grid((uint32_t)((M + BF_COND_TI - 1) / BF_COND_TI), (uint32_t)((Nn + BF_COND_TS - 1) / BF_COND_TS)), block(256);
   hipLaunchKernelGGL(bfCondSubKernel, grid, block, 0, s, C, ldc, A, sAi, sAp, M, B, sBp, sBs, Nn, P, lowerOnly);
-  return hipFailD(hipGetLastError(), "block update launch");
+  return bfHipFail(hipGetLastError(), "block update launch");
 }
 
 // ---------------------------------------------------------------------------
@@ -286,7 +282,7 @@ int bfdevCondCholesky(double *G, uint32_t k, BfCondStat *dStat, void *stream) {
     int const rc = condSub(G + (uint64_t)r0 * k + r0, k, panel, k, 1, below, panel, 1, k, below, nb, 1, s);
     if (rc) return rc;
   }
-  return hipFailD(hipGetLastError(), "Cholesky launch");
+  return bfHipFail(hipGetLastError(), "Cholesky launch");
 }
 
 // ---------------------------------------------------------------------------
@@ -337,7 +333,7 @@ int bfdevCondSolve(double const *L, uint32_t k, double *R, uint32_t b, void *str
     if ((rc = condSub(R, b, L + (uint64_t)j0 * k, 1, k, j0, R + (uint64_t)j0 * b, b, 1, b, nb, 0, s))) return rc;
     if (!j0) break;
   }
-  return hipFailD(hipGetLastError(), "triangular solve launch");
+  return bfHipFail(hipGetLastError(), "triangular solve launch");
 }
 
 // ---------------------------------------------------------------------------
@@ -384,7 +380,7 @@ int bfdevCondResidual(double *R, double *part, double const *Bt, uint64_t n, uin
     else return bfhipFail(BFABI_ERROR_TYPE_ERROR, "residual: real element types only");
   }
   hipLaunchKernelGGL(bfCondResidualKernel, dim3((uint32_t)(((uint64_t)k * b + 255) / 256)), dim3(256), 0, s, R, part, (uint32_t)chunks, k, b, dY, E, lde);
-  return hipFailD(hipGetLastError(), "residual launch");
+  return bfHipFail(hipGetLastError(), "residual launch");
 }
 
 // ---------------------------------------------------------------------------
@@ -412,5 +408,5 @@ int bfdevCondUpdate(void *Wout, double const *Bt, uint64_t n, uint32_t k, double
   if (dtype == BFHIP_F64) hipLaunchKernelGGL(bfCondUpdateKernel<double>, grid, block, 0, s, (double *)Wout, Bt, n, k, alpha, (double const *)W, ldw, b);
   else if (dtype == BFHIP_F32) hipLaunchKernelGGL(bfCondUpdateKernel<float>, grid, block, 0, s, (float *)Wout, Bt, n, k, alpha, (float const *)W, ldw, b);
   else return bfhipFail(BFABI_ERROR_TYPE_ERROR, "update: real element types only");
-  return hipFailD(hipGetLastError(), "update launch");
+  return bfHipFail(hipGetLastError(), "update launch");
 }

@@ -22,13 +22,6 @@ void condLikRelease(BfhipCovCond *c) {
   c->likSlots = 0;
 }
 
-static int likEnter(BfhipCovCond *c, int *prev) {
-  *prev = -1;
-  bfdevGetDevice(prev);
-  return *prev != c->device ? bfdevSetDevice(c->device) : 0;
-}
-static void likLeave(BfhipCovCond *c, int prev) { if (prev >= 0 && prev != c->device) bfdevSetDevice(prev); }
-
 static uint64_t stripBytes(BfhipCovCond const *c) { return (uint64_t)c->k * BF_LIK_STRIP * sizeof(double); }
 
 /* at least `slots` strips of scratch, the inverses of the diagonal tiles of L (formed here, once) and, for the likelihood,
@@ -58,8 +51,9 @@ int bfhipCovCondLogLikelihoodDevice(BfhipCovCond *c, double const *dY, double *d
   uint64_t const ws = opt ? opt->workspaceBytes : 0, strip = stripBytes(c);
   if (ws && ws < strip)
     return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "workspaceBytes %llu is below one strip (%llu bytes)", (unsigned long long)ws, (unsigned long long)strip);
-  int rc, prev;
-  if ((rc = likEnter(c, &prev))) return rc;
+  int rc;
+  BfDevScope ds;
+  if ((rc = bfDevEnter(&ds, c->device))) return rc;
   BfhipOperator *op = c->op;
   uint64_t const n = op->plan.numCols;
   uint32_t const k = c->k;
@@ -82,14 +76,8 @@ int bfhipCovCondLogLikelihoodDevice(BfhipCovCond *c, double const *dY, double *d
     rc = bfdevLikGradNoise(dGradNoise, c->dR, c->dColSq + n, k, stream);
   }
 done:
-  likLeave(c, prev);
+  bfDevLeave(&ds);
   return rc;
-}
-
-typedef struct { uint64_t idx; uint32_t slot; } QueryKey;
-static int queryKeyCmp(void const *a, void const *b) {
-  uint64_t const x = ((QueryKey const *)a)->idx, y = ((QueryKey const *)b)->idx;
-  return x < y ? -1 : x > y;
 }
 
 int bfhipCovCondVarianceDevice(BfhipCovCond *c, uint64_t const *query, size_t numQuery, double *dPrior, double *dPost, void *stream) {
@@ -97,30 +85,20 @@ int bfhipCovCondVarianceDevice(BfhipCovCond *c, uint64_t const *query, size_t nu
   if (numQuery == 0 || numQuery > 0xffffffffu) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "numQuery out of range");
   if (!dPrior && !dPost) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "both variance outputs are NULL");
   uint32_t const nq = (uint32_t)numQuery;
-  QueryKey *keys = malloc(nq * sizeof *keys);
-  if (!keys) return bfhipFail(BFABI_ERROR_MEMORY_ERROR, "out of host memory");
-  for (uint32_t t = 0; t < nq; ++t) { keys[t].idx = query[t]; keys[t].slot = t; }
-  qsort(keys, nq, sizeof *keys, queryKeyCmp);
-  int rc = 0, prev = -1, entered = 0;
-  for (uint32_t t = 1; t < nq && !rc; ++t)
-    if (keys[t].idx == keys[t - 1].idx) rc = bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "query index %llu is repeated", (unsigned long long)keys[t].idx);
-  /* from here on the object is read */
-  if (!rc && keys[nq - 1].idx >= c->op->plan.numRows)
-    rc = bfhipFail(BFABI_ERROR_OUT_OF_RANGE, "query index %llu is outside the %llu rows", (unsigned long long)keys[nq - 1].idx, (unsigned long long)c->op->plan.numRows);
-  if (rc) { free(keys); return rc; }
+  BfCondKey *keys = NULL;
+  BfDevScope ds = {0};
+  int rc = condLookupSort(query, nq, "query", &keys);
+  if (rc) return rc;
+  /* from here on the object is read; a bad index is refused before the device is touched */
+  if ((rc = condLookupRange(keys, nq, "query", c->op->plan.numRows))) { free(keys); return rc; }
 
   BfhipOperator *op = c->op;
-  uint64_t const m = op->plan.numRows, n = op->plan.numCols, big = m > n ? m : n;
+  uint64_t const m = op->plan.numRows, n = op->plan.numCols;
   uint64_t const chunks = (n + BF_COND_CHUNK - 1) / BF_COND_CHUNK;
-  size_t const es = op->plan.elemSize;
-  uint32_t const k = c->k, dtype = op->plan.dtype, Q = BF_COND_MAX_RHS;
-  uint64_t *hRows = malloc(nq * sizeof *hRows), *hSorted = malloc(nq * sizeof *hSorted);
-  uint32_t *hSlot = malloc(nq * sizeof *hSlot);
-  void *dRows = NULL, *dSorted = NULL, *dSlot = NULL, *dFlag = NULL;
+  uint32_t const k = c->k, Q = BF_COND_MAX_RHS;
+  void *dRows = NULL;
   double *dSolved = NULL, *dZeros = NULL;
-  if (!hRows || !hSorted || !hSlot) { rc = bfhipFail(BFABI_ERROR_MEMORY_ERROR, "out of host memory"); goto done; }
-  if ((rc = likEnter(c, &prev))) goto done;
-  entered = 1;
+  if ((rc = bfDevEnter(&ds, c->device))) goto done;
 
   /* ---- workspace: one strip, the panel of rows and the small vectors ---- */
   if ((rc = likEnsure(c, 1, 0, stream))) goto done;
@@ -135,41 +113,24 @@ int bfhipCovCondVarianceDevice(BfhipCovCond *c, uint64_t const *query, size_t nu
   dSolved = c->dVarPart + chunks * BF_LIK_STRIP; dZeros = dSolved + BF_LIK_STRIP;       /* [64] sums of the solve, [k] zeros */
 
   /* ---- the rows i_t with dRowPerm[i_t] = query[t] ---- */
-  if ((rc = bfdevMalloc(&dRows, (size_t)nq * 8))) goto done;
-  if (c->dRowPerm) {
-    uint32_t flag = 0;
-    for (uint32_t t = 0; t < nq; ++t) { hSorted[t] = keys[t].idx; hSlot[t] = keys[t].slot; hRows[t] = UINT64_MAX; }
-    if ((rc = bfdevMalloc(&dSorted, (size_t)nq * 8)) || (rc = bfdevMalloc(&dSlot, (size_t)nq * 4)) || (rc = bfdevMalloc(&dFlag, 4)) ||
-        (rc = bfdevMemcpyH2D(dSorted, hSorted, (size_t)nq * 8)) || (rc = bfdevMemcpyH2D(dSlot, hSlot, (size_t)nq * 4)) || (rc = bfdevMemcpyH2D(dFlag, &flag, 4)) ||
-        (rc = bfdevMemcpyH2D(dRows, hRows, (size_t)nq * 8))) goto done;
-    if ((rc = bfdevCondInvertPerm(c->dRowPerm, m, dSorted, dSlot, nq, dRows, dFlag, stream)) || (rc = bfdevSync(stream)) ||
-        (rc = bfdevMemcpyD2H(hRows, dRows, (size_t)nq * 8)) || (rc = bfdevMemcpyD2H(&flag, dFlag, 4))) goto done;
-    for (uint32_t t = 0; t < nq && !flag; ++t) if (hRows[t] >= m) flag = 1;
-    if (flag) { rc = bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "dRowPerm does not hit every query index exactly once"); goto done; }
-  } else {
-    if ((rc = bfdevMemcpyH2D(dRows, query, (size_t)nq * 8))) goto done;
-  }
+  if ((rc = bfdevMalloc(&dRows, (size_t)nq * 8)) || (rc = condLookupRows(keys, query, nq, "query", c->dRowPerm, m, dRows, stream))) goto done;
 
   /* ---- panels of <= 64 queries: r^T by one adjoint apply, its squares, Bt^T r, the strip solve ---- */
-  {
-    char *v = op->dCov, *tt = (char *)op->dCov + big * Q * es;       /* the scratch's halves, as in Create */
-    for (uint32_t t0 = 0; t0 < nq; t0 += Q) {
-      uint32_t const p = nq - t0 < Q ? nq - t0 : Q;
-      if ((rc = bfdevMemsetAsync(v, 0, m * p * es, stream)) || (rc = bfdevCondUnitPanel(v, m, p, (uint64_t const *)dRows + t0, dtype, stream)) ||
-          (rc = bfhipApplyTransposeDevice(op, v, p, tt, stream)) || (rc = bfdevCondPack(c->dVarBlk, n, p, 0, tt, p, c->dGammaLam, dtype, stream)) ||
-          (rc = bfdevVarPriorPart(c->dVarPart, c->dVarBlk, n, p, stream))) goto done;
-      if (dPost) {
-        /* R = 0 - Bt^T r (the sign does not reach the squares), then ||L^-1 R||^2 per column */
-        if ((rc = bfdevCondResidual(c->dR, c->dPart, c->dBt, n, k, dZeros, c->dVarBlk, p, BFHIP_F64, NULL, 0, p, stream)) ||
-            (rc = bfdevLikStripSolve(c->dL, c->dLinv, k, BF_LIK_SRC_BLOCK, c->dR, p, p, c->dStrips, 1, dSolved, stream))) goto done;
-      }
-      if ((rc = bfdevVarAssemble(dPrior ? dPrior + t0 : NULL, dPost ? dPost + t0 : NULL, c->dVarPart, chunks, dSolved, p, stream))) goto done;
+  for (uint32_t t0 = 0; t0 < nq; t0 += Q) {
+    uint32_t const p = nq - t0 < Q ? nq - t0 : Q;
+    if ((rc = condAdjointPanel(op, c->dGammaLam, (uint64_t const *)dRows + t0, p, c->dVarBlk, p, 0, stream)) ||
+        (rc = bfdevVarPriorPart(c->dVarPart, c->dVarBlk, n, p, stream))) goto done;
+    if (dPost) {
+      /* R = 0 - Bt^T r (the sign does not reach the squares), then ||L^-1 R||^2 per column */
+      if ((rc = bfdevCondResidual(c->dR, c->dPart, c->dBt, n, k, dZeros, c->dVarBlk, p, BFHIP_F64, NULL, 0, p, stream)) ||
+          (rc = bfdevLikStripSolve(c->dL, c->dLinv, k, BF_LIK_SRC_BLOCK, c->dR, p, p, c->dStrips, 1, dSolved, stream))) goto done;
     }
+    if ((rc = bfdevVarAssemble(dPrior ? dPrior + t0 : NULL, dPost ? dPost + t0 : NULL, c->dVarPart, chunks, dSolved, p, stream))) goto done;
   }
-  rc = bfdevSync(stream);                                            /* the index buffers go with the call */
+  rc = bfdevSync(stream);                                            /* the row buffer goes with the call */
 done:
-  bfdevFree(dRows); bfdevFree(dSorted); bfdevFree(dSlot); bfdevFree(dFlag);
-  free(keys); free(hRows); free(hSorted); free(hSlot);
-  if (entered) likLeave(c, prev);
+  bfdevFree(dRows);
+  free(keys);
+  bfDevLeave(&ds);
   return rc;
 }

@@ -27,11 +27,7 @@
 
 #include "bfhip_cond.h"
 #include "../../include/bfhip_abi.h"
-
-static int hipFailL(hipError_t e, char const *what) {
-  if (e == hipSuccess) return 0;
-  return bfhipFail(e == hipErrorOutOfMemory ? BFABI_ERROR_MEMORY_ERROR : BFABI_ERROR_RUNTIME_ERROR, "%s: %s", what, hipGetErrorString(e));
-}
+#include "bfhip_hip.h"
 
 #define BF_LIK_TP 32u            // slab of the contracted index
 #define BF_LIK_TS BF_LIK_STRIP   // 64 columns
@@ -175,7 +171,7 @@ __global__ __launch_bounds__(64) void bfLikInvDiagKernel(double *Linv, double co
 int bfdevLikInvDiag(double *Linv, double const *L, uint32_t k, void *stream) {
   if (!k) return 0;
   hipLaunchKernelGGL(bfLikInvDiagKernel, dim3((k + BF_LIK_NB - 1) / BF_LIK_NB), dim3(64), 0, (hipStream_t)stream, Linv, L, k);
-  return hipFailL(hipGetLastError(), "diagonal tile inverse launch");
+  return bfHipFail(hipGetLastError(), "diagonal tile inverse launch");
 }
 
 int bfdevLikStripSolve(double const *L, double const *Linv, uint32_t k, int kind, double const *src, uint64_t ld, uint64_t numCols, double *strips, uint64_t slots, double *out,
@@ -192,7 +188,7 @@ int bfdevLikStripSolve(double const *L, double const *Linv, uint32_t k, int kind
     hipLaunchKernelGGL(bfLikStripKernel<BF_LIK_SRC_IDENTITY>, grid, block, 0, s, L, Linv, k, src, ld, numCols, numStrips, strips, out);
   } else if (kind == BF_LIK_SRC_BLOCK) hipLaunchKernelGGL(bfLikStripKernel<BF_LIK_SRC_BLOCK>, grid, block, 0, s, L, Linv, k, src, ld, numCols, numStrips, strips, out);
   else return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "strip solve: unknown source");
-  return hipFailL(hipGetLastError(), "strip solve launch");
+  return bfHipFail(hipGetLastError(), "strip solve launch");
 }
 
 // ---------------------------------------------------------------------------
@@ -223,7 +219,7 @@ __global__ __launch_bounds__(256) void bfLikValueKernel(double *value, double co
 
 int bfdevLikValue(double *value, double const *L, uint32_t k, double const *y, double const *alpha, void *stream) {
   hipLaunchKernelGGL(bfLikValueKernel, dim3(1), dim3(256), 0, (hipStream_t)stream, value, L, k, y, alpha);
-  return hipFailL(hipGetLastError(), "likelihood value launch");
+  return bfHipFail(hipGetLastError(), "likelihood value launch");
 }
 
 // ---------------------------------------------------------------------------
@@ -247,7 +243,7 @@ int bfdevLikGradGamma(double *grad, double const *Bt, uint64_t n, uint32_t k, do
   if (!n) return 0;
   uint64_t const need = (n + 3) / 4;
   hipLaunchKernelGGL(bfLikGradGammaKernel, dim3((uint32_t)(need < 65536 ? need : 65536)), dim3(256), 0, (hipStream_t)stream, grad, Bt, n, k, alpha, colSq);
-  return hipFailL(hipGetLastError(), "gamma gradient launch");
+  return bfHipFail(hipGetLastError(), "gamma gradient launch");
 }
 
 __global__ __launch_bounds__(256) void bfLikGradNoiseKernel(double *grad, double const *alpha, double const *colSq, uint32_t k) {
@@ -257,7 +253,7 @@ __global__ __launch_bounds__(256) void bfLikGradNoiseKernel(double *grad, double
 
 int bfdevLikGradNoise(double *grad, double const *alpha, double const *colSq, uint32_t k, void *stream) {
   hipLaunchKernelGGL(bfLikGradNoiseKernel, dim3((k + 255) / 256), dim3(256), 0, (hipStream_t)stream, grad, alpha, colSq, k);
-  return hipFailL(hipGetLastError(), "noise gradient launch");
+  return bfHipFail(hipGetLastError(), "noise gradient launch");
 }
 
 // ---------------------------------------------------------------------------
@@ -282,7 +278,7 @@ int bfdevVarPriorPart(double *part, double const *blk, uint64_t n, uint32_t p, v
   uint64_t const chunks = (n + BF_COND_CHUNK - 1) / BF_COND_CHUNK;
   if (!chunks || chunks > 65535) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "prior variance: 1 .. 65535 chunks of %u columns", BF_COND_CHUNK);
   hipLaunchKernelGGL(bfVarPriorPartKernel, dim3((uint32_t)chunks), dim3(256), 0, (hipStream_t)stream, part, blk, n, p);
-  return hipFailL(hipGetLastError(), "prior variance launch");
+  return bfHipFail(hipGetLastError(), "prior variance launch");
 }
 
 __global__ __launch_bounds__(64) void bfVarAssembleKernel(double *prior, double *post, double const *part, uint64_t chunks, double const *solved, uint32_t p) {
@@ -297,5 +293,5 @@ __global__ __launch_bounds__(64) void bfVarAssembleKernel(double *prior, double 
 int bfdevVarAssemble(double *prior, double *post, double const *part, uint64_t chunks, double const *solved, uint32_t p, void *stream) {
   if (!p || p > BF_LIK_TS) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "variance: 1 .. 64 columns a panel");
   hipLaunchKernelGGL(bfVarAssembleKernel, dim3(1), dim3(64), 0, (hipStream_t)stream, prior, post, part, chunks, solved, p);
-  return hipFailL(hipGetLastError(), "variance assembly launch");
+  return bfHipFail(hipGetLastError(), "variance assembly launch");
 }

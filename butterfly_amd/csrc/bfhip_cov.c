@@ -20,17 +20,14 @@ int bfhipFillNormalDevice(void *d, uint64_t count, uint64_t firstIdx, uint32_t d
 static int covBlockCheck(BfhipOperator const *op, void const *in, void const *out, size_t nrhs, int needAdjoint) {
   if (!op || !in || !out) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL argument");
   if (nrhs == 0 || nrhs > 0xffffu) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "nrhs out of range");
-  if (bfDtypeComplex(op->plan.dtype)) return bfhipFail(BFABI_ERROR_TYPE_ERROR, "covariance products are defined for real operators (not complex128 / complex64)");
-  if (needAdjoint && !op->hasTplan) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "operator was not compiled with BFHIP_FLAG_ADJOINT");
-  if (op->flags & BFHIP_FLAG_PLAN_ONLY) return bfhipFail(BFABI_ERROR_RUNTIME_ERROR, "operator was compiled with BFHIP_FLAG_PLAN_ONLY: no device operator exists");
-  return 0;
+  return bfCovCheckOperator(op, needAdjoint);
 }
 
 /* z = P A (GammaLam w) on blocks.  `scaled`: the input block is already in the scratch's first half, scaled (the draw) */
 int covSampleBlock(BfhipOperator *op, void const *dGammaLam, uint64_t const *dRowPerm, void const *dW, int scaled, size_t nrhs, void *dZ, void *stream) {
-  uint64_t const m = op->plan.numRows, n = op->plan.numCols, big = m > n ? m : n;
-  size_t const es = op->plan.elemSize;
-  char *t0 = op->dCov, *t1 = (char *)op->dCov + big * nrhs * es;
+  uint64_t const m = op->plan.numRows, n = op->plan.numCols;
+  char *t0, *t1;
+  bfCovHalves(op, nrhs, &t0, &t1);
   int rc;
   void const *xin = scaled ? t0 : dW;
   if (!scaled && dGammaLam) { if ((rc = bfdevCovScalePermute(t0, dW, dGammaLam, 1, NULL, n, (uint32_t)nrhs, op->plan.dtype, stream))) return rc; xin = t0; }
@@ -40,25 +37,23 @@ int covSampleBlock(BfhipOperator *op, void const *dGammaLam, uint64_t const *dRo
 }
 
 int bfhipCovSampleBlockDevice(BfhipOperator *op, void const *dGammaLam, uint64_t const *dRowPerm, void const *dW, size_t nrhs, void *dZ, void *stream) {
-  int rc, prev = -1;
-  if ((rc = covBlockCheck(op, dW, dZ, nrhs, 0))) return rc;
-  bfdevGetDevice(&prev);
-  if (prev != op->device && (rc = bfdevSetDevice(op->device))) return rc;
+  int rc;
+  BfDevScope ds;
+  if ((rc = covBlockCheck(op, dW, dZ, nrhs, 0)) || (rc = bfDevEnter(&ds, op->device))) return rc;
   if (!(rc = covScratch(op, nrhs, stream))) rc = covSampleBlock(op, dGammaLam, dRowPerm, dW, 0, nrhs, dZ, stream);
-  if (prev >= 0 && prev != op->device) bfdevSetDevice(prev);
+  bfDevLeave(&ds);
   return rc;
 }
 
 int bfhipCovMatvecBlockDevice(BfhipOperator *op, void const *dGammaLam, uint64_t const *dRowPerm, uint64_t const *dRevRowPerm, void const *dV, size_t nrhs, void *dZ, void *stream) {
-  int rc, prev = -1;
-  if ((rc = covBlockCheck(op, dV, dZ, nrhs, 1))) return rc;
-  bfdevGetDevice(&prev);
-  if (prev != op->device && (rc = bfdevSetDevice(op->device))) return rc;
-  uint64_t const m = op->plan.numRows, n = op->plan.numCols, big = m > n ? m : n;
-  size_t const es = op->plan.elemSize;
+  int rc;
+  BfDevScope ds;
+  if ((rc = covBlockCheck(op, dV, dZ, nrhs, 1)) || (rc = bfDevEnter(&ds, op->device))) return rc;
+  uint64_t const m = op->plan.numRows, n = op->plan.numCols;
   uint32_t const nr = (uint32_t)nrhs;
   if ((rc = covScratch(op, nrhs, stream))) goto out;
-  char *t0 = op->dCov, *t1 = (char *)op->dCov + big * nrhs * es;
+  char *t0, *t1;
+  bfCovHalves(op, nrhs, &t0, &t1);
   void const *vin = dV;
   if (dRevRowPerm) { if ((rc = bfdevCovScalePermute(t0, dV, NULL, 0, dRevRowPerm, m, nr, op->plan.dtype, stream))) goto out; vin = t0; }
   if ((rc = bfhipApplyTransposeDevice(op, vin, nrhs, t1, stream))) goto out;                 /* tmp2 = Phi^T V */
@@ -66,26 +61,26 @@ int bfhipCovMatvecBlockDevice(BfhipOperator *op, void const *dGammaLam, uint64_t
   if ((rc = bfhipApplyDevice(op, t1, nrhs, dRowPerm ? (void *)t0 : dZ, stream))) goto out;
   if (dRowPerm) rc = bfdevCovScalePermute(dZ, t0, NULL, 0, dRowPerm, m, nr, op->plan.dtype, stream);
 out:
-  if (prev >= 0 && prev != op->device) bfdevSetDevice(prev);
+  bfDevLeave(&ds);
   return rc;
 }
 
 int bfhipCovDrawDevice(BfhipOperator *op, void const *dGammaLam, uint64_t const *dRowPerm, uint64_t seed, uint64_t firstSample, size_t nrhs, void *dZ, void *stream) {
-  int rc, prev = -1;
-  if ((rc = covBlockCheck(op, dZ, dZ, nrhs, 0))) return rc;
-  bfdevGetDevice(&prev);
-  if (prev != op->device && (rc = bfdevSetDevice(op->device))) return rc;
+  int rc;
+  BfDevScope ds;
+  if ((rc = covBlockCheck(op, dZ, dZ, nrhs, 0)) || (rc = bfDevEnter(&ds, op->device))) return rc;
   if ((rc = covScratch(op, nrhs, stream))) goto out;
   if ((rc = bfdevCovDrawFill(op->dCov, dGammaLam, op->plan.numCols, (uint32_t)nrhs, op->plan.dtype, seed, firstSample, stream))) goto out;
   rc = covSampleBlock(op, dGammaLam, dRowPerm, NULL, 1, nrhs, dZ, stream);
 out:
-  if (prev >= 0 && prev != op->device) bfdevSetDevice(prev);
+  bfDevLeave(&ds);
   return rc;
 }
 
 int bfhipCovMomentsDevice(BfhipOperator *op, void const *dGammaLam, uint64_t const *dRowPerm, uint64_t seed, uint64_t firstSample, uint64_t numSamples,
                           uint32_t batch, double *dSum, double *dSumSq, void *stream) {
-  int rc, prev = -1;
+  int rc;
+  BfDevScope ds;
   if (!op) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL argument");
   if (!dSum && !dSumSq) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "both moment outputs are NULL");
   if (batch > 64) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "batch out of range (at most 64)");
@@ -93,20 +88,20 @@ int bfhipCovMomentsDevice(BfhipOperator *op, void const *dGammaLam, uint64_t con
   if ((rc = covBlockCheck(op, op, op, 1, 0))) return rc;
   if (!batch) batch = 64;
   if (batch > numSamples) batch = (uint32_t)numSamples;
-  bfdevGetDevice(&prev);
-  if (prev != op->device && (rc = bfdevSetDevice(op->device))) return rc;
-  uint64_t const m = op->plan.numRows, n = op->plan.numCols, big = m > n ? m : n;
+  if ((rc = bfDevEnter(&ds, op->device))) return rc;
+  uint64_t const m = op->plan.numRows, n = op->plan.numCols;
   if ((rc = covScratch(op, batch, stream))) goto out;
   for (uint64_t s0 = 0; s0 < numSamples; s0 += batch) {
     uint32_t const b = (uint32_t)(numSamples - s0 < batch ? numSamples - s0 : batch);
     /* a batch of b columns is packed at b columns: both halves start where they would for a call of nrhs = b */
-    char *t0 = op->dCov, *t1 = (char *)op->dCov + big * b * op->plan.elemSize;
+    char *t0, *t1;
+    bfCovHalves(op, b, &t0, &t1);
     if ((rc = bfdevCovDrawFill(t0, dGammaLam, n, b, op->plan.dtype, seed, firstSample + s0, stream))) goto out;
     if ((rc = bfhipApplyDevice(op, t0, b, t1, stream))) goto out;
     /* Z is never written: the un-permuted result goes straight into the sums of its rows' places */
     if ((rc = bfdevCovMoments(t1, m, b, op->plan.dtype, dRowPerm, dSum, dSumSq, stream))) goto out;
   }
 out:
-  if (prev >= 0 && prev != op->device) bfdevSetDevice(prev);
+  bfDevLeave(&ds);
   return rc;
 }

@@ -12,12 +12,8 @@
 
 #include "bfhip_internal.h"
 #include "../../include/bfhip_abi.h"
+#include "bfhip_hip.h"
 #include "../../include/bfhip_synth.h"
-
-static int hipFailC(hipError_t e, char const *what) {
-  if (e == hipSuccess) return 0;
-  return bfhipFail(e == hipErrorOutOfMemory ? BFABI_ERROR_MEMORY_ERROR : BFABI_ERROR_RUNTIME_ERROR, "%s: %s", what, hipGetErrorString(e));
-}
 
 #define BF_COV_MAX_GRID 65536u          // workgroups per launch; the rest is walked with a grid stride
 
@@ -95,7 +91,7 @@ int bfdevCovScalePermute(void *dst, void const *src, void const *scale, int powe
   if (dtype == BFHIP_F64) { if (vec) BF_COV_SP(double, true); else BF_COV_SP(double, false); }
   else { if (vec) BF_COV_SP(float, true); else BF_COV_SP(float, false); }
 #undef BF_COV_SP
-  return hipFailC(hipGetLastError(), "block scale/permute launch");
+  return bfHipFail(hipGetLastError(), "block scale/permute launch");
 }
 
 // ---------------------------------------------------------------------------
@@ -135,7 +131,7 @@ int bfdevFillNormal(void *d, uint64_t count, uint64_t firstIdx, uint32_t dtype, 
   if (dtype == BFHIP_F64) hipLaunchKernelGGL(bfNormalFillKernel<double>, grid, block, 0, (hipStream_t)stream, (double *)d, count, firstIdx, seed);
   else if (dtype == BFHIP_F32) hipLaunchKernelGGL(bfNormalFillKernel<float>, grid, block, 0, (hipStream_t)stream, (float *)d, count, firstIdx, seed);
   else return bfhipFail(BFABI_ERROR_TYPE_ERROR, "normal fill: real element types only");
-  return hipFailC(hipGetLastError(), "normal fill launch");
+  return bfHipFail(hipGetLastError(), "normal fill launch");
 }
 
 int bfdevCovDrawFill(void *w, void const *gamma, uint64_t cols, uint32_t nrhs, uint32_t dtype, uint64_t seed, uint64_t firstSample, void *stream) {
@@ -145,7 +141,7 @@ int bfdevCovDrawFill(void *w, void const *gamma, uint64_t cols, uint32_t nrhs, u
   if (dtype == BFHIP_F64) hipLaunchKernelGGL(bfCovDrawFillKernel<double>, grid, block, 0, (hipStream_t)stream, (double *)w, (double const *)gamma, cols, nrhs, seed, firstSample, lg);
   else if (dtype == BFHIP_F32) hipLaunchKernelGGL(bfCovDrawFillKernel<float>, grid, block, 0, (hipStream_t)stream, (float *)w, (float const *)gamma, cols, nrhs, seed, firstSample, lg);
   else return bfhipFail(BFABI_ERROR_TYPE_ERROR, "draw fill: real element types only");
-  return hipFailC(hipGetLastError(), "draw fill launch");
+  return bfHipFail(hipGetLastError(), "draw fill launch");
 }
 
 // ---------------------------------------------------------------------------
@@ -218,5 +214,5 @@ int bfdevCovMoments(void const *t, uint64_t rows, uint32_t b, uint32_t dtype, ui
   if (dtype == BFHIP_F64) { if (vec) BF_COV_MOM(double, true); else BF_COV_MOM(double, false); }
   else { if (vec) BF_COV_MOM(float, true); else BF_COV_MOM(float, false); }
 #undef BF_COV_MOM
-  return hipFailC(hipGetLastError(), "moments launch");
+  return bfHipFail(hipGetLastError(), "moments launch");
 }

@@ -38,16 +38,11 @@
 #include "bfhip_internal.h"
 #include "bfhip_stage_c128.h"
 #include "../../include/bfhip_abi.h"
+#include "bfhip_hip.h"
 #include "../../include/bfhip_synth.h"
 
 #define BF_WAVES_PER_WG 4
 #define BF_WAVE_LDS_BYTES (BF_XCAP * 16)
-
-static int hipFail(hipError_t e, char const *what) {
-  if (e == hipSuccess) return 0;
-  int code = (e == hipErrorOutOfMemory) ? BFABI_ERROR_MEMORY_ERROR : BFABI_ERROR_RUNTIME_ERROR;
-  return bfhipFail(code, "%s: %s", what, hipGetErrorString(e));
-}
 
 // ---------------------------------------------------------------------------
 // element traits
@@ -994,19 +989,19 @@ extern "C" {
 
 int bfdevSetDevice(int device) {
   if (device < 0) return 0;
-  return hipFail(hipSetDevice(device), "hipSetDevice");
+  return bfHipFail(hipSetDevice(device), "hipSetDevice");
 }
-int bfdevGetDevice(int *device) { return hipFail(hipGetDevice(device), "hipGetDevice"); }
+int bfdevGetDevice(int *device) { return bfHipFail(hipGetDevice(device), "hipGetDevice"); }
 int bfdevMalloc(void **p, size_t bytes) {
   *p = NULL;
   if (!bytes) bytes = 16;
-  return hipFail(hipMalloc(p, bytes), "hipMalloc");
+  return bfHipFail(hipMalloc(p, bytes), "hipMalloc");
 }
 void bfdevFree(void *p) { if (p) (void)hipFree(p); }
-int bfdevMemcpyH2D(void *dst, void const *src, size_t bytes) { return bytes ? hipFail(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice), "hipMemcpy H2D") : 0; }
-int bfdevMemcpyD2H(void *dst, void const *src, size_t bytes) { return bytes ? hipFail(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost), "hipMemcpy D2H") : 0; }
-int bfdevMemset(void *dst, int value, size_t bytes) { return bytes ? hipFail(hipMemset(dst, value, bytes), "hipMemset") : 0; }
-int bfdevSync(void *stream) { return hipFail(hipStreamSynchronize((hipStream_t)stream), "hipStreamSynchronize"); }
+int bfdevMemcpyH2D(void *dst, void const *src, size_t bytes) { return bytes ? bfHipFail(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice), "hipMemcpy H2D") : 0; }
+int bfdevMemcpyD2H(void *dst, void const *src, size_t bytes) { return bytes ? bfHipFail(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost), "hipMemcpy D2H") : 0; }
+int bfdevMemset(void *dst, int value, size_t bytes) { return bytes ? bfHipFail(hipMemset(dst, value, bytes), "hipMemset") : 0; }
+int bfdevSync(void *stream) { return bfHipFail(hipStreamSynchronize((hipStream_t)stream), "hipStreamSynchronize"); }
 // What a caller's pointer is: 0 plain (pageable / unknown) host memory, 1 device memory of the CURRENT device, 2 host memory the
 // runtime can DMA from / to directly (hipHostMalloc'd or hipHostRegister'ed), 3 device memory of another device.
 int bfdevPointerKind(void const *p) {
@@ -1021,18 +1016,18 @@ int bfdevPointerKind(void const *p) {
   if (a.type == hipMemoryTypeHost) return 2;
   return 0;      // unregistered, managed: staged like pageable memory
 }
-int bfdevHostRegister(void *p, size_t bytes) { return hipFail(hipHostRegister(p, bytes, hipHostRegisterDefault), "hipHostRegister"); }
-int bfdevHostUnregister(void *p) { return hipFail(hipHostUnregister(p), "hipHostUnregister"); }
-int bfdevMemcpyAnyAsync(void *dst, void const *src, size_t bytes, void *stream) { return bytes ? hipFail(hipMemcpyAsync(dst, src, bytes, hipMemcpyDefault, (hipStream_t)stream), "hipMemcpyAsync") : 0; }
-int bfdevHostAllocPinned(void **p, size_t bytes) { return hipFail(hipHostMalloc(p, bytes, hipHostMallocDefault), "hipHostMalloc"); }
+int bfdevHostRegister(void *p, size_t bytes) { return bfHipFail(hipHostRegister(p, bytes, hipHostRegisterDefault), "hipHostRegister"); }
+int bfdevHostUnregister(void *p) { return bfHipFail(hipHostUnregister(p), "hipHostUnregister"); }
+int bfdevMemcpyAnyAsync(void *dst, void const *src, size_t bytes, void *stream) { return bytes ? bfHipFail(hipMemcpyAsync(dst, src, bytes, hipMemcpyDefault, (hipStream_t)stream), "hipMemcpyAsync") : 0; }
+int bfdevHostAllocPinned(void **p, size_t bytes) { return bfHipFail(hipHostMalloc(p, bytes, hipHostMallocDefault), "hipHostMalloc"); }
 void bfdevHostFreePinned(void *p) { if (p) (void)hipHostFree(p); }
 
 int bfdevSynthFill(void *arena, uint32_t dtype, BfSynthPiece const *hostPieces, uint64_t count, uint64_t seed) {
   if (!count) return 0;
   BfSynthPiece *d = NULL;
-  int rc = hipFail(hipMalloc((void **)&d, count * sizeof(BfSynthPiece)), "hipMalloc(synth pieces)");
+  int rc = bfHipFail(hipMalloc((void **)&d, count * sizeof(BfSynthPiece)), "hipMalloc(synth pieces)");
   if (rc) return rc;
-  rc = hipFail(hipMemcpy(d, hostPieces, count * sizeof(BfSynthPiece), hipMemcpyHostToDevice), "hipMemcpy(synth pieces)");
+  rc = bfHipFail(hipMemcpy(d, hostPieces, count * sizeof(BfSynthPiece), hipMemcpyHostToDevice), "hipMemcpy(synth pieces)");
   if (!rc) {
     // a launch's global size (blocks x 256 threads) is a 32-bit count of work-items: at most 2^24 - 1 blocks of 256, or the
     // launch silently covers a truncated grid (found at 18 M pieces: the packed adjoint of the N = 1M streamed operand)
@@ -1043,10 +1038,10 @@ int bfdevSynthFill(void *arena, uint32_t dtype, BfSynthPiece const *hostPieces, 
       else if (dtype == BFHIP_F64) hipLaunchKernelGGL(bfSynthKernel<BFHIP_F64>, dim3(n), dim3(256), 0, 0, arena, d + done, seed);
       else if (dtype == BFHIP_C64) hipLaunchKernelGGL(bfSynthKernel<BFHIP_C64>, dim3(n), dim3(256), 0, 0, arena, d + done, seed);
       else hipLaunchKernelGGL(bfSynthKernel<BFHIP_F32>, dim3(n), dim3(256), 0, 0, arena, d + done, seed);
-      rc = hipFail(hipGetLastError(), "synth fill launch");
+      rc = bfHipFail(hipGetLastError(), "synth fill launch");
       done += n;
     }
-    if (!rc) rc = hipFail(hipDeviceSynchronize(), "synth fill");
+    if (!rc) rc = bfHipFail(hipDeviceSynchronize(), "synth fill");
   }
   (void)hipFree(d);
   return rc;
@@ -1119,11 +1114,11 @@ int bfdevLaunchStage(BfLaunchArgs const *a, void *stream) {
       if (rc) return rc;
     }
   }
-  return hipFail(hipGetLastError(), a->transposed ? "transposed stage launch" : "stage launch");
+  return bfHipFail(hipGetLastError(), a->transposed ? "transposed stage launch" : "stage launch");
 }
 
 
-int bfdevMemsetAsync(void *dst, int value, size_t bytes, void *stream) { return bytes ? hipFail(hipMemsetAsync(dst, value, bytes, (hipStream_t)stream), "hipMemsetAsync") : 0; }
+int bfdevMemsetAsync(void *dst, int value, size_t bytes, void *stream) { return bytes ? bfHipFail(hipMemsetAsync(dst, value, bytes, (hipStream_t)stream), "hipMemsetAsync") : 0; }
 
 int bfdevScalePermute(void *dst, void const *src, void const *scale, int power, uint64_t const *perm, uint64_t n, uint32_t dtype, void *stream) {
   if (!n) return 0;
@@ -1131,7 +1126,7 @@ int bfdevScalePermute(void *dst, void const *src, void const *scale, int power, 
   if (dtype == BFHIP_F64) hipLaunchKernelGGL(bfScalePermuteKernel<double>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (double *)dst, (double const *)src, (double const *)scale, power, perm, n);
   else if (dtype == BFHIP_F32) hipLaunchKernelGGL(bfScalePermuteKernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (float *)dst, (float const *)src, (float const *)scale, power, perm, n);
   else return bfhipFail(BFABI_ERROR_TYPE_ERROR, "scale/permute: real element types only");
-  return hipFail(hipGetLastError(), "scale/permute launch");
+  return bfHipFail(hipGetLastError(), "scale/permute launch");
 }
 
 int bfdevLaunchReduce(BfReduceArgs const *a, uint32_t count, void *stream) {
@@ -1163,24 +1158,24 @@ int bfdevLaunchReduce(BfReduceArgs const *a, uint32_t count, void *stream) {
       case BFHIP_KERNEL_REDUCE_F32: hipLaunchKernelGGL((bfReduceKernel<float, 1>), dim3(blocks), dim3(256), 0, s, B); break;
       default: return bfhipFail(BFABI_ERROR_TYPE_ERROR, "reduce: unknown dtype %u", dtype);
     }
-    int rc = hipFail(hipGetLastError(), "reduce launch");
+    int rc = bfHipFail(hipGetLastError(), "reduce launch");
     if (rc) return rc;
   }
   return 0;
 }
 
-int bfdevMemcpyD2HAsync(void *dst, void const *src, size_t bytes, void *stream) { return bytes ? hipFail(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, (hipStream_t)stream), "hipMemcpyAsync D2H") : 0; }
-int bfdevMemcpyH2DAsync(void *dst, void const *src, size_t bytes, void *stream) { return bytes ? hipFail(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, (hipStream_t)stream), "hipMemcpyAsync H2D") : 0; }
-int bfdevMemcpyD2DAsync(void *dst, void const *src, size_t bytes, void *stream) { return bytes ? hipFail(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream), "hipMemcpyAsync D2D") : 0; }
+int bfdevMemcpyD2HAsync(void *dst, void const *src, size_t bytes, void *stream) { return bytes ? bfHipFail(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, (hipStream_t)stream), "hipMemcpyAsync D2H") : 0; }
+int bfdevMemcpyH2DAsync(void *dst, void const *src, size_t bytes, void *stream) { return bytes ? bfHipFail(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, (hipStream_t)stream), "hipMemcpyAsync H2D") : 0; }
+int bfdevMemcpyD2DAsync(void *dst, void const *src, size_t bytes, void *stream) { return bytes ? bfHipFail(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream), "hipMemcpyAsync D2D") : 0; }
 
-int bfdevEventCreate(void **ev) { return hipFail(hipEventCreate((hipEvent_t *)ev), "hipEventCreate"); }
+int bfdevEventCreate(void **ev) { return bfHipFail(hipEventCreate((hipEvent_t *)ev), "hipEventCreate"); }
 void bfdevEventDestroy(void *ev) { if (ev) (void)hipEventDestroy((hipEvent_t)ev); }
-int bfdevEventRecord(void *ev, void *stream) { return hipFail(hipEventRecord((hipEvent_t)ev, (hipStream_t)stream), "hipEventRecord"); }
-int bfdevEventSync(void *ev) { return hipFail(hipEventSynchronize((hipEvent_t)ev), "hipEventSynchronize"); }
+int bfdevEventRecord(void *ev, void *stream) { return bfHipFail(hipEventRecord((hipEvent_t)ev, (hipStream_t)stream), "hipEventRecord"); }
+int bfdevEventSync(void *ev) { return bfHipFail(hipEventSynchronize((hipEvent_t)ev), "hipEventSynchronize"); }
 int bfdevEventElapsed(void *start, void *stop, float *ms) {
   hipError_t e = hipEventSynchronize((hipEvent_t)stop);
-  if (e != hipSuccess) return hipFail(e, "hipEventSynchronize");
-  return hipFail(hipEventElapsedTime(ms, (hipEvent_t)start, (hipEvent_t)stop), "hipEventElapsedTime");
+  if (e != hipSuccess) return bfHipFail(e, "hipEventSynchronize");
+  return bfHipFail(hipEventElapsedTime(ms, (hipEvent_t)start, (hipEvent_t)stop), "hipEventElapsedTime");
 }
 
 }  // extern "C"

@@ -16,14 +16,9 @@
 #include "bfhip_internal.h"
 #include "bfhip_stage_c128.h"
 #include "../../include/bfhip_abi.h"
+#include "bfhip_hip.h"
 
 #define BF_WAVES_PER_WG 4
-
-static int hipFail(hipError_t e, char const *what) {
-  if (e == hipSuccess) return 0;
-  int code = (e == hipErrorOutOfMemory) ? BFABI_ERROR_MEMORY_ERROR : BFABI_ERROR_RUNTIME_ERROR;
-  return bfhipFail(code, "%s: %s", what, hipGetErrorString(e));
-}
 
 // the stage kernel's body with per-item timestamps (tools/timeline.py)
 __global__ __launch_bounds__(BF_C128_WG_WAVES * 64) void bfStageKernelC128Timeline(StageParams p, uint64_t *timeline) {
@@ -368,7 +363,7 @@ static int bfTimelineLaunch(BfLaunchArgs const *a, StageParams const &p, uint32_
   (void)hipMemsetAsync(dev, 0, (n ? n : 1) * 64, s);
   if (pgrid) (void)bfdevLaunchPersistC128(&p, pgrid, a->tickets, dev, s);
   else hipLaunchKernelGGL(bfStageKernelC128Timeline, dim3(grid), dim3(BF_C128_WG_WAVES * 64), 0, s, p, dev);
-  int rc = hipFail(hipStreamSynchronize(s), "timeline launch");
+  int rc = bfHipFail(hipStreamSynchronize(s), "timeline launch");
   if (!rc && n) {
     std::vector<uint64_t> t(8 * n);
     std::vector<BfDevItem> items(n);
@@ -431,9 +426,9 @@ int bfdevLaunchFlow(BfFlowArgs const *a, void *stream) {
   p.x = a->x; p.y = a->y; p.temp = a->temp;
   // tickets are drawn one item ahead, so how many an apply draws is not fixed: the queue starts from zero every time
   hipError_t e = hipMemsetAsync(a->counters, 0, 4, (hipStream_t)stream);
-  if (e != hipSuccess) return hipFail(e, "flow queue reset");
+  if (e != hipSuccess) return bfHipFail(e, "flow queue reset");
   hipLaunchKernelGGL(bfFlowKernelC128, dim3(a->gridWorkgroups), dim3(BF_WAVES_PER_WG * 64), 0, (hipStream_t)stream, p);
-  return hipFail(hipGetLastError(), "flow launch");
+  return bfHipFail(hipGetLastError(), "flow launch");
 }
 
 // workgroups of the persistent launch: what the device holds at once (occupancy x CUs), never more than the items need
@@ -442,7 +437,7 @@ int bfdevFlowGrid(uint64_t numItems, uint32_t *grid) {
   hipError_t e = hipGetDevice(&dev);
   if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
   if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, bfFlowKernelC128, BF_WAVES_PER_WG * 64, 0);
-  if (e != hipSuccess) return hipFail(e, "flow occupancy");
+  if (e != hipSuccess) return bfHipFail(e, "flow occupancy");
   uint64_t g = (uint64_t)cus * (uint64_t)(perCu > 0 ? perCu : 1);
   uint64_t const need = (numItems + BF_WAVES_PER_WG - 1) / BF_WAVES_PER_WG;
   if (g > need) g = need;

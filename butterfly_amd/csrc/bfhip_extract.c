@@ -108,10 +108,9 @@ int bfhipExtractWorkspaceBytes(BfhipOperator const *op, size_t numRows, size_t n
  * size; else through pinned staging, unpacked and promoted into `host` of hostEs bytes per element). */
 static int runExtract(BfhipOperator *op, BfExtractCall const *c, uint64_t const *rows, size_t numRows, uint64_t const *cols, size_t numCols,
                       void *dOut, void *host, size_t ldOut, int direct, void *stream) {
-  int rc, prev = -1;
-  bfdevGetDevice(&prev);
-  int const dev = bfhipOperatorDevice(op);
-  if (prev != dev && (rc = bfdevSetDevice(dev))) return rc;
+  int rc;
+  BfDevScope ds;
+  if ((rc = bfDevEnter(&ds, bfhipOperatorDevice(op)))) return rc;
   void **slot = bfhipOperatorExtractSlot(op, workRelease);
   if (!*slot && !(*slot = calloc(1, sizeof(BfExtractWork)))) { rc = bfhipFail(BFABI_ERROR_MEMORY_ERROR, "host OOM"); goto out; }
   BfExtractWork *w = *slot;
@@ -212,7 +211,7 @@ static int runExtract(BfhipOperator *op, BfExtractCall const *c, uint64_t const 
   if (host && (rc = bfdevSync(stream))) goto out;
 out:
   if (rc && host && *slot) { bfdevSync(stream); bfdevSync(((BfExtractWork *)*slot)->copyStream); }   /* nothing in flight touches `host` */
-  if (prev >= 0 && prev != dev) bfdevSetDevice(prev);
+  bfDevLeave(&ds);
   return rc;
 }
 
@@ -236,12 +235,10 @@ static int extractHost(BfhipOperator *op, int adjointPlan, uint64_t const *rows,
   if (bfhipOperatorDevice(op) < 0) return bfhipFail(BFABI_ERROR_RUNTIME_ERROR, "operator was compiled with BFHIP_FLAG_PLAN_ONLY: no device operator exists");
   if (!Out) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL output");
   size_t const hostEs = bfDtypeComplex(c.dtype) ? 16 : 8;
-  int prev = -1;
-  bfdevGetDevice(&prev);
-  int const dev = bfhipOperatorDevice(op);
-  if (prev != dev && (rc = bfdevSetDevice(dev))) return rc;
+  BfDevScope ds;
+  if ((rc = bfDevEnter(&ds, bfhipOperatorDevice(op)))) return rc;
   int const kind = hostEs == c.es ? bfdevPointerKind(Out) : 0;      /* pinned / registered / device memory: the DMA's own target */
-  if (prev >= 0 && prev != dev) bfdevSetDevice(prev);
+  bfDevLeave(&ds);
   return runExtract(op, &c, rows, numRows, cols, numCols, NULL, Out, ldOut, kind != 0, NULL);
 }
 

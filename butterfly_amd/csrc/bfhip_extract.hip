@@ -23,15 +23,10 @@
 
 #include "bfhip_internal.h"
 #include "../../include/bfhip_abi.h"
+#include "bfhip_hip.h"
 
 #define BF_EX_THREADS 256
 #define BF_EX_GATHER_BLOCKS_MAX 65535u
-
-static int hipFailX(hipError_t e, char const *what) {
-  if (e == hipSuccess) return 0;
-  int code = (e == hipErrorOutOfMemory) ? BFABI_ERROR_MEMORY_ERROR : BFABI_ERROR_RUNTIME_ERROR;
-  return bfhipFail(code, "%s: %s", what, hipGetErrorString(e));
-}
 
 // value of index k of an index list: idx[base + k], or base + k for the identity (idx == NULL)
 __device__ __forceinline__ uint64_t bfExIndex(uint64_t const *idx, uint64_t base, uint64_t k) { return idx ? idx[base + k] : base + k; }
@@ -117,7 +112,7 @@ int bfdevExtractUnit(void *X, uint32_t dtype, uint64_t ext, uint64_t const *prev
     case BFHIP_F32: hipLaunchKernelGGL(bfExtractUnitKernel<float>, dim3(1), dim3(64), 0, s, (float *)X, ext, prevIdx, prevBase, prevCount, prevLd, idx, base, count, ld); break;
     default: return bfhipFail(BFABI_ERROR_TYPE_ERROR, "unit panel: unknown dtype %u", dtype);
   }
-  return hipFailX(hipGetLastError(), "extract unit-panel launch");
+  return bfHipFail(hipGetLastError(), "extract unit-panel launch");
 }
 
 int bfdevExtractGather(void *Out, uint64_t ldOut, void const *Y, uint64_t ext, uint32_t p, uint64_t const *rows, uint64_t rowBase, uint64_t numRows,
@@ -131,7 +126,7 @@ int bfdevExtractGather(void *Out, uint64_t ldOut, void const *Y, uint64_t ext, u
     case 4: hipLaunchKernelGGL(bfExtractGatherKernel<uint32_t>, g, dim3(BF_EX_THREADS), 0, s, (uint32_t *)Out, ldOut, (uint32_t const *)Y, ext, p, rows, rowBase, numRows); break;
     default: return bfhipFail(BFABI_ERROR_TYPE_ERROR, "gather: element size %u", elemSize);
   }
-  return hipFailX(hipGetLastError(), "extract gather launch");
+  return bfHipFail(hipGetLastError(), "extract gather launch");
 }
 
 int bfdevExtractGatherT(void *Out, uint64_t ldOut, void const *P, uint64_t ext, uint32_t p, uint64_t const *cols, uint64_t colBase, uint64_t numCols,
@@ -145,17 +140,17 @@ int bfdevExtractGatherT(void *Out, uint64_t ldOut, void const *P, uint64_t ext, 
     case 4: hipLaunchKernelGGL((bfExtractGatherTKernel<uint32_t, 64>), bfExGrid(numCols, 64), dim3(BF_EX_THREADS), 0, s, (uint32_t *)Out, ldOut, (uint32_t const *)P, ext, p, cols, colBase, numCols); break;
     default: return bfhipFail(BFABI_ERROR_TYPE_ERROR, "transposed gather: element size %u", elemSize);
   }
-  return hipFailX(hipGetLastError(), "extract transposed-gather launch");
+  return bfHipFail(hipGetLastError(), "extract transposed-gather launch");
 }
 
 // a stream that does not synchronise with the legacy default stream (the host entry's copies overlap the applies on it)
-int bfdevStreamCreateNonBlocking(void **stream) { return hipFailX(hipStreamCreateWithFlags((hipStream_t *)stream, hipStreamNonBlocking), "hipStreamCreateWithFlags"); }
+int bfdevStreamCreateNonBlocking(void **stream) { return bfHipFail(hipStreamCreateWithFlags((hipStream_t *)stream, hipStreamNonBlocking), "hipStreamCreateWithFlags"); }
 void bfdevStreamDestroy(void *stream) { if (stream) (void)hipStreamDestroy((hipStream_t)stream); }
-int bfdevStreamWaitEvent(void *stream, void *ev) { return hipFailX(hipStreamWaitEvent((hipStream_t)stream, (hipEvent_t)ev, 0), "hipStreamWaitEvent"); }
+int bfdevStreamWaitEvent(void *stream, void *ev) { return bfHipFail(hipStreamWaitEvent((hipStream_t)stream, (hipEvent_t)ev, 0), "hipStreamWaitEvent"); }
 // rows of `width` bytes from src (pitch spitch) to dst (pitch dpitch); any memory kinds
 int bfdevMemcpy2DAsync(void *dst, size_t dpitch, void const *src, size_t spitch, size_t width, size_t height, void *stream) {
   if (!width || !height) return 0;
-  return hipFailX(hipMemcpy2DAsync(dst, dpitch, src, spitch, width, height, hipMemcpyDefault, (hipStream_t)stream), "hipMemcpy2DAsync");
+  return bfHipFail(hipMemcpy2DAsync(dst, dpitch, src, spitch, width, height, hipMemcpyDefault, (hipStream_t)stream), "hipMemcpy2DAsync");
 }
 
 }  // extern "C"

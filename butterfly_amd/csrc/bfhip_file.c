@@ -254,13 +254,12 @@ static int loadPlan(FILE *fp, BfhipOperator *op, BfPlan *pl, FileHeader const *f
 int bfhipSave(BfhipOperator *op, char const *path) {
   if (!op || !path) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL argument");
   if (op->flags & BFHIP_FLAG_PLAN_ONLY) return bfhipFail(BFABI_ERROR_RUNTIME_ERROR, "a plan-only operator has no device data to save");
-  int prev = -1;
-  bfdevGetDevice(&prev);
-  int rc = bfdevSetDevice(op->device);
+  BfDevScope ds;
+  int rc = bfDevEnter(&ds, op->device);
   if (rc) return rc;
-  if ((rc = bfdevSync(NULL))) return rc;
+  if ((rc = bfdevSync(NULL))) goto out;
   FILE *fp = fopen(path, "wb");
-  if (!fp) return bfhipFail(BFABI_ERROR_FILE_ERROR, "cannot open %s for writing", path);
+  if (!fp) { rc = bfhipFail(BFABI_ERROR_FILE_ERROR, "cannot open %s for writing", path); goto out; }
   FileHeader fh;
   memset(&fh, 0, sizeof fh);
   memcpy(fh.magic, BFHIP_FILE_MAGIC, 8);
@@ -277,7 +276,8 @@ int bfhipSave(BfhipOperator *op, char const *path) {
   if (!rc) rc = writeDeviceArray(fp, op->dArena, (size_t)op->plan.arenaElems * op->plan.elemSize);
   if (!rc && op->dArenaT) rc = writeDeviceArray(fp, op->dArenaT, (size_t)arenaElemsT * op->plan.elemSize);
   if (fclose(fp) != 0 && !rc) rc = bfhipFail(BFABI_ERROR_FILE_ERROR, "error closing %s", path);
-  if (prev >= 0 && prev != op->device) bfdevSetDevice(prev);
+out:
+  bfDevLeave(&ds);
   return rc;
 }
 
@@ -302,13 +302,12 @@ int bfhipLoad(char const *path, BfhipOptions const *opts, BfhipOperator **out) {
   if (rc) { fclose(fp); return rc; }
   BfhipOperator *op = calloc(1, sizeof *op);
   if (!op) { fclose(fp); return bfhipFail(BFABI_ERROR_MEMORY_ERROR, "host OOM"); }
-  int prevDev = -1;
-  bfdevGetDevice(&prevDev);
+  BfDevScope ds = {0};
   op->flags = o.flags & ~(uint32_t)(BFHIP_FLAG_ADJOINT | BFHIP_FLAG_ADJOINT_PACKED);
   op->srcDtype = fh.srcDtype;
   op->leafBytesAlgorithmic = fh.leafBytesAlgorithmic;
-  if ((rc = bfdevSetDevice(o.device))) goto done;
-  if ((rc = bfdevGetDevice(&op->device))) goto done;
+  if ((rc = bfDevEnter(&ds, o.device))) goto done;
+  if ((rc = bfdevGetDevice(&op->device))) goto done;      /* o.device may be -1: the operator lives on the current device */
   uint64_t arenaElemsT = 0;
   int const packedT = (fh.reserved & 1u) != 0;
   if (fh.reserved & ~1u) { rc = bfhipFail(BFABI_ERROR_FILE_ERROR, "corrupt operator file (header flags)"); goto done; }
@@ -327,8 +326,9 @@ int bfhipLoad(char const *path, BfhipOptions const *opts, BfhipOperator **out) {
   if ((rc = finishOperator(op, o.maxRhs))) goto done;
 done:
   fclose(fp);
-  if (rc) { bfhipFree(&op); if (prevDev >= 0) bfdevSetDevice(prevDev); return rc; }
-  if (prevDev >= 0 && o.device >= 0) bfdevSetDevice(prevDev);
+  if (rc) bfhipFree(&op);
+  bfDevLeave(&ds);
+  if (rc) return rc;
   *out = op;
   return 0;
 }

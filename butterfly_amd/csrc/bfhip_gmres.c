@@ -124,12 +124,11 @@ int bfGmresSolve(BfGmresApplyFn apply, void *ctx, uint64_t n, int device, BfhipG
     if (ms.dtype == BFHIP_C64) return bfhipFail(BFABI_ERROR_NOT_IMPLEMENTED, "a complex64 preconditioner is not implemented");
     if (ms.dtype != BFHIP_C128) return bfhipFail(BFABI_ERROR_TYPE_ERROR, "the preconditioner must be a complex128 operator like the system it preconditions");
   }
-  int prev = -1, dev = device;
-  bfdevGetDevice(&prev);
-  int rc = prev != dev ? bfdevSetDevice(dev) : 0;
+  BfDevScope ds;
+  int rc = bfDevEnter(&ds, device);
   if (rc) return rc;
   rc = solveDevice(apply, ctx, n, solveM, orth, dB, nrhs, dX0, tol, maxNumIter, numIter, residual, dX, stream);
-  if (prev >= 0 && prev != dev) bfdevSetDevice(prev);
+  bfDevLeave(&ds);
   return rc;
 }
 
@@ -367,13 +366,13 @@ int bfhipSolveGMRES(BfhipOperator *op, void const *B, size_t ldb, size_t nrhs, v
   uint64_t n = bfhipGetNumRows(op);
   size_t const vecBytes = (size_t)n * nrhs * 16;
   void *dB = NULL, *dX0 = NULL, *dX = NULL;
-  int prev = -1, dev = bfhipOperatorDevice(op);
+  BfDevScope ds;
+  int const dev = bfhipOperatorDevice(op);
   if (dev < 0) return bfhipFail(BFABI_ERROR_RUNTIME_ERROR, "operator has no device (compiled with BFHIP_FLAG_PLAN_ONLY)");
   char *pack = malloc(vecBytes ? vecBytes : 1);
   int rc = 0;
   if (!pack) return bfhipFail(BFABI_ERROR_MEMORY_ERROR, "host OOM");
-  bfdevGetDevice(&prev);
-  if (prev != dev && (rc = bfdevSetDevice(dev))) { free(pack); return rc; }
+  if ((rc = bfDevEnter(&ds, dev))) { free(pack); return rc; }
   if ((rc = bfdevMalloc(&dB, vecBytes))) goto done;
   if ((rc = bfdevMalloc(&dX, vecBytes))) goto done;
   for (uint64_t i = 0; i < n; ++i) memcpy(pack + i * nrhs * 16, (char const *)B + i * ldb * 16, nrhs * 16);
@@ -389,6 +388,6 @@ int bfhipSolveGMRES(BfhipOperator *op, void const *B, size_t ldb, size_t nrhs, v
 done:
   bfdevFree(dB); bfdevFree(dX0); bfdevFree(dX);
   free(pack);
-  if (prev >= 0 && prev != dev) bfdevSetDevice(prev);
+  bfDevLeave(&ds);
   return rc;
 }

@@ -7,12 +7,7 @@
 
 #include "bfhip_internal.h"
 #include "../../include/bfhip_abi.h"
-
-static int hipFail(hipError_t e, char const *what) {
-  if (e == hipSuccess) return 0;
-  int code = (e == hipErrorOutOfMemory) ? BFABI_ERROR_MEMORY_ERROR : BFABI_ERROR_RUNTIME_ERROR;
-  return bfhipFail(code, "%s: %s", what, hipGetErrorString(e));
-}
+#include "bfhip_hip.h"
 
 // ---------------------------------------------------------------------------
 // device-resident GMRES building blocks (reference caller of the apply path:
@@ -329,66 +324,66 @@ extern "C" {
 int bfdevGmresResidual(void const *B, void const *AX0, void *W, void *partialOut, uint64_t n, uint32_t nrhs, uint32_t nb, void *expOut,
                        void *partialScaled, void *stream) {
   hipLaunchKernelGGL(bfGmresResidualKernel, dim3(nb, nrhs), dim3(BF_GM_THREADS), 0, (hipStream_t)stream, (double2 const *)B, (double2 const *)AX0, (double2 *)W, (double2 *)partialOut, n, nrhs, nb);
-  int rc = hipFail(hipGetLastError(), "gmres residual launch");
+  int rc = bfHipFail(hipGetLastError(), "gmres residual launch");
   if (rc || !expOut) return rc;
   hipLaunchKernelGGL(bfGmresScaleKernel, dim3(nb, nrhs), dim3(BF_GM_THREADS), 0, (hipStream_t)stream, (double2 *)W, (double2 const *)partialOut, (double *)expOut, (double2 *)partialScaled, n, nrhs, nb);
-  return hipFail(hipGetLastError(), "gmres scale launch");
+  return bfHipFail(hipGetLastError(), "gmres scale launch");
 }
 int bfdevGmresDot(void const *Vi, void const *W, void *partialOut, uint64_t n, uint32_t nrhs, uint32_t nb, void *stream) {
   hipLaunchKernelGGL(bfGmresDotKernel, dim3(nb, nrhs), dim3(BF_GM_THREADS), 0, (hipStream_t)stream, (double2 const *)Vi, (double2 const *)W, (double2 *)partialOut, n, nrhs, nb);
-  return hipFail(hipGetLastError(), "gmres dot launch");
+  return bfHipFail(hipGetLastError(), "gmres dot launch");
 }
 int bfdevGmresMgsStep(void const *Vi, void const *Vnext, void *W, void const *partialIn, void *partialOut, void *hOut,
                       uint64_t n, uint32_t nrhs, uint32_t nb, void *stream) {
   hipLaunchKernelGGL(bfGmresMgsKernel, dim3(nb, nrhs), dim3(BF_GM_THREADS), 0, (hipStream_t)stream, (double2 const *)Vi, (double2 const *)Vnext, (double2 *)W, (double2 const *)partialIn, (double2 *)partialOut, (double2 *)hOut, n, nrhs, nb);
-  return hipFail(hipGetLastError(), "gmres mgs launch");
+  return bfHipFail(hipGetLastError(), "gmres mgs launch");
 }
 int bfdevGmresFinish(void const *W, void const *partialIn, void *Vout, void *hOut, uint64_t n, uint32_t nrhs, uint32_t nb, void *stream) {
   hipLaunchKernelGGL(bfGmresFinishKernel, dim3(nb, nrhs), dim3(BF_GM_THREADS), 0, (hipStream_t)stream, (double2 const *)W, (double2 const *)partialIn, (double2 *)Vout, (double2 *)hOut, n, nrhs, nb);
-  return hipFail(hipGetLastError(), "gmres finish launch");
+  return bfHipFail(hipGetLastError(), "gmres finish launch");
 }
 int bfdevGmresDots(void const *V, void const *W, void *partial, uint64_t n, uint32_t nrhs, uint32_t nb, uint32_t numVec, void *stream) {
   hipLaunchKernelGGL(bfGmresDotsKernel, dim3(nb, nrhs, (numVec + BF_GM_GROUP - 1) / BF_GM_GROUP), dim3(BF_GM_THREADS), 0, (hipStream_t)stream,
                      (double2 const *)V, (double2 const *)W, (double2 *)partial, n, nrhs, nb, numVec);
-  return hipFail(hipGetLastError(), "gmres dots launch");
+  return bfHipFail(hipGetLastError(), "gmres dots launch");
 }
 int bfdevGmresDotsFinish(void const *partial, void const *hPrev, void *h, void *hSum, uint32_t nrhs, uint32_t nb, uint32_t numVec, void *stream) {
   hipLaunchKernelGGL(bfGmresDotsFinishKernel, dim3(numVec, nrhs), dim3(BF_GM_THREADS), 0, (hipStream_t)stream, (double2 const *)partial,
                      (double2 const *)hPrev, (double2 *)h, (double2 *)hSum, nrhs, nb, numVec);
-  return hipFail(hipGetLastError(), "gmres dots-finish launch");
+  return bfHipFail(hipGetLastError(), "gmres dots-finish launch");
 }
 int bfdevGmresProject(void const *V, void *W, void const *h, void *partialOut, uint64_t n, uint32_t nrhs, uint32_t nb, uint32_t numVec, void *stream) {
   hipLaunchKernelGGL(bfGmresProjectKernel, dim3(nb, nrhs), dim3(BF_GM_THREADS), 0, (hipStream_t)stream, (double2 const *)V, (double2 *)W,
                      (double2 const *)h, (double2 *)partialOut, n, nrhs, nb, numVec);
-  return hipFail(hipGetLastError(), "gmres project launch");
+  return bfHipFail(hipGetLastError(), "gmres project launch");
 }
 int bfdevGmresUpdate(void const *X0, void const *V, void const *y, uint32_t j, void *X, uint64_t n, uint32_t nrhs, void *stream) {
   uint64_t total = n * nrhs;
   hipLaunchKernelGGL(bfGmresUpdateKernel, dim3((uint32_t)((total + BF_GM_THREADS - 1) / BF_GM_THREADS)), dim3(BF_GM_THREADS), 0, (hipStream_t)stream, (double2 const *)X0, (double2 const *)V, (double2 const *)y, j, (double2 *)X, n, nrhs);
-  return hipFail(hipGetLastError(), "gmres update launch");
+  return bfHipFail(hipGetLastError(), "gmres update launch");
 }
 static inline dim3 bfRefineGrid(uint64_t count) { return dim3((uint32_t)((count + BF_GM_THREADS - 1) / BF_GM_THREADS)); }
 int bfdevRefineDemote(void const *src128, void *dst64, uint64_t count, void *stream) {
   if (!count) return 0;
   hipLaunchKernelGGL(bfRefineDemoteKernel, bfRefineGrid(count), dim3(BF_GM_THREADS), 0, (hipStream_t)stream, (double2 const *)src128, (float2 *)dst64, count);
-  return hipFail(hipGetLastError(), "refine demote launch");
+  return bfHipFail(hipGetLastError(), "refine demote launch");
 }
 int bfdevRefinePromote(void const *src64, void *dst128, uint64_t count, void *stream) {
   if (!count) return 0;
   hipLaunchKernelGGL(bfRefinePromoteKernel, bfRefineGrid(count), dim3(BF_GM_THREADS), 0, (hipStream_t)stream, (float2 const *)src64, (double2 *)dst128, count);
-  return hipFail(hipGetLastError(), "refine promote launch");
+  return bfHipFail(hipGetLastError(), "refine promote launch");
 }
 int bfdevRefineScale(void const *R, void const *partialIn, double const *expIn, void *Rhat, double *scale, uint64_t n, uint32_t nrhs, uint32_t nb,
                      void *stream) {
   hipLaunchKernelGGL(bfRefineScaleKernel, dim3(nb, nrhs), dim3(BF_GM_THREADS), 0, (hipStream_t)stream, (double2 const *)R, (double2 const *)partialIn,
                      expIn, (double2 *)Rhat, scale, n, nrhs, nb);
-  return hipFail(hipGetLastError(), "refine scale launch");
+  return bfHipFail(hipGetLastError(), "refine scale launch");
 }
 int bfdevRefineUpdate(void const *Xin, void const *D, double const *scale, void *Xout, uint64_t n, uint32_t nrhs, void *stream) {
   if (!n) return 0;
   hipLaunchKernelGGL(bfRefineUpdateKernel, bfRefineGrid(n * nrhs), dim3(BF_GM_THREADS), 0, (hipStream_t)stream, (double2 const *)Xin, (double2 const *)D,
                      scale, (double2 *)Xout, n, nrhs);
-  return hipFail(hipGetLastError(), "refine update launch");
+  return bfHipFail(hipGetLastError(), "refine update launch");
 }
 
 }  // extern "C"

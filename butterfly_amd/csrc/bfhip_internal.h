@@ -8,6 +8,7 @@
 #include <stddef.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <time.h>
 #include "../../include/bfhip.h"
 
 #ifdef __cplusplus
@@ -18,6 +19,11 @@ extern "C" {
  * error plumbing
  * ---------------------------------------------------------------------- */
 int bfhipFail(int code, char const *fmt, ...);   /* records message, returns code */
+static inline double bfNowSeconds(void) {       /* monotonic wall clock, for the phase timings the info structs report */
+  struct timespec ts;
+  clock_gettime(CLOCK_MONOTONIC, &ts);
+  return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
+}
 
 /* element types: complex (C128, C64) vs real; the complex128 layout (one element per 16-byte lane load, its own kernels and
  * plan shapes) vs the real family's (C64 is 8 bytes like F64 and gets exactly the F64 plan) */
@@ -272,6 +278,24 @@ struct BfhipOperator *bfhipShardedOperator(struct BfhipSharded const *sh);
  * ---------------------------------------------------------------------- */
 int bfdevSetDevice(int device);                 /* -1: keep current; returns BfError */
 int bfdevGetDevice(int *device);
+/* Run on `device`, give the caller's device back.  bfDevEnter: device < 0 keeps the current one (no call at all); otherwise the device
+ * is set only when the query failed or named another one, and a failed set returns its code with the scope left inert (nothing was
+ * changed).  bfDevLeave restores only after a switch whose query had succeeded; it is idempotent and a no-op on a zeroed scope, so a
+ * function declares `BfDevScope ds = {0}` up front and reaches one bfDevLeave from every exit. */
+typedef struct BfDevScope { int prev; int switched; } BfDevScope;
+static inline int bfDevEnter(BfDevScope *s, int device) {
+  s->prev = -1; s->switched = 0;
+  if (device < 0) return 0;
+  int const known = !bfdevGetDevice(&s->prev) && s->prev >= 0;
+  if (known && s->prev == device) return 0;
+  int const rc = bfdevSetDevice(device);
+  if (!rc) s->switched = known;
+  return rc;
+}
+static inline void bfDevLeave(BfDevScope *s) {
+  if (s->switched) bfdevSetDevice(s->prev);
+  s->switched = 0;
+}
 int bfdevMalloc(void **p, size_t bytes);
 void bfdevFree(void *p);
 int bfdevMemcpyH2D(void *dst, void const *src, size_t bytes);

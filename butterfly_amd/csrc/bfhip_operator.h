@@ -6,6 +6,7 @@
 #define BFHIP_OPERATOR_H
 
 #include "bfhip_internal.h"
+#include "../../include/bfhip_abi.h"
 
 struct BfhipOperator {
   BfPlan plan;
@@ -53,6 +54,22 @@ struct BfhipOperator {
   void *extract;                    /* workspace of the dense extraction (bfhip_extract.c), released by extractRelease */
   void (*extractRelease)(void *);
 };
+
+/* The scratch convention of the covariance products, in one place: op->dCov (covScratch) is two blocks of the longer side, and a
+ * block of `nrhs` columns packs both at nrhs columns -- t0 = the permuted / scaled input, t1 = where the apply's result starts. */
+static inline void bfCovHalves(BfhipOperator const *op, size_t nrhs, char **t0, char **t1) {
+  uint64_t const big = op->plan.numRows > op->plan.numCols ? op->plan.numRows : op->plan.numCols;
+  *t0 = (char *)op->dCov;
+  *t1 = (char *)op->dCov + big * nrhs * op->plan.elemSize;
+}
+
+/* what every covariance entry refuses about its operator, in this order: element type, (adjoint,) device */
+static inline int bfCovCheckOperator(BfhipOperator const *op, int needAdjoint) {
+  if (bfDtypeComplex(op->plan.dtype)) return bfhipFail(BFABI_ERROR_TYPE_ERROR, "covariance products are defined for real operators (not complex128 / complex64)");
+  if (needAdjoint && !op->hasTplan) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "operator was not compiled with BFHIP_FLAG_ADJOINT");
+  if (op->flags & BFHIP_FLAG_PLAN_ONLY) return bfhipFail(BFABI_ERROR_RUNTIME_ERROR, "operator was compiled with BFHIP_FLAG_PLAN_ONLY: no device operator exists");
+  return 0;
+}
 
 #define BF_ARENA_SLACK 256u
 #define BF_HOST_PIECE_ROWS 8192u    /* host vectors of more than 4 x this many rows cross PCIe in 4 pieces, copy and DMA overlapped */

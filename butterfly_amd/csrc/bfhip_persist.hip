@@ -30,6 +30,7 @@
 
 #include "bfhip_internal.h"
 #include "../../include/bfhip_abi.h"
+#include "bfhip_hip.h"
 #include "bfhip_stage_c128.h"
 
 template <bool TL>
@@ -102,6 +103,6 @@ extern "C" int bfdevLaunchPersistC128(void const *stageParams, uint32_t grid, vo
   if (!grid || grid >= p.numItems || grid % (8u * BF_TICKET_POOLS) || !tickets) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "persistent launch: bad grid");
   if (timeline) hipLaunchKernelGGL(bfStageKernelC128PTimeline, dim3(grid), dim3(64), 0, (hipStream_t)stream, p, (uint32_t *)tickets, (uint64_t *)timeline);
   else hipLaunchKernelGGL(bfStageKernelC128P, dim3(grid), dim3(64), 0, (hipStream_t)stream, p, (uint32_t *)tickets);
-  hipError_t const e = hipGetLastError();
+  hipError_t const e = hipGetLastError();      // not bfHipFail: a launch that fails for lack of memory is a RUNTIME_ERROR here
   return e == hipSuccess ? 0 : bfhipFail(BFABI_ERROR_RUNTIME_ERROR, "persistent stage launch: %s", hipGetErrorString(e));
 }

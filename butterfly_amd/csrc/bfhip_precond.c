@@ -22,15 +22,8 @@
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
-#include <time.h>
 
 #define BJ_DEFAULT_MAX_BLOCK 128u
-
-static double nowSec(void) {
-  struct timespec ts;
-  clock_gettime(CLOCK_MONOTONIC, &ts);
-  return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
-}
 
 /* one direct contribution: item rows [pr0, pr0 + nr) of a piece, landing on y rows [y0, y0 + nr) */
 typedef struct BjDirect {
@@ -215,16 +208,6 @@ static int checkSquare(BfhipOperator const *op) {
   return 0;
 }
 
-static int withOpDevice(BfhipOperator const *op, int *prev) {
-  *prev = -1;
-  if (bfhipOperatorDevice(op) < 0) return 0;
-  bfdevGetDevice(prev);
-  if (*prev == bfhipOperatorDevice(op)) { *prev = -1; return 0; }
-  int rc = bfdevSetDevice(bfhipOperatorDevice(op));
-  if (rc) *prev = -1;
-  return rc;
-}
-
 int bfhipBlockJacobiPartition(BfhipOperator const *op, uint32_t maxBlock, uint64_t *cuts, uint64_t cap, uint64_t *numBlocks) {
   int rc = checkSquare(op);
   if (rc) return rc;
@@ -234,9 +217,9 @@ int bfhipBlockJacobiPartition(BfhipOperator const *op, uint32_t maxBlock, uint64
   uint64_t const n = bfhipOperatorPlan(op)->numRows;
   BjDirectList L = {0};
   int64_t *reach = malloc((n ? n : 1) * sizeof *reach);
-  int prev = -1;
+  BfDevScope ds = {0};
   if (!reach) { rc = bfhipFail(BFABI_ERROR_MEMORY_ERROR, "host OOM"); goto out; }
-  if ((rc = withOpDevice(op, &prev))) goto out;
+  if ((rc = bfDevEnter(&ds, bfhipOperatorDevice(op)))) goto out;      /* -1 (plan-only): no device is touched */
   if ((rc = collectDirect(op, &L))) goto out;
   if ((rc = diagonalIntervals(&L, n, reach))) goto out;
   uint64_t nb = 0, unc = 0, lng = 0;
@@ -247,7 +230,7 @@ int bfhipBlockJacobiPartition(BfhipOperator const *op, uint32_t maxBlock, uint64
   }
   *numBlocks = nb;
 out:
-  if (prev >= 0) bfdevSetDevice(prev);
+  bfDevLeave(&ds);
   free(reach);
   free(L.d);
   return rc;
@@ -349,7 +332,7 @@ int bfhipBlockJacobi(BfhipOperator *op, BfhipBlockJacobiOptions const *opt, Bfhi
   int const planOnly = bfhipOperatorDevice(op) < 0;
   int const cplx = bfDtypeComplex(srcDt);
   size_t const wes = cplx ? 16 : 8;
-  double const t0 = nowSec();
+  double const t0 = bfNowSeconds();
   double t1 = t0, t2 = t0;
 
   BjDirectList L = {0};
@@ -365,7 +348,7 @@ int bfhipBlockJacobi(BfhipOperator *op, BfhipBlockJacobiOptions const *opt, Bfhi
   void *dWs = NULL, *dBlocks = NULL, *dTasks = NULL, *dRes = NULL;
   uint64_t *descArrays = NULL;
   uint8_t *kinds = NULL;
-  int prev = -1;
+  BfDevScope ds = {0};
   int64_t firstSingular = -1;
   double minPivotRel = NAN;
   uint64_t wsElems = 0;
@@ -373,7 +356,7 @@ int bfhipBlockJacobi(BfhipOperator *op, BfhipBlockJacobiOptions const *opt, Bfhi
   reach = malloc((n ? n : 1) * sizeof *reach);
   covered = malloc(n ? n : 1);
   if (!reach || !covered) { rc = bfhipFail(BFABI_ERROR_MEMORY_ERROR, "host OOM"); goto out; }
-  if ((rc = withOpDevice(op, &prev))) goto out;
+  if ((rc = bfDevEnter(&ds, bfhipOperatorDevice(op)))) goto out;      /* -1 (plan-only): no device is touched */
   if ((rc = collectDirect(op, &L))) goto out;
   if ((rc = diagonalIntervals(&L, n, reach))) goto out;
   autoPartition(reach, n, NULL, 0, &nb, &unc, &lng, covered);
@@ -474,7 +457,7 @@ int bfhipBlockJacobi(BfhipOperator *op, BfhipBlockJacobiOptions const *opt, Bfhi
   if ((rc = bfdevMemcpyH2D(dTasks, sorted, numTasks * sizeof *sorted))) goto out;
   if ((rc = bfdevBjGather(dWs, bfhipOperatorArena(op), pl->arenaElems, srcDt, dBlocks, dTasks, nb, NULL))) goto out;
   if ((rc = bfdevSync(NULL))) goto out;
-  t1 = nowSec();
+  t1 = bfNowSeconds();
 
   /* inversion */
   if (!(o.flags & BFHIP_BJ_NO_INVERT)) {
@@ -496,7 +479,7 @@ int bfhipBlockJacobi(BfhipOperator *op, BfhipBlockJacobiOptions const *opt, Bfhi
       goto out;
     }
   }
-  t2 = nowSec();
+  t2 = bfNowSeconds();
 
   /* the result: a BlockDiag of dense leaves 0..nb-1, root nb */
   {
@@ -535,7 +518,7 @@ int bfhipBlockJacobi(BfhipOperator *op, BfhipBlockJacobiOptions const *opt, Bfhi
 
 out:
   {
-    double const t3 = nowSec();
+    double const t3 = bfNowSeconds();
     if (info) {
       info->numBlocks = nb; info->maxBlockRows = 0; info->uncoveredRows = unc;
       if (cuts) for (uint64_t b = 0; b < nb; ++b) if (cuts[b + 1] - cuts[b] > info->maxBlockRows) info->maxBlockRows = cuts[b + 1] - cuts[b];
@@ -547,7 +530,7 @@ out:
     }
   }
   bfdevFree(dWs); bfdevFree(dBlocks); bfdevFree(dTasks); bfdevFree(dRes);
-  if (prev >= 0) bfdevSetDevice(prev);
+  bfDevLeave(&ds);
   free(L.d); free(reach); free(covered); free(cuts); free(blockOf); free(TL.t); free(TL.block); free(sorted); free(blocks); free(res); free(cnt);
   free(descArrays); free(kinds);
   return rc;

@@ -27,15 +27,10 @@
 
 #include "bfhip_internal.h"
 #include "../../include/bfhip_abi.h"
+#include "bfhip_hip.h"
 
 #define BF_BJ_THREADS 256
 #define BF_BJ_MAX_M 256      // BFHIP_BJ_MAX_BLOCK: the inversion keeps one LDS entry per row / column of a block
-
-static int hipFailP(hipError_t e, char const *what) {
-  if (e == hipSuccess) return 0;
-  int code = (e == hipErrorOutOfMemory) ? BFABI_ERROR_MEMORY_ERROR : BFABI_ERROR_RUNTIME_ERROR;
-  return bfhipFail(code, "%s: %s", what, hipGetErrorString(e));
-}
 
 // ---- element helpers: W = working type (double2 / double), S / O = stored types ----
 __device__ __forceinline__ double2 bjWiden(double2 v) { return v; }
@@ -250,7 +245,7 @@ int bfdevBjGather(void *ws, void const *arena, uint64_t arenaElems, uint32_t src
     case BFHIP_F32: hipLaunchKernelGGL((bfBjGatherKernel<float, double>), grid, block, 0, s, (double *)ws, (float const *)arena, arenaElems, dBlocks, dTasks); break;
     default: return bfhipFail(BFABI_ERROR_TYPE_ERROR, "block-Jacobi gather: unknown dtype %u", srcDtype);
   }
-  return hipFailP(hipGetLastError(), "block-Jacobi gather launch");
+  return bfHipFail(hipGetLastError(), "block-Jacobi gather launch");
 }
 
 int bfdevBjInvert(void *ws, int cplx, BfBjBlock const *dBlocks, BfBjResult *dResults, uint64_t numBlocks, void *stream) {
@@ -260,7 +255,7 @@ int bfdevBjInvert(void *ws, int cplx, BfBjBlock const *dBlocks, BfBjResult *dRes
   dim3 const grid((uint32_t)numBlocks), block(BF_BJ_THREADS);
   if (cplx) hipLaunchKernelGGL((bfBjInvertKernel<double2>), grid, block, 0, s, (double2 *)ws, dBlocks, dResults);
   else hipLaunchKernelGGL((bfBjInvertKernel<double>), grid, block, 0, s, (double *)ws, dBlocks, dResults);
-  return hipFailP(hipGetLastError(), "block-Jacobi inversion launch");
+  return bfHipFail(hipGetLastError(), "block-Jacobi inversion launch");
 }
 
 int bfdevBjFill(void *arena, uint32_t outDtype, void const *ws, BfBjFillPiece const *dPieces, uint64_t numPieces, void *stream) {
@@ -275,7 +270,7 @@ int bfdevBjFill(void *arena, uint32_t outDtype, void const *ws, BfBjFillPiece co
     case BFHIP_F32: hipLaunchKernelGGL((bfBjFillKernel<double, float>), grid, block, 0, s, (float *)arena, (double const *)ws, dPieces); break;
     default: return bfhipFail(BFABI_ERROR_TYPE_ERROR, "block-Jacobi fill: unknown dtype %u", outDtype);
   }
-  return hipFailP(hipGetLastError(), "block-Jacobi fill launch");
+  return bfHipFail(hipGetLastError(), "block-Jacobi fill launch");
 }
 
 }  // extern "C"

@@ -221,11 +221,10 @@ int bfhipSolveGMRESRefineDevice(BfhipOperator *op, BfhipOperator *opLow, BfhipGm
   if (rc) return rc;
   if (!dB || !dX) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL argument");
   if ((rc = deviceOf(op, opLow, opt->solveM, &dev))) return rc;
-  int prev = -1;
-  bfdevGetDevice(&prev);
-  if (prev != dev && (rc = bfdevSetDevice(dev))) return rc;
+  BfDevScope ds;
+  if ((rc = bfDevEnter(&ds, dev))) return rc;
   rc = refineDevice(op, opLow, opt, n, lowM, dB, nrhs, dX0, numOuter, numInner, residual, history, dX, stream);
-  if (prev >= 0 && prev != dev) bfdevSetDevice(prev);
+  bfDevLeave(&ds);
   return rc;
 }
 
@@ -240,11 +239,10 @@ int bfhipSolveGMRESRefine(BfhipOperator *op, BfhipOperator *opLow, BfhipGmresRef
   if ((rc = deviceOf(op, opLow, opt->solveM, &dev))) return rc;
   size_t const vecBytes = (size_t)n * nrhs * 16;
   void *dB = NULL, *dX0 = NULL, *dX = NULL;
-  int prev = -1;
+  BfDevScope ds;
   char *pack = malloc(vecBytes ? vecBytes : 1);
   if (!pack) return bfhipFail(BFABI_ERROR_MEMORY_ERROR, "host OOM");
-  bfdevGetDevice(&prev);
-  if (prev != dev && (rc = bfdevSetDevice(dev))) { free(pack); return rc; }
+  if ((rc = bfDevEnter(&ds, dev))) { free(pack); return rc; }
   if ((rc = bfdevMalloc(&dB, vecBytes))) goto done;
   if ((rc = bfdevMalloc(&dX, vecBytes))) goto done;
   for (uint64_t i = 0; i < n; ++i) memcpy(pack + i * nrhs * 16, (char const *)B + i * ldb * 16, nrhs * 16);
@@ -260,6 +258,6 @@ int bfhipSolveGMRESRefine(BfhipOperator *op, BfhipOperator *opLow, BfhipGmresRef
 done:
   bfdevFree(dB); bfdevFree(dX0); bfdevFree(dX);
   free(pack);
-  if (prev >= 0 && prev != dev) bfdevSetDevice(prev);
+  bfDevLeave(&ds);
   return rc;
 }

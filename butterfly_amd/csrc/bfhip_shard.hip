@@ -24,6 +24,7 @@
 
 #include "bfhip_internal.h"
 #include "../../include/bfhip_abi.h"
+#include "bfhip_hip.h"
 
 namespace {
 
@@ -82,11 +83,6 @@ int ncclFail(ncclResult_t r, char const *what) {
   if (r == ncclSuccess) return 0;
   return bfhipFail(BFABI_ERROR_RUNTIME_ERROR, "%s: %s", what, g.GetErrorString ? g.GetErrorString(r) : "RCCL error");
 }
-int hipFailS(hipError_t e, char const *what) {
-  if (e == hipSuccess) return 0;
-  return bfhipFail(e == hipErrorOutOfMemory ? BFABI_ERROR_MEMORY_ERROR : BFABI_ERROR_RUNTIME_ERROR, "%s: %s", what, hipGetErrorString(e));
-}
-
 struct Seg { uint64_t globalOff, srcOff, rows; };    // rows [globalOff, +rows) of y come from gather-buffer rows [srcOff, +rows)
 
 // Row ranges that several ranks contributed to (a block row shared by columns): y[row] = sum, in list order, of the
@@ -181,13 +177,13 @@ int bfhipCommInitRank(void const *id128, int nranks, int rank, int device, Bfhip
   if (rc) return rc;
   int prev = -1;
   (void)hipGetDevice(&prev);
-  if (device >= 0 && (rc = hipFailS(hipSetDevice(device), "hipSetDevice"))) return rc;
+  if (device >= 0 && (rc = bfHipFail(hipSetDevice(device), "hipSetDevice"))) return rc;
   BfhipComm *c = (BfhipComm *)calloc(1, sizeof *c);
   if (!c) return bfhipFail(BFABI_ERROR_MEMORY_ERROR, "host OOM");
   ncclUniqueId id;
   memcpy(&id, id128, sizeof id);
   rc = ncclFail(g.CommInitRank(&c->comm, nranks, id, rank), "ncclCommInitRank");
-  if (!rc) rc = hipFailS(hipGetDevice(&c->device), "hipGetDevice");
+  if (!rc) rc = bfHipFail(hipGetDevice(&c->device), "hipGetDevice");
   if (device >= 0 && prev >= 0 && prev != device) (void)hipSetDevice(prev);
   if (rc) { free(c); return rc; }
   c->nranks = nranks; c->rank = rank;
@@ -238,7 +234,7 @@ int bfhipShardedCreate(BfhipOperator *op, BfhipComm *comm, BfhipShardSpec const 
   s->numRowsGlobal = spec->numRowsGlobal;
   int prev = -1;
   (void)hipGetDevice(&prev);
-  if ((rc = hipFailS(hipSetDevice(comm->device), "hipSetDevice"))) { free(s); return rc; }
+  if ((rc = bfHipFail(hipSetDevice(comm->device), "hipSetDevice"))) { free(s); return rc; }
   if (spec->mode == BFHIP_SHARD_BLOCKS) {
     if (st.numRows != spec->numRowsGlobal) rc = bfhipFail(BFABI_ERROR_INCOMPATIBLE_SHAPES, "blocks mode: the local operator must produce all %llu rows", (unsigned long long)spec->numRowsGlobal);
   } else {
@@ -297,10 +293,10 @@ int bfhipShardedCreate(BfhipOperator *op, BfhipComm *comm, BfhipShardSpec const 
         if (!rc && covered != spec->numRowsGlobal) rc = bfhipFail(BFABI_ERROR_INCOMPATIBLE_SHAPES, "segments cover %llu rows, operator has %llu", (unsigned long long)covered, (unsigned long long)spec->numRowsGlobal);
         if (!rc && shared) {
           s->numGroups = ng;
-          rc = hipFailS(hipMalloc((void **)&s->dGroups, ng * sizeof *hg), "hipMalloc(sum groups)");
-          if (!rc) rc = hipFailS(hipMalloc((void **)&s->dSrcOff, (size_t)ns * 8), "hipMalloc(sum sources)");
-          if (!rc) rc = hipFailS(hipMemcpy(s->dGroups, hg, ng * sizeof *hg, hipMemcpyHostToDevice), "hipMemcpy(sum groups)");
-          if (!rc) rc = hipFailS(hipMemcpy(s->dSrcOff, hsrc, (size_t)ns * 8, hipMemcpyHostToDevice), "hipMemcpy(sum sources)");
+          rc = bfHipFail(hipMalloc((void **)&s->dGroups, ng * sizeof *hg), "hipMalloc(sum groups)");
+          if (!rc) rc = bfHipFail(hipMalloc((void **)&s->dSrcOff, (size_t)ns * 8), "hipMalloc(sum sources)");
+          if (!rc) rc = bfHipFail(hipMemcpy(s->dGroups, hg, ng * sizeof *hg, hipMemcpyHostToDevice), "hipMemcpy(sum groups)");
+          if (!rc) rc = bfHipFail(hipMemcpy(s->dSrcOff, hsrc, (size_t)ns * 8, hipMemcpyHostToDevice), "hipMemcpy(sum sources)");
         } else if (!rc) {
           // every range has one owner after all: the plain reorder kernel needs the segments sorted by global row
           Seg *sorted = (Seg *)malloc((ns ? ns : 1) * sizeof *sorted);
@@ -309,9 +305,9 @@ int bfhipShardedCreate(BfhipOperator *op, BfhipComm *comm, BfhipShardSpec const 
         }
         free(ord); free(hg); free(hsrc);
       }
-      if (!rc) rc = hipFailS(hipMalloc(&s->dGather, (size_t)comm->nranks * s->maxRows * s->maxRhs * s->elemSize + 16), "hipMalloc(gather buffer)");
-      if (!rc) rc = hipFailS(hipMalloc((void **)&s->dSegs, (s->numSegs ? s->numSegs : 1) * sizeof(Seg)), "hipMalloc(segments)");
-      if (!rc) rc = hipFailS(hipMemcpy(s->dSegs, s->hSegs, s->numSegs * sizeof(Seg), hipMemcpyHostToDevice), "hipMemcpy(segments)");
+      if (!rc) rc = bfHipFail(hipMalloc(&s->dGather, (size_t)comm->nranks * s->maxRows * s->maxRhs * s->elemSize + 16), "hipMalloc(gather buffer)");
+      if (!rc) rc = bfHipFail(hipMalloc((void **)&s->dSegs, (s->numSegs ? s->numSegs : 1) * sizeof(Seg)), "hipMalloc(segments)");
+      if (!rc) rc = bfHipFail(hipMemcpy(s->dSegs, s->hSegs, s->numSegs * sizeof(Seg), hipMemcpyHostToDevice), "hipMemcpy(segments)");
     }
     free(rowsOf);
   }
@@ -339,26 +335,26 @@ int bfhipShardedCreate(BfhipOperator *op, BfhipComm *comm, BfhipShardSpec const 
       for (uint32_t i = 1; i < cnt; ++i) oneRun = oneRun && mine[i].globalOff == mine[i - 1].globalOff + mine[i - 1].rows;
       if (oneRun) { s->numMySegs = 1; s->myFirstGlobal = mine[0].globalOff; }
       else if (cnt) {
-        rc = hipFailS(hipMalloc((void **)&s->dMySegs, cnt * sizeof(Seg)), "hipMalloc(own segments)");
-        if (!rc) rc = hipFailS(hipMemcpy(s->dMySegs, mine, cnt * sizeof(Seg), hipMemcpyHostToDevice), "hipMemcpy(own segments)");
-        if (!rc) rc = hipFailS(hipMalloc(&s->dVr, (size_t)s->myRows * s->maxRhs * s->elemSize + 16), "hipMalloc(compacted v)");
+        rc = bfHipFail(hipMalloc((void **)&s->dMySegs, cnt * sizeof(Seg)), "hipMalloc(own segments)");
+        if (!rc) rc = bfHipFail(hipMemcpy(s->dMySegs, mine, cnt * sizeof(Seg), hipMemcpyHostToDevice), "hipMemcpy(own segments)");
+        if (!rc) rc = bfHipFail(hipMalloc(&s->dVr, (size_t)s->myRows * s->maxRhs * s->elemSize + 16), "hipMalloc(compacted v)");
       }
       free(mine);
     }
   }
   {
     uint64_t const big = s->numRowsGlobal > s->numCols ? s->numRowsGlobal : s->numCols;
-    if (!rc && s->hasAdjoint && !bfDtypeComplex(s->dtype)) rc = hipFailS(hipMalloc(&s->dCov, 2 * (size_t)big * s->elemSize + 32), "hipMalloc(covariance scratch)");
-    if (!rc) rc = hipFailS(hipMalloc(&s->dHostX, (size_t)big * s->maxRhs * s->elemSize + 16), "hipMalloc(host staging)");
-    if (!rc) rc = hipFailS(hipMalloc(&s->dHostY, (size_t)big * s->maxRhs * s->elemSize + 16), "hipMalloc(host staging)");
+    if (!rc && s->hasAdjoint && !bfDtypeComplex(s->dtype)) rc = bfHipFail(hipMalloc(&s->dCov, 2 * (size_t)big * s->elemSize + 32), "hipMalloc(covariance scratch)");
+    if (!rc) rc = bfHipFail(hipMalloc(&s->dHostX, (size_t)big * s->maxRhs * s->elemSize + 16), "hipMalloc(host staging)");
+    if (!rc) rc = bfHipFail(hipMalloc(&s->dHostY, (size_t)big * s->maxRhs * s->elemSize + 16), "hipMalloc(host staging)");
   }
   s->timing = 1;
   // every allocation a step could need happens here: a step that fails on ONE rank after the others have enqueued
   // their half of the collective would leave them waiting forever
   if (!rc) rc = bfhipOperatorReserveRhs(op, s->maxRhs);
-  if (!rc) rc = hipFailS(hipEventCreate(&s->e0), "hipEventCreate");
-  if (!rc) rc = hipFailS(hipEventCreate(&s->e1), "hipEventCreate");
-  if (!rc) rc = hipFailS(hipEventCreate(&s->e2), "hipEventCreate");
+  if (!rc) rc = bfHipFail(hipEventCreate(&s->e0), "hipEventCreate");
+  if (!rc) rc = bfHipFail(hipEventCreate(&s->e1), "hipEventCreate");
+  if (!rc) rc = bfHipFail(hipEventCreate(&s->e2), "hipEventCreate");
   if (prev >= 0) (void)hipSetDevice(prev);
   if (rc) { bfhipShardedFree(&s); return rc; }
   *out = s;
@@ -372,7 +368,7 @@ int bfhipShardedApplyDevice(BfhipSharded *s, void const *dX, size_t nrhs, void *
   hipStream_t stream = (hipStream_t)streamV;
   int prev = -1;
   (void)hipGetDevice(&prev);
-  int rc = prev != s->device ? hipFailS(hipSetDevice(s->device), "hipSetDevice") : 0;
+  int rc = prev != s->device ? bfHipFail(hipSetDevice(s->device), "hipSetDevice") : 0;
   if (rc) return rc;
   ncclDataType_t const dt = (s->dtype == BFHIP_F32 || s->dtype == BFHIP_C64) ? ncclFloat32 : ncclFloat64;
   size_t const scalarsPerElem = bfDtypeComplex(s->dtype) ? 2 : 1;
@@ -398,7 +394,7 @@ int bfhipShardedApplyDevice(BfhipSharded *s, void const *dX, size_t nrhs, void *
       if (grid) {
         if (s->dtype == BFHIP_F32 || s->dtype == BFHIP_C64) hipLaunchKernelGGL(bfSumSegmentsKernel<float>, dim3(grid), dim3(256), 0, stream, s->dGroups, s->numGroups, s->dSrcOff, s->numRowsGlobal, (float const *)s->dGather, (float *)dY, scalarsPerRow);
         else hipLaunchKernelGGL(bfSumSegmentsKernel<double>, dim3(grid), dim3(256), 0, stream, s->dGroups, s->numGroups, s->dSrcOff, s->numRowsGlobal, (double const *)s->dGather, (double *)dY, scalarsPerRow);
-        rc = hipFailS(hipGetLastError(), "segment sum launch");
+        rc = bfHipFail(hipGetLastError(), "segment sum launch");
       }
     } else if (!rc && s->numSegs) {
       // unit = the largest power of two <= 16 bytes dividing a row; buffers are 16-byte aligned
@@ -411,7 +407,7 @@ int bfhipShardedApplyDevice(BfhipSharded *s, void const *dX, size_t nrhs, void *
         if (unit == 16) hipLaunchKernelGGL(bfScatterSegmentsKernel<uint4>, dim3(grid), dim3(256), 0, stream, s->dSegs, s->numSegs, s->numRowsGlobal, (uint4 const *)s->dGather, (uint4 *)dY, unitsPerRow);
         else if (unit == 8) hipLaunchKernelGGL(bfScatterSegmentsKernel<uint2>, dim3(grid), dim3(256), 0, stream, s->dSegs, s->numSegs, s->numRowsGlobal, (uint2 const *)s->dGather, (uint2 *)dY, unitsPerRow);
         else hipLaunchKernelGGL(bfScatterSegmentsKernel<uint32_t>, dim3(grid), dim3(256), 0, stream, s->dSegs, s->numSegs, s->numRowsGlobal, (uint32_t const *)s->dGather, (uint32_t *)dY, unitsPerRow);
-        rc = hipFailS(hipGetLastError(), "segment scatter launch");
+        rc = bfHipFail(hipGetLastError(), "segment scatter launch");
       }
     }
   }
@@ -438,7 +434,7 @@ int bfhipShardedApplyTransposeDevice(BfhipSharded *s, void const *dV, size_t nrh
   hipStream_t stream = (hipStream_t)streamV;
   int prev = -1;
   (void)hipGetDevice(&prev);
-  int rc = prev != s->device ? hipFailS(hipSetDevice(s->device), "hipSetDevice") : 0;
+  int rc = prev != s->device ? bfHipFail(hipSetDevice(s->device), "hipSetDevice") : 0;
   if (rc) return rc;
   ncclDataType_t const dt = (s->dtype == BFHIP_F32 || s->dtype == BFHIP_C64) ? ncclFloat32 : ncclFloat64;
   size_t const scalarsPerElem = bfDtypeComplex(s->dtype) ? 2 : 1;
@@ -455,13 +451,13 @@ int bfhipShardedApplyTransposeDevice(BfhipSharded *s, void const *dV, size_t nrh
         if (unit == 16) hipLaunchKernelGGL(bfGatherSegmentsKernel<uint4>, dim3(grid), dim3(256), 0, stream, s->dMySegs, s->numMySegs, s->myRows, (uint4 const *)dV, (uint4 *)s->dVr, unitsPerRow);
         else if (unit == 8) hipLaunchKernelGGL(bfGatherSegmentsKernel<uint2>, dim3(grid), dim3(256), 0, stream, s->dMySegs, s->numMySegs, s->myRows, (uint2 const *)dV, (uint2 *)s->dVr, unitsPerRow);
         else hipLaunchKernelGGL(bfGatherSegmentsKernel<uint32_t>, dim3(grid), dim3(256), 0, stream, s->dMySegs, s->numMySegs, s->myRows, (uint32_t const *)dV, (uint32_t *)s->dVr, unitsPerRow);
-        rc = hipFailS(hipGetLastError(), "segment gather launch");
+        rc = bfHipFail(hipGetLastError(), "segment gather launch");
       }
       vr = s->dVr;
     }
   }
   if (!rc) {
-    if (s->mode == BFHIP_SHARD_ROWS && !s->numMySegs) rc = hipFailS(hipMemsetAsync(dZ, 0, (size_t)s->numCols * rowBytes, stream), "hipMemsetAsync");      // a rank without rows contributes zeros
+    if (s->mode == BFHIP_SHARD_ROWS && !s->numMySegs) rc = bfHipFail(hipMemsetAsync(dZ, 0, (size_t)s->numCols * rowBytes, stream), "hipMemsetAsync");      // a rank without rows contributes zeros
     else rc = bfhipApplyTransposeDevice(s->op, vr, nrhs, dZ, stream);
   }
   if (!rc) rc = ncclFail(g.AllReduce(dZ, dZ, (size_t)s->numCols * nrhs * scalarsPerElem, dt, ncclSum, s->comm->comm, stream), "ncclAllReduce");
@@ -476,7 +472,7 @@ int bfhipShardedCovMatvecDevice(BfhipSharded *s, void const *dGammaLam, uint64_t
   if (!s->hasAdjoint || !s->dCov) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "the sharded operator was not compiled with BFHIP_FLAG_ADJOINT");
   int prev = -1;
   (void)hipGetDevice(&prev);
-  int rc = prev != s->device ? hipFailS(hipSetDevice(s->device), "hipSetDevice") : 0;
+  int rc = prev != s->device ? bfHipFail(hipSetDevice(s->device), "hipSetDevice") : 0;
   if (rc) return rc;
   uint64_t const m = s->numRowsGlobal, n = s->numCols, big = m > n ? m : n;
   char *t0 = (char *)s->dCov, *t1 = (char *)s->dCov + big * s->elemSize;
@@ -516,7 +512,7 @@ int bfhipShardedApplyHost(BfhipSharded *s, int transpose, void const *X, size_t 
   if (!nrhs || nrhs > s->maxRhs || ldx < nrhs || ldy < nrhs) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "bad nrhs / leading dimension (the sharded apply was created for %u right-hand sides)", s->maxRhs);
   int prev = -1;
   (void)hipGetDevice(&prev);
-  int rc = prev != s->device ? hipFailS(hipSetDevice(s->device), "hipSetDevice") : 0;
+  int rc = prev != s->device ? bfHipFail(hipSetDevice(s->device), "hipSetDevice") : 0;
   if (rc) return rc;
   uint64_t const n = transpose ? s->numRowsGlobal : s->numCols, m = transpose ? s->numCols : s->numRowsGlobal;
   size_t const es = s->elemSize, hostEs = bfDtypeComplex(s->dtype) ? 16 : 8;
@@ -525,9 +521,9 @@ int bfhipShardedApplyHost(BfhipSharded *s, int transpose, void const *X, size_t 
   if (!hx || !hy) { free(hx); free(hy); if (prev >= 0 && prev != s->device) (void)hipSetDevice(prev); return bfhipFail(BFABI_ERROR_MEMORY_ERROR, "host OOM"); }
   if (es == hostEs) for (uint64_t i = 0; i < n; ++i) memcpy((char *)hx + i * nrhs * es, (char const *)X + i * ldx * es, nrhs * es);
   else for (uint64_t i = 0; i < n; ++i) for (size_t q = 0; q < nrhs * nc; ++q) ((float *)hx)[i * nrhs * nc + q] = (float)((double const *)X)[i * ldx * nc + q];
-  rc = hipFailS(hipMemcpy(s->dHostX, hx, n * nrhs * es, hipMemcpyHostToDevice), "hipMemcpy H2D");
+  rc = bfHipFail(hipMemcpy(s->dHostX, hx, n * nrhs * es, hipMemcpyHostToDevice), "hipMemcpy H2D");
   if (!rc) rc = transpose ? bfhipShardedApplyTransposeDevice(s, s->dHostX, nrhs, s->dHostY, NULL) : bfhipShardedApplyDevice(s, s->dHostX, nrhs, s->dHostY, NULL);
-  if (!rc) rc = hipFailS(hipMemcpy(hy, s->dHostY, m * nrhs * es, hipMemcpyDeviceToHost), "hipMemcpy D2H");
+  if (!rc) rc = bfHipFail(hipMemcpy(hy, s->dHostY, m * nrhs * es, hipMemcpyDeviceToHost), "hipMemcpy D2H");
   if (!rc) {
     if (es == hostEs) for (uint64_t i = 0; i < m; ++i) memcpy((char *)Y + i * ldy * es, (char *)hy + i * nrhs * es, nrhs * es);
     else for (uint64_t i = 0; i < m; ++i) for (size_t q = 0; q < nrhs * nc; ++q) ((double *)Y)[i * ldy * nc + q] = ((float *)hy)[i * nrhs * nc + q];
@@ -539,10 +535,10 @@ int bfhipShardedApplyHost(BfhipSharded *s, int transpose, void const *X, size_t 
 
 int bfhipShardedLastTimes(BfhipSharded *s, double *localMs, double *collectiveMs) {
   if (!s || !s->timed) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "the last sharded apply was not timed (none ran, it failed, or bfhipShardedSetTiming(0))");
-  int rc = hipFailS(hipEventSynchronize(s->e2), "hipEventSynchronize");
+  int rc = bfHipFail(hipEventSynchronize(s->e2), "hipEventSynchronize");
   float a = 0, b = 0;
-  if (!rc) rc = hipFailS(hipEventElapsedTime(&a, s->e0, s->e1), "hipEventElapsedTime");
-  if (!rc) rc = hipFailS(hipEventElapsedTime(&b, s->e1, s->e2), "hipEventElapsedTime");
+  if (!rc) rc = bfHipFail(hipEventElapsedTime(&a, s->e0, s->e1), "hipEventElapsedTime");
+  if (!rc) rc = bfHipFail(hipEventElapsedTime(&b, s->e1, s->e2), "hipEventElapsedTime");
   if (localMs) *localMs = a;
   if (collectiveMs) *collectiveMs = b;
   return rc;
