@@ -569,6 +569,8 @@ def load():
     lib.bfhipChebCovDrawDevice.restype = C.c_int
     lib.bfhipChebCovMomentsDevice.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, vp, vp, vp]
     lib.bfhipChebCovMomentsDevice.restype = C.c_int
+    lib.bfhipChebCovCondCreate.argtypes = [vp, vp, C.c_size_t, vp, C.POINTER(vp), vp]
+    lib.bfhipChebCovCondCreate.restype = C.c_int
     lib.bfhipSetProfileSampling.argtypes = [vp, C.c_uint32]
     lib.bfhipSetProfileSampling.restype = C.c_int
     lib.bfhipPlanGetInfo.argtypes = [vp, C.POINTER(BfhipPlanInfo)]

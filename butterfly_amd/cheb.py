@@ -126,6 +126,22 @@ class ChebCovariance:
         self.set_coefficients(coef)
         return coef
 
+    # ---- what a CovCondition asks of the thing it conditions ----
+    @property
+    def shape(self):
+        return (self.n, self.n)
+
+    def _torch_dtype(self):
+        import torch
+        return torch.float64
+
+    def condition(self, obs, noise_var=None):
+        """A CovCondition for the field z = D p(S) w given noisy values at the vertices `obs` (bfhipChebCovCondCreate):
+        kriging means, posterior samples and their moments, the log marginal likelihood and exact kriging variances, with
+        the coefficients in force now.  set_coefficients afterwards makes it refuse: condition again."""
+        from .operator import ChebCovCondition
+        return ChebCovCondition(self, obs, noise_var)
+
     # ---- device entries: contiguous float64 [n, q] tensors on the object's GPU ----
     def _stream(self):
         import torch

@@ -2,13 +2,16 @@
  * covariance"): the second route of the reference's covariance examples (examples/covariance/cheb_cov.c), which needs no
  * eigenpairs and no butterfly.  Host side: the Chebyshev fit and evaluation, the P1 assembly of a triangle mesh, the
  * object (S = D L D in CSR on the device, folded here) and the drivers of Clenshaw's recurrence, one bfdevChebStep
- * (bfhip_cheb.hip) per degree.  The draw and the moments reuse the kernels of bfhip_cov.hip. */
+ * (bfhip_cheb.hip) per degree.  The draw and the moments reuse the kernels of bfhip_cov.hip.  Last in the file: the
+ * Chebyshev backend of conditioning on observations (bfhipChebCovCondCreate; the object is bfhip_cond.c's, DESIGN.md
+ * section 24). */
 #include <math.h>
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include "bfhip_internal.h"
+#include "bfhip_cond.h"
 #include "../../include/bfhip.h"
 #include "../../include/bfhip_abi.h"
 
@@ -165,6 +168,7 @@ struct BfhipChebCov {
   uint64_t deviceBytes;
   double *coef;
   size_t order;
+  uint64_t generation;          /* bumped by every SetCoefficients: a conditioning object made before it is stale */
   void *dWork;
   uint64_t workBytes;
 };
@@ -248,6 +252,7 @@ int bfhipChebCovSetCoefficients(BfhipChebCov *c, double const *coef, size_t orde
   memcpy(copy, coef, order * sizeof *copy);
   free(c->coef);
   c->coef = copy; c->order = order;
+  ++c->generation;
   return 0;
 }
 
@@ -375,6 +380,73 @@ int bfhipChebCovMomentsDevice(BfhipChebCov *c, uint64_t seed, uint64_t firstSamp
     if ((rc = bfdevCovMoments(z, c->n, b, BFHIP_F64, NULL, dSum, dSumSq, stream))) goto out;
   }
 out:
+  bfDevLeave(&ds);
+  return rc;
+}
+
+/* ------------------------------------------------------------------------
+ * conditioning on observations: the backend of struct BfhipCovCond for B = D p(S)
+ * ---------------------------------------------------------------------- */
+/* The rows of B at the observed vertices, transposed, are X = p(S) D E_obs: unit columns scaled by d in the object's own block
+ * (it is read at every step), one recurrence without the output scaling, the result packed into its columns of Bt. */
+static int chebCondPanel(BfhipCovCond *c, uint64_t const *dRows, uint32_t p, double *Bt, uint32_t ld, uint32_t c0, void *stream) {
+  BfhipChebCov *cheb = c->cheb;
+  double *x = NULL;
+  int rc;
+  if ((rc = chebWork(cheb, 2, p, stream)) || (rc = bfdevChebUnitPanel(c->dWp, cheb->n, p, dRows, cheb->dD, stream)) ||
+      (rc = chebMul(cheb, c->dWp, 0, 0, p, NULL, &x, stream))) return rc;
+  return bfdevCondPack(Bt, cheb->n, ld, c0, x, p, NULL, BFHIP_F64, stream);
+}
+
+static void *chebCondWprime(BfhipCovCond *c) { return c->dWp; }
+
+/* Z = D p(S) W': one polynomial application, as a prior batch costs; there is no permutation, so `scatter` changes nothing */
+static int chebCondField(BfhipCovCond *c, uint32_t b, int scatter, void *dZ, void **packed, void *stream) {
+  BfhipChebCov *cheb = c->cheb;
+  double *z = NULL;
+  int rc;
+  (void)scatter;
+  if ((rc = chebWork(cheb, 2, b, stream)) || (rc = chebMul(cheb, c->dWp, 0, 1, b, dZ, &z, stream))) return rc;
+  if (packed) *packed = z;
+  return 0;
+}
+
+static int chebCondLive(BfhipCovCond const *c) {
+  if (c->cheb->generation == c->chebGeneration) return 0;
+  return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "stale conditioning object: bfhipChebCovSetCoefficients was called after it was made (its rows hold the earlier polynomial); create a new one");
+}
+
+int bfhipChebCovCondCreate(BfhipChebCov *cheb, uint64_t const *obs, size_t numObs, double const *noiseVar, BfhipCovCond **out, void *stream) {
+  if (out) *out = NULL;
+  if (!cheb || !obs || !out) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL argument");
+  if (numObs == 0 || numObs > BFHIP_COND_MAX_OBS) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "numObs out of range (1 .. %u)", BFHIP_COND_MAX_OBS);
+  uint32_t const k = (uint32_t)numObs;
+  BfCondKey *keys = NULL;
+  BfDevScope ds = {0};
+  int rc = condCheckObs(obs, k, noiseVar, &keys);      /* nothing is read through cheb before the checks that need the arguments alone */
+  if (rc) return rc;
+  uint64_t const n = cheb->n;
+  rc = condLookupRange(keys, k, "observed", n);
+  if (!rc && !cheb->order) rc = bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "no coefficients: call bfhipChebCovSetCoefficients first");
+  if (!rc && !bfdevCondFits(n)) rc = bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "conditioning: %llu vertices are more than the contractions' grids take (%llu)",
+                                               (unsigned long long)n, (unsigned long long)BF_COND_MAX_COLS);
+  if (rc) { free(keys); return rc; }
+
+  BfhipCovCond *c = calloc(1, sizeof *c);
+  if (!c) { rc = bfhipFail(BFABI_ERROR_MEMORY_ERROR, "out of host memory"); goto fail; }
+  c->be = (BfCondBackend){ n, n, BFHIP_F64, sizeof(double), 0, chebCondPanel, chebCondWprime, chebCondField, chebCondLive };
+  c->cheb = cheb; c->chebGeneration = cheb->generation; c->k = k; c->device = cheb->device;
+  if ((rc = bfDevEnter(&ds, cheb->device))) goto fail;
+
+  /* ---- the recurrence's two blocks at 64 columns in cheb's workspace, and the object's own W' block ---- */
+  size_t const bytesWp = n * BF_COND_MAX_RHS * sizeof(double);
+  if ((rc = bfdevSync(stream)) || (rc = chebWork(cheb, 2, BF_COND_MAX_RHS, stream)) || (rc = bfdevMalloc(&c->dWp, bytesWp))) goto fail;
+  c->info.factorBytes = bytesWp;
+  if ((rc = condSetup(c, keys, obs, noiseVar, stream))) goto fail;
+  *out = c; c = NULL;
+fail:
+  condRelease(c);
+  free(keys);
   bfDevLeave(&ds);
   return rc;
 }

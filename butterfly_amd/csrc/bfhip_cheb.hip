@@ -99,6 +99,27 @@ __global__ __launch_bounds__(256) void bfChebStepKernel(BfChebStep a, uint32_t l
   }
 }
 
+// The scaled unit panel of conditioning (bfhip_cheb.c: chebCondPanel): U [n x p] = D E for the p <= 64 vertices rows[0 .. p),
+// cleared and filled in one launch.  One thread per element, consecutive threads on consecutive columns; every element
+// is written by its owner alone (d[j] where j == rows[c], else 0), so repeated or out-of-range rows could not reach
+// outside the block (the host refuses both before).
+__global__ __launch_bounds__(256) void bfChebUnitPanelKernel(double *U, uint64_t n, uint32_t p, uint64_t const *rows, double const *d) {
+  uint64_t const total = n * p;
+  for (uint64_t e = (uint64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (uint64_t)gridDim.x * 256) {
+    uint64_t const j = e / p;
+    uint32_t const c = (uint32_t)(e - j * p);
+    U[e] = rows[c] == j ? d[j] : 0.0;
+  }
+}
+
+int bfdevChebUnitPanel(double *U, uint64_t n, uint32_t p, uint64_t const *dRows, double const *d, void *stream) {
+  if (!n || !p) return 0;
+  uint64_t const need = (n * p + 255) / 256;
+  dim3 const grid((uint32_t)(need < 65536 ? need : 65536)), block(256);
+  hipLaunchKernelGGL(bfChebUnitPanelKernel, grid, block, 0, (hipStream_t)stream, U, n, p, dRows, d);
+  return bfHipFail(hipGetLastError(), "Chebyshev unit panel launch");
+}
+
 int bfdevChebStep(BfChebStep const *s, void *stream) {
   if (!s->n || !s->q) return 0;
   uint32_t lg = 0;

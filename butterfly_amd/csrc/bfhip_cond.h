@@ -8,18 +8,43 @@
 #include "bfhip_operator.h"
 #include "../../include/bfhip.h"
 
+typedef struct BfCondKey { uint64_t idx; uint32_t slot; } BfCondKey;      /* an index and the place it came from (condLookupSort) */
+
+/* What the object needs from the field z = B w it conditions (B is m x n): the sizes, the element type of the blocks and four
+ * calls.  Two backends fill it: the butterfly route (bfhip_cond.c: B = P A GammaLam of an operator) and the Chebyshev route
+ * (bfhip_cheb.c: B = D p(S), m = n, float64, no permutation).
+ *   panel   columns c0 .. c0 + p - 1 of the double matrix Bt [n x ld] = the rows of B at dRows[0 .. p), p <= 64, transposed
+ *   wprime  where the packed block W' [n x b] of a pass starts (read at every pass: a scratch may have been grown since)
+ *   field   the b columns of W' into the field block: dZ [m x b] packed (then `scatter` says whether the rows are permuted), or
+ *           with dZ == NULL into scratch of the backend's, whose place *packed receives
+ *   live    NULL, or the refusal of an object whose backend has changed under it (stale Chebyshev coefficients) */
+typedef struct BfCondBackend {
+  uint64_t n, m;
+  uint32_t dtype;
+  size_t elemSize;
+  int columnWeights;             /* B = (...) GammaLam: the likelihood has a gradient in log gamma */
+  int (*panel)(BfhipCovCond *c, uint64_t const *dRows, uint32_t p, double *Bt, uint32_t ld, uint32_t c0, void *stream);
+  void *(*wprime)(BfhipCovCond *c);
+  int (*field)(BfhipCovCond *c, uint32_t b, int scatter, void *dZ, void **packed, void *stream);
+  int (*live)(BfhipCovCond const *c);
+} BfCondBackend;
+
 struct BfhipCovCond {
-  BfhipOperator *op;             /* referenced, like dGammaLam and dRowPerm */
+  BfCondBackend be;
+  BfhipOperator *op;             /* butterfly route: referenced, like dGammaLam and dRowPerm */
   void const *dGammaLam;
-  uint64_t const *dRowPerm;
-  int device;                    /* the operator's, kept so that Free reads nothing through op */
+  uint64_t const *dRowPerm;      /* NULL on the Chebyshev route */
+  BfhipChebCov *cheb;            /* Chebyshev route: referenced */
+  uint64_t chebGeneration;       /* the coefficients Bt was made with */
+  void *dWp;                     /* Chebyshev route: the object's own W' block [n x 64], also the unit panel of a setup pass */
+  int device;                    /* the backend's, kept so that Free reads nothing through op / cheb */
   uint32_t k;
   double *dBt;                   /* [n x k] */
   double *dL;                    /* [k x k]: G + D, then L */
   double *dNoiseVar, *dNoiseSd;  /* [k] each; NULL without noise */
   double *dR;                    /* [k x 64]: R, solved in place into alpha */
   double *dE;                    /* [k x 64]: the draw's noise block */
-  void *dWn;                     /* [n x 64], operator dtype: the draw's normals */
+  void *dWn;                     /* [n x 64], the backend's dtype: the draw's normals */
   double *dPart;                 /* [chunks x k x 64]: partial sums of R */
   BfhipCovCondInfo info;
   /* bfhip_condlik.c: allocated by the first likelihood / variance call, not counted in info.factorBytes */
@@ -33,6 +58,15 @@ struct BfhipCovCond {
 
 /* releases what bfhip_condlik.c allocated (the device is drained by the caller) */
 BF_HIDDEN void condLikRelease(BfhipCovCond *c);
+/* the whole object (bfhip_cond.c; the device is drained by the caller) */
+BF_HIDDEN void condRelease(BfhipCovCond *c);
+/* the refusals the two constructors share that need the arguments alone, in this order: a repeated index, a bad noiseVar entry.
+ * *keys as condLookupSort leaves them (free() them), NULL after a refusal */
+BF_HIDDEN int condCheckObs(uint64_t const *obs, uint32_t k, double const *noiseVar, BfCondKey **keys);
+/* the rest of a Create once c->be, c->k and c->device are set, the device is entered and the backend's scratch holds passes of 64
+ * columns: the object's blocks, Bt by panels, G + D, its Cholesky factor; c->info (factorBytes is ADDED to).  The caller releases
+ * c after a failure */
+BF_HIDDEN int condSetup(BfhipCovCond *c, BfCondKey const *keys, uint64_t const *obs, double const *noiseVar, void *stream);
 
 /* The rows i_t with dRowPerm[i_t] = idx[t], t < count (bfhip_cond.c): Create looks up its observed indices with it, the variance its
  * queries; `what` ("observed" / "query") is the word the refusals use.  In steps, because each caller has refusals and device work
@@ -41,7 +75,6 @@ BF_HIDDEN void condLikRelease(BfhipCovCond *c);
  *   condLookupRange  an index >= numRows is refused
  *   condLookupRows   dRows [count], allocated by the caller on the current device: dRowPerm inverted there (refused unless every
  *                    index is hit exactly once; drains `stream`), or idx itself without a permutation */
-typedef struct BfCondKey { uint64_t idx; uint32_t slot; } BfCondKey;
 BF_HIDDEN int condLookupSort(uint64_t const *idx, uint32_t count, char const *what, BfCondKey **keys);
 BF_HIDDEN int condLookupRange(BfCondKey const *keys, uint32_t count, char const *what, uint64_t numRows);
 BF_HIDDEN int condLookupRows(BfCondKey const *keys, uint64_t const *idx, uint32_t count, char const *what, uint64_t const *dRowPerm, uint64_t numRows, void *dRows,

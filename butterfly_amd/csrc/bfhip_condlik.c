@@ -40,7 +40,7 @@ static int likEnsure(BfhipCovCond *c, uint64_t slots, int colSq, void *stream) {
     if ((rc = bfdevMalloc((void **)&c->dLinv, tiles * BF_LIK_NB * BF_LIK_NB * sizeof(double)))) return rc;
     if ((rc = bfdevLikInvDiag(c->dLinv, c->dL, c->k, stream))) { bfdevFree(c->dLinv); c->dLinv = NULL; return rc; }
   }
-  if (colSq && !c->dColSq && (rc = bfdevMalloc((void **)&c->dColSq, (c->op->plan.numCols + c->k) * sizeof(double)))) return rc;
+  if (colSq && !c->dColSq && (rc = bfdevMalloc((void **)&c->dColSq, (c->be.n + c->k) * sizeof(double)))) return rc;
   return 0;
 }
 
@@ -51,11 +51,12 @@ int bfhipCovCondLogLikelihoodDevice(BfhipCovCond *c, double const *dY, double *d
   uint64_t const ws = opt ? opt->workspaceBytes : 0, strip = stripBytes(c);
   if (ws && ws < strip)
     return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "workspaceBytes %llu is below one strip (%llu bytes)", (unsigned long long)ws, (unsigned long long)strip);
+  if (dGradLogGamma && !c->be.columnWeights)
+    return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "dGradLogGamma: the field of this object has no per-column weights (Chebyshev route)");
   int rc;
   BfDevScope ds;
-  if ((rc = bfDevEnter(&ds, c->device))) return rc;
-  BfhipOperator *op = c->op;
-  uint64_t const n = op->plan.numCols;
+  if ((c->be.live && (rc = c->be.live(c))) || (rc = bfDevEnter(&ds, c->device))) return rc;
+  uint64_t const n = c->be.n;
   uint32_t const k = c->k;
   /* no more slots than the wider of the two solves has strips */
   uint64_t const most = ((n > k ? n : k) + BF_LIK_STRIP - 1) / BF_LIK_STRIP;
@@ -64,7 +65,7 @@ int bfhipCovCondLogLikelihoodDevice(BfhipCovCond *c, double const *dY, double *d
   if (!slots) slots = 1;
   if ((dGradLogGamma || dGradNoise) && (rc = likEnsure(c, slots, 1, stream))) goto done;
   /* alpha = K^-1 y into c->dR: the first two steps of the mean's pass (W = 0, E = 0, one column) */
-  if ((rc = bfdevCondResidual(c->dR, c->dPart, c->dBt, n, k, dY, NULL, 1, op->plan.dtype, NULL, 1, 1, stream))) goto done;
+  if ((rc = bfdevCondResidual(c->dR, c->dPart, c->dBt, n, k, dY, NULL, 1, c->be.dtype, NULL, 1, 1, stream))) goto done;
   if ((rc = bfdevCondSolve(c->dL, k, c->dR, 1, stream))) goto done;
   if ((rc = bfdevLikValue(dValue, c->dL, k, dY, c->dR, stream))) goto done;
   if (dGradLogGamma) {
@@ -90,10 +91,9 @@ int bfhipCovCondVarianceDevice(BfhipCovCond *c, uint64_t const *query, size_t nu
   int rc = condLookupSort(query, nq, "query", &keys);
   if (rc) return rc;
   /* from here on the object is read; a bad index is refused before the device is touched */
-  if ((rc = condLookupRange(keys, nq, "query", c->op->plan.numRows))) { free(keys); return rc; }
+  if ((rc = condLookupRange(keys, nq, "query", c->be.m)) || (c->be.live && (rc = c->be.live(c)))) { free(keys); return rc; }
 
-  BfhipOperator *op = c->op;
-  uint64_t const m = op->plan.numRows, n = op->plan.numCols;
+  uint64_t const m = c->be.m, n = c->be.n;
   uint64_t const chunks = (n + BF_COND_CHUNK - 1) / BF_COND_CHUNK;
   uint32_t const k = c->k, Q = BF_COND_MAX_RHS;
   void *dRows = NULL;
@@ -115,10 +115,10 @@ int bfhipCovCondVarianceDevice(BfhipCovCond *c, uint64_t const *query, size_t nu
   /* ---- the rows i_t with dRowPerm[i_t] = query[t] ---- */
   if ((rc = bfdevMalloc(&dRows, (size_t)nq * 8)) || (rc = condLookupRows(keys, query, nq, "query", c->dRowPerm, m, dRows, stream))) goto done;
 
-  /* ---- panels of <= 64 queries: r^T by one adjoint apply, its squares, Bt^T r, the strip solve ---- */
+  /* ---- panels of <= 64 queries: r^T by the backend's panel (one adjoint apply), its squares, Bt^T r, the strip solve ---- */
   for (uint32_t t0 = 0; t0 < nq; t0 += Q) {
     uint32_t const p = nq - t0 < Q ? nq - t0 : Q;
-    if ((rc = condAdjointPanel(op, c->dGammaLam, (uint64_t const *)dRows + t0, p, c->dVarBlk, p, 0, stream)) ||
+    if ((rc = c->be.panel(c, (uint64_t const *)dRows + t0, p, c->dVarBlk, p, 0, stream)) ||
         (rc = bfdevVarPriorPart(c->dVarPart, c->dVarBlk, n, p, stream))) goto done;
     if (dPost) {
       /* R = 0 - Bt^T r (the sign does not reach the squares), then ||L^-1 R||^2 per column */

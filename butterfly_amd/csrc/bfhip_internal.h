@@ -504,6 +504,8 @@ typedef struct BfChebStep {
   double ck, alpha, beta;
 } BfChebStep;
 int bfdevChebStep(BfChebStep const *s, void *stream);
+/* U [n x p] = D E: U[j, c] = d[j] where j == rows[c], else 0 (the whole block is written; rows [p] on the device, p <= 64) */
+int bfdevChebUnitPanel(double *U, uint64_t n, uint32_t p, uint64_t const *dRows, double const *d, void *stream);
 
 /* device-resident GMRES building blocks (bfhip_gmres.hip; complex128; bfhip_gmres.c drives them).
  * Vectors are n x nrhs row-major; reductions are per RHS column, two-stage and

@@ -885,3 +885,25 @@ class CovCondition:
         ptr = HipOperator._ptr
         check(self._lib.bfhipCovCondVarianceDevice(self._h, q.ctypes.data if q.size else None, q.size, ptr(vprior), ptr(vpost), self._stream()))
         return (vpost, vprior) if (prior and post) else (vpost if post else vprior)
+
+
+class ChebCovCondition(CovCondition):
+    """The CovCondition of the Chebyshev route (bfhipChebCovCondCreate): the field z = D p(S) w of a ChebCovariance given noisy
+    values at the mesh vertices `obs`.  Every method of CovCondition works on it, on float64 [n, q] blocks in mesh order;
+    log_likelihood(grad_log_gamma=True) raises the library's refusal (this route has no per-column weights), and so does every
+    method but info and close once set_coefficients has been called on the ChebCovariance: make a new one then.  The object
+    keeps its ChebCovariance alive."""
+
+    def __init__(self, cheb, obs, noise_var=None):
+        import torch
+        self._op, self._lib, self._h = cheb, cheb._lib, C.c_void_p()       # _op: the shape and element type of the blocks
+        self._gamma = self._perm = None
+        obs = np.ascontiguousarray(np.asarray(obs, dtype=np.uint64))
+        nv = None if noise_var is None else np.ascontiguousarray(np.asarray(noise_var, dtype=np.float64))
+        if obs.ndim != 1 or (nv is not None and nv.shape != obs.shape):
+            raise ValueError("obs and noise_var are one-dimensional and of one length")
+        self._dev = torch.device("cuda", cheb._dev)
+        s = torch.cuda.current_stream(self._dev)
+        check(self._lib.bfhipChebCovCondCreate(cheb.handle, obs.ctypes.data, obs.size, nv.ctypes.data if nv is not None else None,
+                                               C.byref(self._h), C.c_void_p(s.cuda_stream)))
+        self.num_obs = int(obs.size)

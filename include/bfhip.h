@@ -821,6 +821,33 @@ int bfhipChebCovDrawDevice(BfhipChebCov *c, uint64_t seed, uint64_t firstSample,
 int bfhipChebCovMomentsDevice(BfhipChebCov *c, uint64_t seed, uint64_t firstSample, uint64_t numSamples, uint32_t batch,
                               double *dSum, double *dSumSq, void *stream);
 
+/* Conditioning the Chebyshev route on observations: a BfhipCovCond (above, "conditioning on observations") for the field
+ * z = B w, B = D p(S), given noisy values at the mesh vertices obs[] (host, distinct, < n, mesh order: there is no
+ * permutation).  The observed rows of B, transposed, are X = p(S) D E_obs [n x k]: panels of <= 64 unit columns scaled by d
+ * (one small kernel), one recurrence each without the output scaling, packed into the stored n x k double matrix; then
+ * G = X^T X + D, its Cholesky factor and every entry of the object are the butterfly route's, kernel for kernel.  The
+ * correction W' = W + X alpha happens in w space, so a batch of posterior samples costs ONE polynomial application, as a
+ * prior batch does.  BfhipCovCondInfo: setupApplies = the number of panels; factorBytes counts everything Create allocates,
+ * the object's own W' block [n x 64] included (X alone is n * numObs doubles: a failed allocation is MEMORY_ERROR and
+ * leaks nothing).
+ *
+ * Every block is float64: dW, dZ [n x nrhs], moments [n].  Draw: w_s[j] = N(seed, (firstSample + s) n + j), the stream of
+ * bfhipChebCovDrawDevice; the noise as on the butterfly route.  Variance: queries are vertex indices,
+ * prior = ||p(S) D e_i||^2, post = prior - ||L^-1 X^T x_i||^2.  LogLikelihood: value and dGradNoise; dGradLogGamma != NULL is
+ * refused (INVALID_ARGUMENTS): this route has no per-column weights.
+ *
+ * `cheb` is referenced: it must outlive the object (bfhipCovCondFree reads nothing through it), and the recurrence runs in
+ * cheb's workspace, which Create grows to two blocks of 64 columns.  X holds the polynomial in force at Create:
+ * bfhipChebCovSetCoefficients on `cheb` afterwards makes the object STALE -- sample, mean, draw, moments, likelihood and
+ * variance then refuse with INVALID_ARGUMENTS and a message that says so; Free and GetInfo still work.  Create a new one.
+ *
+ * Errors, raised before the device is touched, in bfhipCovCondCreate's order: INVALID_ARGUMENTS (NULL cheb, obs or out;
+ * numObs == 0 or > BFHIP_COND_MAX_OBS; a repeated observed index; a noiseVar entry negative or not finite), OUT_OF_RANGE (an
+ * observed index >= n), INVALID_ARGUMENTS (no coefficients set; n beyond 65535 x 1024).  A Cholesky pivot <= 0 or not
+ * finite: RUNTIME_ERROR, as there. */
+int bfhipChebCovCondCreate(BfhipChebCov *cheb, const uint64_t *obs, size_t numObs, const double *noiseVar, BfhipCovCond **out,
+                           void *stream);
+
 /* ---- plan inspection (no device needed) ---------------------------------- */
 /* The flattened per-stage layout, as the kernels see it.  Valid only for an
  * operator compiled with BFHIP_FLAG_PLAN_ONLY (the host mirrors are dropped
