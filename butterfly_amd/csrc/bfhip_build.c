@@ -199,7 +199,7 @@ static void batchSizes(BfhipHelm2Problem const *prob, uint64_t const *idx, uint6
  * launches, two batched GEMM launches:
  *   plain:  A V = W (orthogonal columns, norms sigma):  T = diag(1/sigma^2) W^H B,  X = V T;
  *   QR:     A P = Q R in place, B <- Q^H B, and the Jacobi kernel gets Xq = (R[0:r] P^T)^H (me x r) instead of A:
- *           Xq V1 = W  =>  X = W diag(1/sigma^2) V1^H (Q^H B)[0:r]  (bfhip_build.hip).
+ *           Xq V1 = W  =>  X = W diag(1/sigma^2) V1^H (Q^H B)[0:r]  (bfhip_lstsq.hip).
  * qrOut (host [count] or NULL): the QR stage's rank of each problem (me when the problem skips it), with BF_QR_NONFINITE
  * when A was not finite; routes (host [count] or NULL): the route each problem took. */
 typedef struct BfLsJob {

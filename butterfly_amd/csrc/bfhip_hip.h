@@ -12,4 +12,12 @@ static inline int bfHipFail(hipError_t e, char const *what) {
   return bfhipFail(code, "%s: %s", what, hipGetErrorString(e));
 }
 
+/* *d = a fresh device copy of h[0..count) (the builder's problem lists and tables) */
+template <typename T> static inline int uploadArrayB(T **d, T const *h, uint64_t count, char const *what) {
+  *d = NULL;
+  int rc = bfHipFail(hipMalloc((void **)d, count * sizeof(T)), what);
+  if (rc) return rc;
+  return bfHipFail(hipMemcpy(*d, h, count * sizeof(T), hipMemcpyHostToDevice), what);
+}
+
 #endif

@@ -15,6 +15,13 @@
 extern "C" {
 #endif
 
+/* a function the C host and a kernel both call (bfJacobiTile) */
+#ifdef __HIPCC__
+#define BF_HOST_DEVICE __host__ __device__
+#else
+#define BF_HOST_DEVICE
+#endif
+
 /* ------------------------------------------------------------------------
  * error plumbing
  * ---------------------------------------------------------------------- */
@@ -544,7 +551,8 @@ int bfdevRefineUpdate(void const *Xin, void const *D, double const *scale, void 
 int bfdevMemcpyD2HAsync(void *dst, void const *src, size_t bytes, void *stream);
 
 /* ------------------------------------------------------------------------
- * Builder device layer (bfhip_build.hip; driven by bfhip_build.c).  All
+ * Builder device layer (bfhip_build.hip: kernel evaluation, pack, dense check; bfhip_lstsq.hip: the truncated
+ * least squares -- QR, Jacobi SVD, GEMM; driven by bfhip_build.c).  All
  * matrices are complex128, column-major; offsets are in complex elements
  * relative to the base pointer named per call.
  * ---------------------------------------------------------------------- */
@@ -637,28 +645,46 @@ static inline uint32_t bfQrcpLdsClass(uint32_t need) {
   while (c + 1 < BF_QR_LDS_CLASSES && bfQrcpLdsCap(c) < need) ++c;
   return c;
 }
+/* LDS tile of the four classes of the plain Jacobi kernel: the router picks the class, the launcher asks for its bytes */
+#define BF_JACOBI_LDS_CLASSES 4
+static inline uint32_t bfJacobiLdsCap(uint32_t cls) {
+  static uint32_t const cap[BF_JACOBI_LDS_CLASSES] = {16u << 10, 32u << 10, 64u << 10, BF_JACOBI_LDS_MAX};
+  return cap[cls];
+}
+/* Geometry of the plain Jacobi kernel's tile of ldsBytes for an mt x me problem, the one copy the router and
+ * bfJacobiKernel share.  A stacked column [a_j; v_j] has mt + me rows; Rp, its stride in 16-byte units, is odd so that
+ * the lane groups of a wavefront spread over the banks.  The tile holds an even number C >= 2 of them: blocks of
+ * b = min(C / 2, ceil(me / 2)) columns, a pair of blocks at a time.  resident: at most two blocks, so everything is
+ * loaded once and slot = column.  (me = 0 gives b = 0 and counts as resident; the kernel returns before it asks.) */
+typedef struct BfJacobiTile { uint32_t Rp, b, resident; } BfJacobiTile;
+BF_HOST_DEVICE static inline BfJacobiTile bfJacobiTile(uint32_t ldsBytes, uint32_t mt, uint32_t me) {
+  BfJacobiTile t;
+  t.Rp = (mt + me) | 1u;
+  uint32_t C = (ldsBytes / 16u) / t.Rp;
+  C = C < 2 ? 2 : C & ~1u;
+  t.b = C / 2 < (me + 1) / 2 ? C / 2 : (me + 1) / 2;
+  t.resident = t.b ? (me + t.b - 1) / t.b <= 2 : 1;
+  return t;
+}
 /* the Jacobi stage of an mt x me problem (after the QR stage: me x rank) */
 static inline void bfJacobiRoute(uint32_t mt, uint32_t me, BfLstSqOpts const *o, BfLstSqRoute *r) {
-  static uint32_t const lds[4] = {16u << 10, 32u << 10, 64u << 10, BF_JACOBI_LDS_MAX};
-  uint64_t const R = (uint64_t)mt + me, Rp = R | 1u;
+  uint64_t const R = (uint64_t)mt + me, Rp = R | 1u;       /* 64 bits: `fits` is asked of every shape */
   r->w = 64; r->threads = 1024; r->ldsClass = 0; r->resident = 0;
   int const fits = !(2 * Rp * 16 > BF_JACOBI_LDS_MAX || me > BF_JACOBI_MAX_COLS);
   if (!o->forceGlobal && me <= BF_GRAM_MAX_COLS && (!fits || R >= (uint64_t)o->gramMin)) { r->jacobi = BF_JACOBI_GRAM; r->threads = 512; return; }
   if (!fits || o->forceGlobal) { r->jacobi = BF_JACOBI_GLOBAL; return; }
   r->jacobi = BF_JACOBI_PLAIN;
   uint64_t const meEven = me + (me & 1u);
-  uint32_t lc = 3;
-  for (uint32_t c = 0; c < 3; ++c)
-    if (meEven * Rp * 16 <= lds[c]) { lc = c; break; }
-  uint32_t C = (uint32_t)((lds[lc] / 16u) / Rp);           /* stacked columns the tile holds (bfJacobiKernel) */
-  C = C < 2 ? 2 : C & ~1u;
-  uint32_t const b = C / 2 < (me + 1) / 2 ? C / 2 : (me + 1) / 2;
+  uint32_t lc = BF_JACOBI_LDS_CLASSES - 1;
+  for (uint32_t c = 0; c + 1 < BF_JACOBI_LDS_CLASSES; ++c)
+    if (meEven * Rp * 16 <= bfJacobiLdsCap(c)) { lc = c; break; }
+  BfJacobiTile const t = bfJacobiTile(bfJacobiLdsCap(lc), mt, me);
   r->ldsClass = lc;
   r->threads = me > 64 ? 1024 : 256;
   uint32_t w = 64;
-  while (w > 4 && (r->threads / w < b || w / 2 >= mt)) w >>= 1;
+  while (w > 4 && (r->threads / w < t.b || w / 2 >= mt)) w >>= 1;
   r->w = w;
-  r->resident = b ? (me + b - 1) / b <= 2 : 1;
+  r->resident = t.resident;
 }
 /* the whole route of an mt x me least-squares problem; `rank`: what the QR stage leaves for the Jacobi stage (if it runs) */
 static inline void bfLstSqRoute(uint32_t mt, uint32_t me, uint32_t rank, BfLstSqOpts const *o, BfLstSqRoute *r) {

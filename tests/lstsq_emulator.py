@@ -1,4 +1,4 @@
-"""A numpy fp64 restatement of what the device does for one least-squares problem (bfhip_build.hip: bfQrcpKernel,
+"""A numpy fp64 restatement of what the device does for one least-squares problem (bfhip_lstsq.hip: bfQrcpKernel,
 bfJacobiKernel / bfJacobiFinish, bfJacobiFreeze, the two GEMMs), in the manner of tests/plan_emulator.py: the round-robin
 order, the rotation of bfJacobiAngle, the freezing of columns below dim eps x the largest column, the QR stop rule and
 the truncation rule.  The arithmetic is numpy's (not the device's summation order), so results agree with the device to

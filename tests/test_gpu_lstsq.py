@@ -1,4 +1,4 @@
-"""The device builder's least-squares kernels (bfQrcpKernel, bfJacobiKernel<W>, bfJacobiGramKernel, bfJacobiGlobalKernel,
+"""The device builder's least-squares kernels (bfhip_lstsq.hip: bfQrcpKernel, bfJacobiKernel<W>, bfJacobiGramKernel, bfJacobiGlobalKernel,
 bfGemmKernel) through bfhipLstSqTruncated, on the designed cases of tests/lstsq_catalogue.py: every case on its declared
 route and on the forced alternatives it fits, against the long-double reference and the bounds of tests/lstsq_ref.py."""
 import numpy as np

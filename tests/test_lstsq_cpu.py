@@ -26,12 +26,13 @@ def _small(c):
 
 def _plain_classes_by_brute_force():
     """Every (W, threads, LDS class, resident) of the plain Jacobi kernel the router emits, over every shape the kernel
-    takes (me <= 2304, mt + me <= 4607) with the Gram form and the QR stage switched off."""
+    takes (me <= 2304, mt + me <= 4607) with the Gram form and the QR stage switched off, each with the shape (mt, me) of the
+    smallest mt me^2 that reaches it (among equals: the fewest columns)."""
     from butterfly_amd import _capi
     from butterfly_amd.operator import _lstsq_options
     lib = _capi.load()
     opts = _lstsq_options(qr_min=cat.HUGE, gram_min=cat.HUGE, force_global=0)
-    found = set()
+    found = {}
     for me in range(1, 2305):
         mts = np.arange(1, 4608 - me + 1, dtype=np.uint32)
         sh = np.zeros((len(mts), 3), np.uint32)
@@ -39,14 +40,36 @@ def _plain_classes_by_brute_force():
         out = (_capi.BfhipLstSqRoute * len(mts))()
         assert lib.bfhipLstSqRoutes(len(mts), sh.ctypes.data, None, C.byref(opts), out) == 0
         r = np.frombuffer(out, dtype=np.uint32).reshape(-1, 8)
-        r = r[r[:, 3] == 0]
-        found |= set(map(tuple, r[:, 4:8].tolist()))
+        plain = r[:, 3] == 0
+        classes, first = np.unique(r[plain, 4:8], axis=0, return_index=True)       # mts ascend: the first is the shortest
+        for k, mt in zip(map(tuple, classes.tolist()), mts[plain][first].tolist()):
+            if k not in found or mt * me * me < found[k][0] * found[k][1] ** 2:
+                found[k] = (mt, me)
     return found
+
+
+# (W, threads, LDS class, resident) of the plain kernel -> the smallest shape (mt, me) routed to it, as the router stood
+# when the tile geometry was its own copy of the kernel's: bfJacobiTile, which both now call, must reproduce it
+_PLAIN_ROUTES = {
+    (4, 256, 0, 1): (1, 1), (4, 256, 1, 1): (1, 31), (4, 256, 2, 1): (1, 45), (4, 256, 3, 1): (1, 63),
+    (4, 1024, 3, 0): (1, 95), (4, 1024, 3, 1): (1, 65), (8, 256, 0, 1): (5, 1), (8, 256, 1, 1): (5, 29),
+    (8, 256, 2, 1): (5, 43), (8, 256, 3, 0): (221, 35), (8, 256, 3, 1): (5, 61), (8, 1024, 3, 0): (5, 93),
+    (8, 1024, 3, 1): (5, 65), (16, 256, 0, 1): (9, 1), (16, 256, 1, 1): (9, 27), (16, 256, 2, 1): (97, 17),
+    (16, 256, 3, 0): (441, 19), (16, 256, 3, 1): (211, 17), (16, 1024, 3, 0): (9, 91), (16, 1024, 3, 1): (9, 65),
+    (32, 256, 0, 1): (17, 1), (32, 256, 1, 1): (93, 9), (32, 256, 2, 1): (195, 9), (32, 256, 3, 0): (757, 11),
+    (32, 256, 3, 1): (401, 9), (32, 1024, 3, 0): (17, 123), (64, 256, 0, 1): (33, 1), (64, 256, 1, 1): (511, 1),
+    (64, 256, 2, 1): (1023, 1), (64, 256, 3, 0): (2301, 3), (64, 256, 3, 1): (2047, 1), (64, 1024, 3, 0): (207, 65),
+}
 
 
 def test_the_catalogue_reaches_every_reachable_route():
     from butterfly_amd.operator import lstsq_routes
-    reachable = _plain_classes_by_brute_force()
+    representatives = _plain_classes_by_brute_force()
+    assert representatives == _PLAIN_ROUTES
+    for (w, threads, lds, res), (mt, me) in _PLAIN_ROUTES.items():
+        r = lstsq_routes([(mt, me, 1)], **cat.PLAIN)[0]
+        assert (r["jacobi"], r["w"], r["threads"], r["ldsClass"], r["resident"]) == (0, w, threads, lds, res), (mt, me, r)
+    reachable = set(representatives)
     assert reachable == set(cat.PLAIN_SHAPES)
     # the unreachable (W, threads, LDS) classes: 1024 threads only with the 144 KiB tile (catalogue docstring)
     wtl = {(w, t, l) for w, t, l, _ in reachable}
