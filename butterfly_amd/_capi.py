@@ -159,6 +159,24 @@ class BfhipChebCovInfo(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_ if n not in ("structSize", "reserved")}
 
 
+EIGS_MASS_NORMALISED = 1   # BFHIP_EIGS_MASS_NORMALISED
+EIGS_NO_GUARD = 2          # BFHIP_EIGS_NO_GUARD
+
+
+class BfhipEigsOptions(C.Structure):
+    _fields_ = [("structSize", C.c_uint32), ("guard", C.c_uint32), ("degree", C.c_uint32), ("maxIter", C.c_uint32), ("tol", C.c_double),
+                ("seed", C.c_uint64), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class BfhipEigsInfo(C.Structure):
+    _fields_ = [("structSize", C.c_uint32), ("iterations", C.c_uint32), ("converged", C.c_uint32), ("blockColumns", C.c_uint32),
+                ("maxDegreeUsed", C.c_uint32), ("reserved", C.c_uint32), ("operatorColumns", C.c_uint64), ("workspaceBytes", C.c_uint64),
+                ("maxResidual", C.c_double), ("lamMax", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n not in ("structSize", "reserved")}
+
+
 CHEB_DENSITY_FN = C.CFUNCTYPE(C.c_double, C.c_double, C.c_void_p)      # double (*f)(double, void *)
 
 
@@ -571,6 +589,8 @@ def load():
     lib.bfhipChebCovMomentsDevice.restype = C.c_int
     lib.bfhipChebCovCondCreate.argtypes = [vp, vp, C.c_size_t, vp, C.POINTER(vp), vp]
     lib.bfhipChebCovCondCreate.restype = C.c_int
+    lib.bfhipChebCovEigsDevice.argtypes = [vp, C.POINTER(BfhipEigsOptions), C.c_size_t, vp, vp, vp, C.c_size_t, C.POINTER(BfhipEigsInfo), vp]
+    lib.bfhipChebCovEigsDevice.restype = C.c_int
     lib.bfhipSetProfileSampling.argtypes = [vp, C.c_uint32]
     lib.bfhipSetProfileSampling.restype = C.c_int
     lib.bfhipPlanGetInfo.argtypes = [vp, C.POINTER(BfhipPlanInfo)]

@@ -190,3 +190,33 @@ class ChebCovariance:
         ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
         check(self._lib.bfhipChebCovMomentsDevice(self._h, int(seed), int(first), int(num), int(batch), ptr(sum), ptr(sumsq), self._stream()))
         return sum, sumsq
+
+    def eigs(self, nev, guard=None, degree=None, tol=None, max_iter=None, seed=0, mass_normalised=False, ldu=None, raise_on_limit=True):
+        """The nev lowest eigenpairs of the lumped-mass pencil L phi = lambda M phi (bfhipChebCovEigsDevice): Chebyshev-filtered
+        subspace iteration on the device, synchronous.  Returns (lam: numpy [nev] ascending, U: float64 [n, nev] on the GPU,
+        info: dict with the residuals under "residual" and the return code under "code").  U has orthonormal columns
+        (eigenvectors of S = D L D); with mass_normalised it is Phi = D U, Phi^T M Phi = I.  guard: extra block columns
+        (None: the default, 0: none, legal only when nev == n).  ldu > nev returns U as the leading columns of a zero-filled
+        [n, ldu] tensor.  raise_on_limit=False returns the best pairs found instead of raising when max_iter was reached."""
+        import torch
+        nev = int(nev)
+        opt = _capi.BfhipEigsOptions()
+        opt.structSize = C.sizeof(opt)
+        opt.guard = 0 if guard is None else int(guard)
+        opt.degree = 0 if degree is None else int(degree)
+        opt.maxIter = 0 if max_iter is None else int(max_iter)
+        opt.tol = 0.0 if tol is None else float(tol)
+        opt.seed = int(seed)
+        opt.flags = (_capi.EIGS_MASS_NORMALISED if mass_normalised else 0) | (_capi.EIGS_NO_GUARD if guard is not None and int(guard) == 0 else 0)
+        info = _capi.BfhipEigsInfo()
+        info.structSize = C.sizeof(info)
+        ldu = max(nev, 1) if ldu is None else int(ldu)
+        lam, res = np.zeros(max(nev, 1)), np.zeros(max(nev, 1))
+        full = torch.zeros((self.n, ldu), dtype=torch.float64, device=torch.device("cuda", self._dev))
+        rc = self._lib.bfhipChebCovEigsDevice(self._h, C.byref(opt), nev, lam.ctypes.data, res.ctypes.data, C.c_void_p(full.data_ptr()), ldu,
+                                              C.byref(info), self._stream())
+        if rc != 0 and (raise_on_limit or info.blockColumns == 0):
+            check(rc)
+        out = info.as_dict()
+        out["residual"], out["code"] = res[:nev], rc
+        return lam[:nev], full[:, :nev], out

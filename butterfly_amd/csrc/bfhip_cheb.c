@@ -160,19 +160,7 @@ int bfhipTrimeshLboFem(uint64_t numVerts, double const *verts, uint64_t numFaces
 /* ------------------------------------------------------------------------
  * the object
  * ---------------------------------------------------------------------- */
-struct BfhipChebCov {
-  int device;
-  uint64_t n, nnz;
-  double lamMax;
-  void *dRowptr, *dColind, *dVal, *dD;
-  uint64_t deviceBytes;
-  double *coef;
-  size_t order;
-  uint64_t generation;          /* bumped by every SetCoefficients: a conditioning object made before it is stale */
-  void *dWork;
-  uint64_t workBytes;
-};
-
+/* struct BfhipChebCov: bfhip_internal.h (bfhip_eigs.c reads it too) */
 void bfhipChebCovFree(BfhipChebCov **pc) {
   if (!pc || !*pc) return;
   BfhipChebCov *c = *pc;

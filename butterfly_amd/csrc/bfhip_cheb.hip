@@ -14,12 +14,9 @@
 #include "bfhip_internal.h"
 #include "../../include/bfhip_abi.h"
 #include "bfhip_hip.h"
+#include "bfhip_cheb_gather.h"          // BF_CHEB_GATHERS and the row gather (shared with bfhip_eigs.hip)
 
 #define BF_CHEB_MAX_GRID (1u << 20)     // workgroups per launch; the rest is walked with a grid stride
-#ifndef BF_CHEB_GATHERS
-#define BF_CHEB_GATHERS 8               // gathered rows in flight per output row, a power of two (tools/cheb_cov_rate.py)
-#endif
-static_assert(BF_CHEB_GATHERS >= 1 && BF_CHEB_GATHERS <= 64 && (BF_CHEB_GATHERS & (BF_CHEB_GATHERS - 1)) == 0, "BF_CHEB_GATHERS: a power of two <= 64");
 
 // Threads: lanes = min(64, next power of two >= q) neighbouring lanes own row i, so a wavefront covers 64 / lanes rows and
 // a workgroup of 256 covers 256 / lanes.  A lane owns columns lane, lane + lanes, ... : at q <= 64 one column, beyond
@@ -38,10 +35,8 @@ static_assert(BF_CHEB_GATHERS >= 1 && BF_CHEB_GATHERS <= 64 && (BF_CHEB_GATHERS 
 // Rows owned by fewer lanes than a group has pairs (q <= BF_CHEB_GATHERS / 2) load them per lane: there a wavefront
 // covers 16 rows or more and the instructions are shared by all of them.
 __global__ __launch_bounds__(256) void bfChebStepKernel(BfChebStep a, uint32_t lanesLog2) {
-  constexpr int G = BF_CHEB_GATHERS;
   uint32_t const lanes = 1u << lanesLog2, lane = threadIdx.x & (lanes - 1), rowsPerWg = 256u >> lanesLog2;
   uint64_t const q = a.q;
-  bool const shared = lanes >= (uint32_t)G;
   for (uint64_t i = (uint64_t)blockIdx.x * rowsPerWg + (threadIdx.x >> lanesLog2); i < a.n; i += (uint64_t)gridDim.x * rowsPerWg) {
     uint64_t const beg = a.rowptr[i], end = a.rowptr[i + 1];
     double const ws = a.wScale ? a.wScale[i] : 1.0, os = a.outScale ? a.outScale[i] : 1.0;
@@ -59,36 +54,7 @@ __global__ __launch_bounds__(256) void bfChebStepKernel(BfChebStep a, uint32_t l
       if (a.wScale) r *= ws;
       r *= a.ck;
       if (a.b1) {
-        double acc = 0;
-        for (uint64_t j = beg; j < end; j += G) {
-          double v[G];
-          uint32_t col[G];
-          if (shared) {
-            uint64_t const mine = j + (lane & (G - 1)) < end ? j + (lane & (G - 1)) : end - 1;
-            double const pv = a.val[mine];
-            uint32_t const pc = a.colind[mine];
-#pragma unroll
-            for (int t = 0; t < G; ++t) {
-              v[t] = __shfl(pv, t, (int)lanes);
-              col[t] = __shfl(pc, t, (int)lanes);
-            }
-          } else {
-#pragma unroll
-            for (int t = 0; t < G; ++t) {
-              uint64_t const jj = j + t < end ? j + t : end - 1;
-              v[t] = a.val[jj];
-              col[t] = a.colind[jj];
-            }
-          }
-          if (live) {
-            double x[G];
-#pragma unroll
-            for (int t = 0; t < G; ++t) x[t] = j + t < end ? a.b1[(uint64_t)col[t] * q + c] : 0.0;
-#pragma unroll
-            for (int t = 0; t < G; ++t)
-              if (j + t < end) acc = fma(v[t], x[t], acc);
-          }
-        }
+        double const acc = bfChebRowGather(a.colind, a.val, beg, end, a.b1, q, c, lane, lanes, live);
         r = fma(a.alpha, acc, r);
         r = fma(a.beta, own, r);
       }

@@ -514,6 +514,51 @@ int bfdevChebStep(BfChebStep const *s, void *stream);
 /* U [n x p] = D E: U[j, c] = d[j] where j == rows[c], else 0 (the whole block is written; rows [p] on the device, p <= 64) */
 int bfdevChebUnitPanel(double *U, uint64_t n, uint32_t p, uint64_t const *dRows, double const *d, void *stream);
 
+/* the object of the Chebyshev covariance (bfhip_cheb.c makes and frees it; bfhip_eigs.c reads S, D and lamMax from it) */
+struct BfhipChebCov {
+  int device;
+  uint64_t n, nnz;
+  double lamMax;
+  void *dRowptr, *dColind, *dVal, *dD;
+  uint64_t deviceBytes;
+  double *coef;
+  size_t order;
+  uint64_t generation;          /* bumped by every SetCoefficients: a conditioning object made before it is stale */
+  void *dWork;
+  uint64_t workBytes;
+};
+
+/* filtered subspace iteration on S (bfhip_eigs.hip; driven by bfhip_eigs.c).  Blocks are row-major n x ld doubles, ld = p
+ * rounded up to a multiple of 16, the padding columns zero and never written.
+ *   step:     out = alpha (S b1) + beta b1 + gamma b2 on the first p columns; b2 may be NULL, out may be b2
+ *   gram:     G [ld x ld] = X^T Y, partials per chunk of bfdevEigsChunkRows rows in `part` (chunks x ld x ld), summed in chunk order
+ *   rotate:   out = X W, W [ld x ld] on the device with zero padding; out is another block
+ *   residual: sumSq[c] = sum_r (Y[r][c] - theta[c] X[r][c])^2, partials in `part` (chunks x ld)
+ *   store:    dst[i * ldu + j] = (d ? d[i] : 1) X[i][j], j < nev */
+typedef struct BfEigsStep {
+  uint64_t const *rowptr;
+  uint32_t const *colind;
+  double const *val;
+  uint64_t n;
+  uint32_t p, ld;
+  double const *b1, *b2;
+  double *out;
+  double alpha, beta, gamma;
+} BfEigsStep;
+uint64_t bfdevEigsChunkRows(uint64_t n, uint32_t ld);
+int bfdevEigsStep(BfEigsStep const *s, void *stream);
+int bfdevEigsGram(double const *X, double const *Y, uint64_t n, uint32_t ld, double *part, double *G, void *stream);
+int bfdevEigsRotate(double const *X, double const *W, double *out, uint64_t n, uint32_t ld, void *stream);
+int bfdevEigsResidual(double const *X, double const *Y, double const *theta, uint64_t n, uint32_t ld, double *part, double *sumSq, void *stream);
+int bfdevEigsStore(double const *X, uint64_t n, uint32_t ld, uint32_t nev, double const *d, double *dst, uint64_t ldu, void *stream);
+/* host, bfhip_eigs.c: the eigenpairs of a symmetric p x p matrix (row-major, lda), ascending, Q's columns the vectors; outside the
+ * public header so that tests/native/eigs_symeig_check.c can call it alone.  work: 2 p doubles.  Returns 0, or 1 when QL did not converge */
+int bfEigsSymEig(size_t p, double *A, size_t lda, double *theta, double *work);
+/* phase seconds of the last bfhipChebCovEigsDevice of this thread when bfEigsProfile(1) was called before (tools/lbo_eigs_rate.py):
+ * filter, S X, Gram, rotate, residual, host dense, summed over the call; the phases are then separated by stream synchronisations */
+void bfEigsProfile(int on);
+void bfEigsLastPhases(double out[6]);
+
 /* device-resident GMRES building blocks (bfhip_gmres.hip; complex128; bfhip_gmres.c drives them).
  * Vectors are n x nrhs row-major; reductions are per RHS column, two-stage and
  * in fixed order (per-block partials, then a tree over the partials), so a

@@ -848,6 +848,57 @@ int bfhipChebCovMomentsDevice(BfhipChebCov *c, uint64_t seed, uint64_t firstSamp
 int bfhipChebCovCondCreate(BfhipChebCov *cheb, const uint64_t *obs, size_t numObs, const double *noiseVar, BfhipCovCond **out,
                            void *stream);
 
+/* Lowest eigenpairs of the lumped-mass pencil L phi = lambda M phi, on the device, from a BfhipChebCov: the nev lowest
+ * pairs (theta, u) of S = D L D by Chebyshev-filtered subspace iteration (Zhou and Saad) on a block of p = nev + guard
+ * columns -- what the reference takes from ARPACK and UMFPACK (bfGetShiftedEigs, src/linalg.c) for the lowest band, with
+ * no factorisation.  lam[j] = theta_j ascending; dU [n x nev, row-major, leading dimension ldu] = the orthonormal
+ * eigenvectors U of S (U^T U = I), or with BFHIP_EIGS_MASS_NORMALISED Phi = D U (Phi^T M Phi = I), the eigenfunctions of
+ * the pencil.  Lumped mass only: the reference's consistent-mass pencil has other numbers.  Lowest pairs only, p <= 256.
+ *
+ * Per outer iteration: a degree-m Chebyshev filter that damps [largest Ritz value, lamMax] (m <= degree, lowered so that
+ * the filtered block's condition number stays below 2^23), Cholesky QR twice, Rayleigh-Ritz, residuals
+ * r_j = ||S u_j - theta_j u_j||_2; converged when the first nev are <= tol * lamMax.  The p x p factorisations and the
+ * p x p symmetric eigenproblem run on the host, so the call is SYNCHRONOUS (it drains `stream` in every iteration).  It
+ * needs no coefficients, leaves the generation counter alone, allocates its own workspace (three blocks of n x p16
+ * doubles, p16 = p rounded up to 16, and the partial sums) and frees it before it returns: the object's Clenshaw workspace,
+ * which live BfhipCovCond objects share, is not touched.  Two calls with the same arguments give the same bits.
+ *
+ * Errors, in this order and before the device is touched: INVALID_ARGUMENTS for a NULL c, lam or dU; nev == 0 or
+ * nev > min(n, 255); ldu < nev; a wrong structSize; nev + guard > 256, an explicit request for no guard column
+ * (BFHIP_EIGS_NO_GUARD, refused unless nev == n) or nev + guard > n with a guard given; degree == 1; tol negative or not
+ * finite.  Not converged within maxIter: RUNTIME_ERROR, the outputs hold the best pairs found and the message says how
+ * many converged.  A Cholesky pivot that is not positive: one retry of the pass with a shifted Gram matrix, then
+ * RUNTIME_ERROR; the caller's buffers are not written in that case. */
+#define BFHIP_EIGS_MASS_NORMALISED 1u
+#define BFHIP_EIGS_NO_GUARD 2u             /* flags: ask for guard == 0 explicitly (the field's 0 means "default") */
+typedef struct BfhipEigsOptions {
+  uint32_t structSize;   /* in: sizeof(BfhipEigsOptions) */
+  uint32_t guard;        /* extra block columns; 0 = default max(8, nev / 4), clipped so that nev + guard <= min(n, 256) */
+  uint32_t degree;       /* filter degree per outer iteration; 0 = default 20; >= 2 */
+  uint32_t maxIter;      /* 0 = default 100 */
+  double tol;            /* a pair is converged when ||S u - theta u||_2 <= tol * lamMax; 0 = default 1e-10 */
+  uint64_t seed;         /* start block X[i][j] = N(seed, i * p + j), the normal stream of bfhipFillNormalDevice */
+  uint32_t flags;        /* BFHIP_EIGS_MASS_NORMALISED | BFHIP_EIGS_NO_GUARD */
+  uint32_t reserved;
+} BfhipEigsOptions;
+
+typedef struct BfhipEigsInfo {
+  uint32_t structSize;   /* in: sizeof(BfhipEigsInfo) */
+  uint32_t iterations;   /* outer iterations (filters) run */
+  uint32_t converged;    /* leading pairs at or below the tolerance, at most nev */
+  uint32_t blockColumns; /* p */
+  uint32_t maxDegreeUsed;
+  uint32_t reserved;
+  uint64_t operatorColumns;   /* columns of S applied in total */
+  uint64_t workspaceBytes;
+  double maxResidual;         /* over the nev returned pairs, divided by lamMax */
+  double lamMax;
+} BfhipEigsInfo;
+
+int bfhipChebCovEigsDevice(BfhipChebCov *c, const BfhipEigsOptions *opt /* NULL = defaults */, size_t nev,
+                           double *lam /* host, nev, ascending */, double *residual /* host, nev, or NULL */,
+                           double *dU /* device, n x nev row-major */, size_t ldu, BfhipEigsInfo *info /* or NULL */, void *stream);
+
 /* ---- plan inspection (no device needed) ---------------------------------- */
 /* The flattened per-stage layout, as the kernels see it.  Valid only for an
  * operator compiled with BFHIP_FLAG_PLAN_ONLY (the host mirrors are dropped
