@@ -589,6 +589,8 @@ def load():
     lib.bfhipChebCovMomentsDevice.restype = C.c_int
     lib.bfhipChebCovCondCreate.argtypes = [vp, vp, C.c_size_t, vp, C.POINTER(vp), vp]
     lib.bfhipChebCovCondCreate.restype = C.c_int
+    lib.bfhipChebCovCondLogLikGradDevice.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_size_t, vp, vp, C.POINTER(BfhipCovCondLikOptions), vp]
+    lib.bfhipChebCovCondLogLikGradDevice.restype = C.c_int
     lib.bfhipChebCovEigsDevice.argtypes = [vp, C.POINTER(BfhipEigsOptions), C.c_size_t, vp, vp, vp, C.c_size_t, C.POINTER(BfhipEigsInfo), vp]
     lib.bfhipChebCovEigsDevice.restype = C.c_int
     lib.bfhipSetProfileSampling.argtypes = [vp, C.c_uint32]

@@ -36,6 +36,19 @@ def matern_density(kappa, nu):
     return lambda lam: np.abs(1 + kappa * kappa * lam) ** (-nu / 4 - 0.5)
 
 
+def matern_density_grad(kappa, nu):
+    """The derivatives of matern_density(kappa, nu) in its parameters, as callables of lambda >= 0: (d g / d kappa, d g / d nu)
+    of the Matern density, and the 1-tuple (d g / d kappa,) of the squared exponential (nu == 0).  What
+    ChebCovCondition.log_likelihood_grad takes as `density_grads`."""
+    kappa, nu = float(kappa), float(nu)
+    if nu == 0:
+        return (lambda lam: -lam * lam * np.exp(-kappa * lam * lam),)
+    e = -nu / 4 - 0.5
+    d_kappa = lambda lam: e * (1 + kappa * kappa * lam) ** (e - 1) * (2 * kappa * lam)
+    d_nu = lambda lam: -0.25 * np.log1p(kappa * kappa * lam) * (1 + kappa * kappa * lam) ** e
+    return d_kappa, d_nu
+
+
 def trimesh_lbo_fem(verts, faces):
     """(rowptr, colind, L, mass_lumped) of the P1 stiffness matrix of a triangle mesh (bfhipTrimeshLboFem), host arrays."""
     lib = _capi.load()

@@ -2,9 +2,10 @@
  * covariance"): the second route of the reference's covariance examples (examples/covariance/cheb_cov.c), which needs no
  * eigenpairs and no butterfly.  Host side: the Chebyshev fit and evaluation, the P1 assembly of a triangle mesh, the
  * object (S = D L D in CSR on the device, folded here) and the drivers of Clenshaw's recurrence, one bfdevChebStep
- * (bfhip_cheb.hip) per degree.  The draw and the moments reuse the kernels of bfhip_cov.hip.  Last in the file: the
- * Chebyshev backend of conditioning on observations (bfhipChebCovCondCreate; the object is bfhip_cond.c's, DESIGN.md
- * section 24). */
+ * (bfhip_cheb.hip) per degree.  The draw and the moments reuse the kernels of bfhip_cov.hip.  Then the Chebyshev backend
+ * of conditioning on observations (bfhipChebCovCondCreate; the object is bfhip_cond.c's) and, last in
+ * the file, the likelihood's gradient in the density's parameters on such an object (bfhipChebCovCondLogLikGradDevice;
+ * kernels: bfhip_likgrad.hip). */
 #include <math.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -273,17 +274,19 @@ static int chebWork(BfhipChebCov *c, uint32_t blocks, size_t q, void *stream) {
 }
 static double *chebBlock(BfhipChebCov const *c, uint32_t k, size_t q) { return (double *)c->dWork + (uint64_t)k * c->n * q; }
 
-/* out = [outScale] p(S) ([wScale] w) by Clenshaw, b_k written over b_{k+2} in blocks 0 and 1 of the workspace.  out == NULL:
- * the result takes the place b_0 would (a workspace block); *where receives it either way */
-static int chebMul(BfhipChebCov *c, double const *w, int scaleIn, int scaleOut, size_t q, double *out, double **where, void *stream) {
+/* out = [outScale] r(S) ([wScale] w) by Clenshaw for the polynomial r with coefficients coef[0 .. order - 1] on [0, lamMax],
+ * b_k written over b_{k+2} in blocks 0 and 1 of the workspace.  out == NULL: the result takes the place b_0 would (a workspace
+ * block); *where receives it either way */
+static int chebMulCoef(BfhipChebCov *c, double const *coef, size_t order, double const *w, int scaleIn, int scaleOut, size_t q, double *out,
+                       double **where, void *stream) {
   BfChebStep s = { c->dRowptr, c->dColind, c->dVal, c->n, (uint32_t)q, w, scaleIn ? c->dD : NULL, NULL, NULL, NULL, NULL, 0, 0, 0 };
   double *P[2] = { chebBlock(c, 0, q), chebBlock(c, 1, q) };
   double *b1 = NULL, *b2 = NULL;
   int rc;
-  for (size_t k = c->order; k-- > 0;) {
+  for (size_t k = order; k-- > 0;) {
     double *dst = b2 ? b2 : b1 == P[0] ? P[1] : P[0];
     if (k == 0 && out) dst = out;
-    s.b1 = b1; s.b2 = b2; s.out = dst; s.ck = c->coef[k];
+    s.b1 = b1; s.b2 = b2; s.out = dst; s.ck = coef[k];
     s.alpha = (k ? 4.0 : 2.0) / c->lamMax; s.beta = k ? -2.0 : -1.0;
     s.outScale = k == 0 && scaleOut ? c->dD : NULL;
     if ((rc = bfdevChebStep(&s, stream))) return rc;
@@ -291,6 +294,11 @@ static int chebMul(BfhipChebCov *c, double const *w, int scaleIn, int scaleOut, 
   }
   if (where) *where = b1;
   return 0;
+}
+
+/* the object's own polynomial p */
+static int chebMul(BfhipChebCov *c, double const *w, int scaleIn, int scaleOut, size_t q, double *out, double **where, void *stream) {
+  return chebMulCoef(c, c->coef, c->order, w, scaleIn, scaleOut, q, out, where, stream);
 }
 
 static int chebBlockCheck(BfhipChebCov const *c, void const *in, void const *out, size_t q) {
@@ -424,6 +432,8 @@ int bfhipChebCovCondCreate(BfhipChebCov *cheb, uint64_t const *obs, size_t numOb
   if (!c) { rc = bfhipFail(BFABI_ERROR_MEMORY_ERROR, "out of host memory"); goto fail; }
   c->be = (BfCondBackend){ n, n, BFHIP_F64, sizeof(double), 0, chebCondPanel, chebCondWprime, chebCondField, chebCondLive };
   c->cheb = cheb; c->chebGeneration = cheb->generation; c->k = k; c->device = cheb->device;
+  if (!(c->hObs = malloc(k * sizeof *c->hObs))) { rc = bfhipFail(BFABI_ERROR_MEMORY_ERROR, "out of host memory"); goto fail; }
+  memcpy(c->hObs, obs, k * sizeof *c->hObs);         /* the gradient in the density's parameters makes the unit panels again */
   if ((rc = bfDevEnter(&ds, cheb->device))) goto fail;
 
   /* ---- the recurrence's two blocks at 64 columns in cheb's workspace, and the object's own W' block ---- */
@@ -435,6 +445,103 @@ int bfhipChebCovCondCreate(BfhipChebCov *cheb, uint64_t const *obs, size_t numOb
 fail:
   condRelease(c);
   free(keys);
+  bfDevLeave(&ds);
+  return rc;
+}
+
+/* ------------------------------------------------------------------------
+ * the likelihood's gradient in the density's parameters
+ * ---------------------------------------------------------------------- */
+/* profile switch of tools/cheb_gradient_rate.py: with it on, the phases of a call are separated by stream synchronisations */
+enum { GPH_ALPHA, GPH_MPANEL, GPH_CONTRACT, GPH_RECURRENCE, GPH_DOT, GPH_COUNT };
+static _Thread_local int gradProfileOn;
+static _Thread_local double gradPhases[GPH_COUNT], gradT0;
+void bfChebGradProfile(int on) { gradProfileOn = on; }
+void bfChebGradLastPhases(double out[GPH_COUNT]) { memcpy(out, gradPhases, sizeof gradPhases); }
+static void gradPhaseBegin(void *stream) {
+  if (gradProfileOn) { bfdevSync(stream); gradT0 = bfNowSeconds(); }
+}
+static void gradPhaseEnd(void *stream, int ph) {
+  if (gradProfileOn) { bfdevSync(stream); gradPhases[ph] += bfNowSeconds() - gradT0; }
+}
+
+/* the scratch of the gradient: allocated by the first call (which drains `stream`: allocating is not stream-ordered), kept until
+ * the object is freed, not counted in factorBytes */
+static int chebGradEnsure(BfhipCovCond *c, uint64_t chunks, void *stream) {
+  if (c->dGradRows && c->dGradY && c->dGradM && c->dGradPart) return 0;
+  uint64_t const n = c->be.n;
+  uint32_t const k = c->k, Q = BF_COND_MAX_RHS;
+  int rc;
+  if ((rc = bfdevSync(stream))) return rc;
+  if (!c->dGradRows) {
+    if ((rc = bfdevMalloc((void **)&c->dGradRows, (size_t)k * 8))) return rc;
+    if ((rc = bfdevMemcpyH2D(c->dGradRows, c->hObs, (size_t)k * 8))) { bfdevFree(c->dGradRows); c->dGradRows = NULL; return rc; }
+  }
+  if (!c->dGradY && (rc = bfdevMalloc((void **)&c->dGradY, n * Q * sizeof(double)))) return rc;
+  if (!c->dGradM && (rc = bfdevMalloc((void **)&c->dGradM, 2 * (size_t)k * Q * sizeof(double)))) return rc;
+  if (!c->dGradPart && (rc = bfdevMalloc((void **)&c->dGradPart, 64 * chunks * sizeof(double)))) return rc;
+  return 0;
+}
+
+int bfhipChebCovCondLogLikGradDevice(BfhipCovCond *c, double const *dY, double const *dcoef, size_t const *orders, size_t numParams, size_t ldCoef,
+                                     double *dGrad, double *dValue, BfhipCovCondLikOptions const *opt, void *stream) {
+  if (!c || !dY || !dcoef || !orders || !dGrad) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL argument");
+  if (numParams == 0 || numParams > 64) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "numParams out of range (1 .. 64)");
+  for (size_t t = 0; t < numParams; ++t)
+    if (orders[t] == 0 || orders[t] > ldCoef)
+      return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "orders[%zu] = %zu is zero or above ldCoef = %zu", t, orders[t], ldCoef);
+  for (size_t t = 0; t < numParams; ++t)
+    for (size_t j = 0; j < orders[t]; ++j)
+      if (!isfinite(dcoef[t * ldCoef + j])) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "coefficient %zu of parameter %zu is not finite", j, t);
+  if (opt && opt->structSize != sizeof *opt) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "BfhipCovCondLikOptions.structSize is not the struct's");
+  /* from here on the object is read */
+  if (!c->cheb || !c->hObs) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "the object was not made by bfhipChebCovCondCreate: the gradient in the density's parameters is the Chebyshev route's");
+  int rc;
+  BfDevScope ds;
+  if ((rc = chebCondLive(c)) || (rc = bfDevEnter(&ds, c->device))) return rc;
+  BfhipChebCov *cheb = c->cheb;
+  uint64_t const n = c->be.n, chunks = (n + BF_COND_CHUNK - 1) / BF_COND_CHUNK;
+  uint32_t const k = c->k, Q = BF_COND_MAX_RHS, T = (uint32_t)numParams;
+  if (gradProfileOn) memset(gradPhases, 0, sizeof gradPhases);
+  if ((rc = chebGradEnsure(c, chunks, stream)) || (rc = chebWork(cheb, 2, Q, stream))) goto done;
+  double *Kinv = c->dGradM, *Mp = c->dGradM + (size_t)k * Q;
+
+  /* alpha = K^-1 y into c->dR and the value, launch for launch as bfhipCovCondLogLikelihoodDevice forms them */
+  gradPhaseBegin(stream);
+  if ((rc = bfdevCondResidual(c->dR, c->dPart, c->dBt, n, k, dY, NULL, 1, c->be.dtype, NULL, 1, 1, stream)) ||
+      (rc = bfdevCondSolve(c->dL, k, c->dR, 1, stream)) || (dValue && (rc = bfdevLikValue(dValue, c->dL, k, dY, c->dR, stream)))) goto done;
+  gradPhaseEnd(stream, GPH_ALPHA);
+
+  for (uint32_t c0 = 0; c0 < k; c0 += Q) {
+    uint32_t const pc = k - c0 < Q ? k - c0 : Q;
+    /* M[:, panel] = alpha alpha[panel]^T - K^-1 E_panel: the two triangular solves of a sample pass on a k x pc block */
+    gradPhaseBegin(stream);
+    if ((rc = bfdevLikGradUnit(Kinv, k, c0, pc, stream)) || (rc = bfdevCondSolve(c->dL, k, Kinv, pc, stream)) ||
+        (rc = bfdevLikGradM(Mp, c->dR, Kinv, k, c0, pc, stream))) goto done;
+    gradPhaseEnd(stream, GPH_MPANEL);
+    /* Y = X M[:, panel], once per panel */
+    gradPhaseBegin(stream);
+    if ((rc = bfdevLikGradContract(c->dGradY, c->dBt, n, k, Mp, pc, stream))) goto done;
+    gradPhaseEnd(stream, GPH_CONTRACT);
+    /* the panel of X'_t = q_t(S) D E_panel as Create makes X's: the unit panel (once), one recurrence per parameter, no output scaling */
+    gradPhaseBegin(stream);
+    if ((rc = bfdevChebUnitPanel(c->dWp, n, pc, c->dGradRows + c0, cheb->dD, stream))) goto done;
+    gradPhaseEnd(stream, GPH_RECURRENCE);
+    for (uint32_t t = 0; t < T; ++t) {
+      double *xp = NULL;
+      gradPhaseBegin(stream);
+      if ((rc = chebMulCoef(cheb, dcoef + t * ldCoef, orders[t], c->dWp, 0, 0, pc, NULL, &xp, stream))) goto done;
+      gradPhaseEnd(stream, GPH_RECURRENCE);
+      gradPhaseBegin(stream);
+      if ((rc = bfdevLikGradDot(c->dGradPart + t * chunks, c->dGradY, xp, n, pc, stream))) goto done;
+      gradPhaseEnd(stream, GPH_DOT);
+    }
+    /* one owner per parameter: the panel's chunks in order, the panels in order */
+    gradPhaseBegin(stream);
+    if ((rc = bfdevLikGradSum(dGrad, c->dGradPart, chunks, T, c0 == 0, stream))) goto done;
+    gradPhaseEnd(stream, GPH_DOT);
+  }
+done:
   bfDevLeave(&ds);
   return rc;
 }

@@ -77,6 +77,7 @@ void condRelease(BfhipCovCond *c) {
   bfdevFree(c->dBt); bfdevFree(c->dL); bfdevFree(c->dNoiseVar); bfdevFree(c->dNoiseSd); bfdevFree(c->dR); bfdevFree(c->dE); bfdevFree(c->dWn); bfdevFree(c->dPart);
   bfdevFree(c->dWp);
   condLikRelease(c);
+  free(c->hObs);
   free(c);
 }
 

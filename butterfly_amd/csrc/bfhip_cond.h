@@ -54,6 +54,12 @@ struct BfhipCovCond {
   double *dColSq;                /* [n + k]: ||L^-1 b_j||^2, then ||L^-1 e_a||^2 */
   double *dVarBlk;               /* [n x 64]: a panel of rows of P A GammaLam, transposed (variance) */
   double *dVarPart;              /* [chunks x 64] partial sums of its columns' squares, then [64] ||L^-1 Bt^T r||^2, then [k] zeros */
+  /* bfhip_cheb.c: the gradient in the density's parameters (Chebyshev route) */
+  uint64_t *hObs;                /* host [k]: the observed vertices, kept by bfhipChebCovCondCreate (the unit panels are made again) */
+  uint64_t *dGradRows;           /* [k]: the same on the device, uploaded by the first gradient call like everything below */
+  double *dGradY;                /* [n x 64]: Y = X M[:, panel] */
+  double *dGradM;                /* [k x 64] K^-1[:, panel] packed at the panel's width, then [k x 64] M[:, panel] */
+  double *dGradPart;             /* [64 x chunks]: a panel's partial sums, one row per parameter */
 };
 
 /* releases what bfhip_condlik.c allocated (the device is drained by the caller) */
@@ -109,6 +115,19 @@ int bfdevLikGradNoise(double *grad, double const *alpha, double const *colSq, ui
 int bfdevVarPriorPart(double *part, double const *blk, uint64_t n, uint32_t p, void *stream);
 /* prior[s] = sum_c part[c][s] in chunk order (NULL: not stored), post[s] = that - solved[s] (NULL: not stored), s < p */
 int bfdevVarAssemble(double *prior, double *post, double const *part, uint64_t chunks, double const *solved, uint32_t p, void *stream);
+
+/* ---- the gradient in the density's parameters (bfhip_likgrad.hip; driven by bfhip_cheb.c), one panel of pc <= 64 observed
+ * columns c0 .. c0 + pc - 1 at a time ---- */
+/* E [k x pc] packed = the panel's columns of the identity */
+int bfdevLikGradUnit(double *E, uint32_t k, uint32_t c0, uint32_t pc, void *stream);
+/* Mp [k x 64]: Mp[a, c] = alpha[a] alpha[c0 + c] - Kinv[a, c] for c < pc (Kinv [k x pc] packed), zero beyond */
+int bfdevLikGradM(double *Mp, double const *alpha, double const *Kinv, uint32_t k, uint32_t c0, uint32_t pc, void *stream);
+/* Y [n x 64] = X [n x k] Mp [k x 64] on the FP64 matrix cores; columns >= pc of Mp are not read, those of Y are exact zeros */
+int bfdevLikGradContract(double *Y, double const *X, uint64_t n, uint32_t k, double const *Mp, uint32_t pc, void *stream);
+/* part[chunk] = sum over the rows r of the chunk (BF_COND_CHUNK rows) and c < pc of Y[r, c] Xp[r, c]; Y [n x 64], Xp [n x pc] packed */
+int bfdevLikGradDot(double *part, double const *Y, double const *Xp, uint64_t n, uint32_t pc, void *stream);
+/* grad[t] = (first ? 0 : grad[t]) + sum_chunk part[t * chunks + chunk] in chunk order, t < numParams */
+int bfdevLikGradSum(double *grad, double const *part, uint64_t chunks, uint32_t numParams, int first, void *stream);
 #ifdef __cplusplus
 }
 #endif

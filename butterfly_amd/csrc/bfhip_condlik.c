@@ -20,6 +20,8 @@ void condLikRelease(BfhipCovCond *c) {
   bfdevFree(c->dStrips); bfdevFree(c->dLinv); bfdevFree(c->dColSq); bfdevFree(c->dVarBlk); bfdevFree(c->dVarPart);
   c->dStrips = c->dLinv = c->dColSq = c->dVarBlk = c->dVarPart = NULL;
   c->likSlots = 0;
+  bfdevFree(c->dGradRows); bfdevFree(c->dGradY); bfdevFree(c->dGradM); bfdevFree(c->dGradPart);
+  c->dGradRows = NULL; c->dGradY = c->dGradM = c->dGradPart = NULL;
 }
 
 static uint64_t stripBytes(BfhipCovCond const *c) { return (uint64_t)c->k * BF_LIK_STRIP * sizeof(double); }

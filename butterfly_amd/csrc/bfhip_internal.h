@@ -558,6 +558,10 @@ int bfEigsSymEig(size_t p, double *A, size_t lda, double *theta, double *work);
  * filter, S X, Gram, rotate, residual, host dense, summed over the call; the phases are then separated by stream synchronisations */
 void bfEigsProfile(int on);
 void bfEigsLastPhases(double out[6]);
+/* the same switch for bfhipChebCovCondLogLikGradDevice (bfhip_cheb.c; tools/cheb_gradient_rate.py): phase seconds of this thread's
+ * last call, summed over its panels: alpha and value, the M panels, the contraction, the recurrences, the dot and the owner's sum */
+void bfChebGradProfile(int on);
+void bfChebGradLastPhases(double out[5]);
 
 /* device-resident GMRES building blocks (bfhip_gmres.hip; complex128; bfhip_gmres.c drives them).
  * Vectors are n x nrhs row-major; reductions are per RHS column, two-stage and

@@ -892,7 +892,8 @@ class ChebCovCondition(CovCondition):
     values at the mesh vertices `obs`.  Every method of CovCondition works on it, on float64 [n, q] blocks in mesh order;
     log_likelihood(grad_log_gamma=True) raises the library's refusal (this route has no per-column weights), and so does every
     method but info and close once set_coefficients has been called on the ChebCovariance: make a new one then.  The object
-    keeps its ChebCovariance alive."""
+    keeps its ChebCovariance alive.  On this route alone: log_likelihood_grad, the exact gradient of the likelihood in the
+    parameters of the spectral density, and grad_log_scale."""
 
     def __init__(self, cheb, obs, noise_var=None):
         import torch
@@ -907,3 +908,61 @@ class ChebCovCondition(CovCondition):
         check(self._lib.bfhipChebCovCondCreate(cheb.handle, obs.ctypes.data, obs.size, nv.ctypes.data if nv is not None else None,
                                                C.byref(self._h), C.c_void_p(s.cuda_stream)))
         self.num_obs = int(obs.size)
+        self._noise_var = nv
+
+    def log_likelihood_grad(self, y, density_grads, order=None, value=False):
+        """The exact gradient of log_likelihood(y)[0] in the parameters of the spectral density
+        (bfhipChebCovCondLogLikGradDevice): density_grads is a sequence of callables of lambda, d g / d theta_t (for the Matern
+        family: matern_density_grad).  Each is fitted with cheb_fit on [0, lamMax] at the order of the ChebCovariance's
+        polynomial (or at `order`: an int, or one per parameter): at that order the result is the derivative of the value the
+        library returns.  Returns a float64 [numParams] device tensor; with value=True (gradient, value [3])."""
+        import torch
+        from .cheb import cheb_fit
+        self._check_y(y)
+        grads = list(density_grads)
+        info = self._op.info()
+        if order is None:
+            orders = [int(info["order"])] * len(grads)
+        elif np.ndim(order) == 0:
+            orders = [int(order)] * len(grads)
+        else:
+            orders = [int(o) for o in order]
+        if not grads or len(orders) != len(grads):
+            raise ValueError("density_grads is a non-empty sequence of callables, with one order each")
+        ld = max(max(orders), 1)
+        coef = np.zeros((len(grads), ld), dtype=np.float64)
+        for t, (f, o) in enumerate(zip(grads, orders)):
+            coef[t, :o] = cheb_fit(f, o, 0.0, info["lamMax"])
+        return self.log_likelihood_grad_coef(y, coef, orders, value=value)
+
+    def log_likelihood_grad_coef(self, y, coef, orders=None, value=False):
+        """log_likelihood_grad for derivative polynomials given by their Chebyshev coefficients on [0, lamMax]: coef is
+        [numParams, ld] float64 on the host, of row t the first orders[t] (None: ld) entries are read."""
+        import torch
+        self._check_y(y)
+        coef = np.ascontiguousarray(coef, dtype=np.float64)
+        if coef.ndim != 2:
+            raise ValueError("coef is [numParams, ld]")
+        num, ld = coef.shape
+        ords = np.full(num, ld, dtype=np.uintp) if orders is None else np.ascontiguousarray(orders, dtype=np.uintp)
+        if ords.shape != (num,):
+            raise ValueError("orders has one entry per parameter")
+        g = torch.empty(num, dtype=torch.float64, device=y.device)
+        v = torch.empty(3, dtype=torch.float64, device=y.device) if value else None
+        opt = _capi.BfhipCovCondLikOptions()
+        opt.structSize = C.sizeof(opt)
+        ptr = HipOperator._ptr
+        check(self._lib.bfhipChebCovCondLogLikGradDevice(self._h, ptr(y), coef.ctypes.data, ords.ctypes.data, num, ld, ptr(g), ptr(v), C.byref(opt),
+                                                         self._stream()))
+        return (g, v) if value else g
+
+    def grad_log_scale(self, y):
+        """d logLik / d log s for the covariance s X^T X + N at s = 1, in closed form from outputs the library already has:
+        (quad - k) / 2 - sum_a noiseVar[a] gradNoise[a].  A float64 scalar device tensor.  It is what log_likelihood_grad
+        returns for the derivative polynomial p / 2."""
+        value, _, h = self.log_likelihood(y, grad_noise=True)
+        g = (value[1] - self.num_obs) / 2
+        if self._noise_var is not None:
+            import torch
+            g = g - (torch.from_numpy(self._noise_var).to(h.device) * h).sum()
+        return g

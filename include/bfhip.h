@@ -848,6 +848,36 @@ int bfhipChebCovMomentsDevice(BfhipChebCov *c, uint64_t seed, uint64_t firstSamp
 int bfhipChebCovCondCreate(BfhipChebCov *cheb, const uint64_t *obs, size_t numObs, const double *noiseVar, BfhipCovCond **out,
                            void *stream);
 
+/* The gradient of the log marginal likelihood in the parameters of the spectral density, on an object made by
+ * bfhipChebCovCondCreate.  With X = p(S) D E_obs [n x k] (the object's rows), K = X^T X + N,
+ * alpha = K^-1 y and, for a parameter theta_t, the polynomial q_t = d p / d theta_t,
+ *   d logLik / d theta_t = < X M, X'_t >_F,   M = alpha alpha^T - K^-1 [k x k],   X'_t = q_t(S) D E_obs.
+ * q_t is given by its Chebyshev coefficients on [0, lamMax]: row t of dcoef (HOST, numParams rows of ldCoef doubles, of which
+ * the first orders[t] are read).  The fit is linear, so the interpolant of d g / d theta at the order of p IS d coef / d theta:
+ * with those coefficients the result is the exact derivative of the value bfhipCovCondLogLikelihoodDevice returns.  An order
+ * other than p's is legal.  X'_t is never stored: it is made 64 observed columns at a time as Create makes X (the unit panel,
+ * one recurrence with q_t's coefficients, no output scaling), so a call costs numParams x ceil(k / 64) polynomial applications.
+ *
+ * Per panel of <= 64 observed columns: M[:, panel] from the two triangular solves of a sample pass on the panel's columns of
+ * the identity; Y = X M[:, panel] on the FP64 matrix cores (v_mfma_f64_16x16x4_f64), once per panel; per parameter the
+ * recurrence and the partial sums of Y o X'_t per 1024 rows; one owner adds the partials in chunk, then panel order.  No
+ * atomics: every sum order depends on (n, k, panel) alone, two calls give equal bits, and dGrad[t] depends neither on numParams
+ * nor on t's place among the parameters.
+ *
+ * dGrad [numParams] (device, double).  dValue [3] (device, double) or NULL: { logLik, quad, logDet }, the bits of
+ * bfhipCovCondLogLikelihoodDevice.  opt may be NULL; workspaceBytes is not used.  The recurrence runs in cheb's workspace and
+ * the unit panels in the object's W' block, as in Create; the scratch of the gradient (Y [n x 64], two k x 64 blocks, the
+ * partial sums, the observed indices) is allocated by the first call, which drains `stream`, and kept until bfhipCovCondFree
+ * (not counted in factorBytes); a later call only enqueues work.  dcoef and orders are read before the call returns.
+ *
+ * Errors, raised before the device is touched, in this order: INVALID_ARGUMENTS (a NULL c, dY, dcoef, orders or dGrad;
+ * numParams outside 1 .. 64; an order of 0 or above ldCoef; a coefficient that is not finite; a structSize that is not the
+ * struct's) -- nothing is read through c up to here --, INVALID_ARGUMENTS (an object not made by bfhipChebCovCondCreate), and
+ * the refusal of a stale object (bfhipChebCovSetCoefficients was called after it was made). */
+int bfhipChebCovCondLogLikGradDevice(BfhipCovCond *c, const double *dY, const double *dcoef, const size_t *orders,
+                                     size_t numParams, size_t ldCoef, double *dGrad, double *dValue,
+                                     const BfhipCovCondLikOptions *opt, void *stream);
+
 /* Lowest eigenpairs of the lumped-mass pencil L phi = lambda M phi, on the device, from a BfhipChebCov: the nev lowest
  * pairs (theta, u) of S = D L D by Chebyshev-filtered subspace iteration (Zhou and Saad) on a block of p = nev + guard
  * columns -- what the reference takes from ARPACK and UMFPACK (bfGetShiftedEigs, src/linalg.c) for the lowest band, with
