@@ -177,6 +177,11 @@ class BfhipEigsInfo(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_ if n not in ("structSize", "reserved")}
 
 
+class BfhipEigsLocked(C.Structure):
+    _fields_ = [("structSize", C.c_uint32), ("reserved", C.c_uint32), ("count", C.c_uint64), ("dVectors", C.c_void_p), ("ld", C.c_uint64),
+                ("lam", C.c_void_p)]
+
+
 CHEB_DENSITY_FN = C.CFUNCTYPE(C.c_double, C.c_double, C.c_void_p)      # double (*f)(double, void *)
 
 
@@ -593,6 +598,11 @@ def load():
     lib.bfhipChebCovCondLogLikGradDevice.restype = C.c_int
     lib.bfhipChebCovEigsDevice.argtypes = [vp, C.POINTER(BfhipEigsOptions), C.c_size_t, vp, vp, vp, C.c_size_t, C.POINTER(BfhipEigsInfo), vp]
     lib.bfhipChebCovEigsDevice.restype = C.c_int
+    lib.bfhipChebCovEigsBandDevice.argtypes = [vp, C.POINTER(BfhipEigsOptions), C.POINTER(BfhipEigsLocked), C.c_size_t, vp, vp, vp, C.c_size_t,
+                                               C.POINTER(BfhipEigsInfo), vp]
+    lib.bfhipChebCovEigsBandDevice.restype = C.c_int
+    lib.bfhipChebCovEigsMassNormaliseDevice.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp]
+    lib.bfhipChebCovEigsMassNormaliseDevice.restype = C.c_int
     lib.bfhipSetProfileSampling.argtypes = [vp, C.c_uint32]
     lib.bfhipSetProfileSampling.restype = C.c_int
     lib.bfhipPlanGetInfo.argtypes = [vp, C.POINTER(BfhipPlanInfo)]

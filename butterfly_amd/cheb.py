@@ -233,3 +233,75 @@ class ChebCovariance:
         out = info.as_dict()
         out["residual"], out["code"] = res[:nev], rc
         return lam[:nev], full[:, :nev], out
+
+    def eigs_band(self, nev, locked=None, guard=None, degree=None, tol=None, max_iter=None, seed=0, out=None, raise_on_limit=True):
+        """The nev eigenpairs of S that follow the locked ones (bfhipChebCovEigsBandDevice), with what eigs returns.  locked:
+        None, (U_all, lam_all, m) -- a float64 [n, total] tensor on this GPU whose first m columns are the locked vectors, and at
+        least m eigenvalues -- or (U, lam) with U an [n, m] tensor or view (unit column stride; any row stride).  The locked vectors
+        must be orthonormal eigenvectors of S, not mass-normalised.  out: an [n, nev] view to write into (unit column stride),
+        e.g. U_all[:, m:m + nev]; None allocates."""
+        import torch
+        nev = int(nev)
+        opt = _capi.BfhipEigsOptions()
+        opt.structSize = C.sizeof(opt)
+        opt.guard = 0 if guard is None else int(guard)
+        opt.degree = 0 if degree is None else int(degree)
+        opt.maxIter = 0 if max_iter is None else int(max_iter)
+        opt.tol = 0.0 if tol is None else float(tol)
+        opt.seed = int(seed)
+        opt.flags = _capi.EIGS_NO_GUARD if guard is not None and int(guard) == 0 else 0
+        info = _capi.BfhipEigsInfo()
+        info.structSize = C.sizeof(info)
+        dev = torch.device("cuda", self._dev)
+
+        def view(t, cols, what):
+            if t.dtype != torch.float64 or t.device != dev or t.dim() != 2 or t.shape[0] != self.n or t.shape[1] < cols:
+                raise ValueError(f"{what}: a float64 tensor [n, >= {cols}] on cuda:{self._dev}")
+            if cols and (t.stride(1) != 1 or (self.n > 1 and t.stride(0) < cols)):
+                raise ValueError(f"{what}: rows must be contiguous (column stride 1)")
+            return t.stride(0) if self.n > 1 else max(cols, 1)
+
+        lk, keep = None, None
+        if locked is not None:
+            U_l, lam_l = locked[0], np.ascontiguousarray(locked[1], dtype=np.float64)
+            m = int(locked[2]) if len(locked) > 2 else int(U_l.shape[1])
+            if m:
+                if lam_l.size < m:
+                    raise ValueError("locked: fewer eigenvalues than vectors")
+                lk = _capi.BfhipEigsLocked()
+                lk.structSize, lk.count, lk.dVectors, lk.ld, lk.lam = C.sizeof(lk), m, U_l.data_ptr(), view(U_l, m, "locked"), lam_l.ctypes.data
+                keep = (U_l, lam_l)
+        if out is None:
+            out = torch.zeros((self.n, max(nev, 1)), dtype=torch.float64, device=dev)
+        ldu = view(out, nev, "out")
+        lam, res = np.zeros(max(nev, 1)), np.zeros(max(nev, 1))
+        rc = self._lib.bfhipChebCovEigsBandDevice(self._h, C.byref(opt), C.byref(lk) if lk is not None else None, nev, lam.ctypes.data, res.ctypes.data,
+                                                  C.c_void_p(out.data_ptr()), ldu, C.byref(info), self._stream())
+        del keep
+        if rc != 0 and (raise_on_limit or info.blockColumns == 0):
+            check(rc)
+        d = info.as_dict()
+        d["residual"], d["code"] = res[:nev], rc
+        return lam[:nev], out[:, :nev], d
+
+    def eigs_bands(self, total, band=64, guard=None, degree=None, tol=None, max_iter=None, seed=0, mass_normalised=False):
+        """The `total` lowest eigenpairs in successive bands of `band` (the last one ragged), each deflated against all the
+        earlier ones: (lam [total] ascending, U [n, total] on the GPU, the list of per-band info dicts).  A guard that no longer
+        fits the space left is clipped.  mass_normalised scales the rows by d once at the end (Phi = D U)."""
+        import torch
+        total, band = int(total), int(band)
+        if not 1 <= total <= self.n or not 1 <= band <= 255:
+            raise ValueError("total in 1 .. n and band in 1 .. 255")
+        U = torch.zeros((self.n, total), dtype=torch.float64, device=torch.device("cuda", self._dev))
+        lam, infos, m = np.zeros(total), [], 0
+        while m < total:
+            nev = min(band, total - m)
+            left = self.n - m - nev
+            g = 0 if left == 0 else None if guard is None else min(int(guard), left, 256 - nev)
+            lam_b, _, info = self.eigs_band(nev, (U, lam, m), guard=g, degree=degree, tol=tol, max_iter=max_iter, seed=seed, out=U[:, m:m + nev])
+            lam[m:m + nev] = lam_b
+            infos.append(info)
+            m += nev
+        if mass_normalised:
+            check(self._lib.bfhipChebCovEigsMassNormaliseDevice(self._h, C.c_void_p(U.data_ptr()), total, total, self._stream()))
+        return lam, U, infos

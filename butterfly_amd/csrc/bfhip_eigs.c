@@ -4,7 +4,9 @@
  * 2006, for the scaled filter).  Host side: the argument checks, the outer loop, the scalar recurrence that caps the
  * filter's degree, and the p x p dense work (Cholesky factor, triangular inverse, symmetric eigenproblem; p <= 256) in
  * double -- the loop needs the Ritz values and the residuals on the host in every iteration anyway.  The kernels are
- * bfhip_eigs.hip's. */
+ * bfhip_eigs.hip's.  bfEigsSolve is also the iteration of bfhipChebCovEigsBandDevice (bfhip_eigs_band.c):
+ * with locked vectors the block is projected against them before every orthonormalisation and their lowest eigenvalue joins
+ * the degree cap; with none it is section 25's call, launch for launch. */
 #include <math.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -163,10 +165,30 @@ static void eigsInverseTransposed(size_t p, double const *G, size_t ld, double *
  * profile switch of tools/lbo_eigs_rate.py
  * ---------------------------------------------------------------------- */
 static _Thread_local int eigsProfileOn;
-static _Thread_local double eigsPhases[6];
-enum { PH_FILTER, PH_SX, PH_GRAM, PH_ROTATE, PH_RESIDUAL, PH_HOST };
+static _Thread_local double eigsPhases[7];
+enum { PH_FILTER, PH_SX, PH_GRAM, PH_ROTATE, PH_RESIDUAL, PH_HOST, PH_PROJECT };
 void bfEigsProfile(int on) { eigsProfileOn = on; }
-void bfEigsLastPhases(double out[6]) { memcpy(out, eigsPhases, sizeof eigsPhases); }
+void bfEigsLastPhases(double out[6]) { memcpy(out, eigsPhases, 6 * sizeof(double)); }
+double bfEigsLastProjectSeconds(void) { return eigsPhases[PH_PROJECT]; }
+/* with the switch on, per Rayleigh-Ritz step of the last call (the first BF_EIGS_HISTORY of them): the largest residual of the
+ * wanted pairs over lamMax, and the degree of the filter before it (0 for the start block) */
+enum { BF_EIGS_HISTORY = 128 };
+static _Thread_local uint32_t eigsHistoryCount, eigsHistoryDegree[BF_EIGS_HISTORY];
+static _Thread_local double eigsHistoryResidual[BF_EIGS_HISTORY];
+uint32_t bfEigsLastHistory(double *residual, uint32_t *degree, uint32_t cap) {
+  uint32_t const k = eigsHistoryCount < cap ? eigsHistoryCount : cap;
+  memcpy(residual, eigsHistoryResidual, k * sizeof *residual);
+  memcpy(degree, eigsHistoryDegree, k * sizeof *degree);
+  return k;
+}
+static void eigsRecord(double const *res, size_t nev, double lamMax, uint32_t degree) {
+  if (!eigsProfileOn || eigsHistoryCount >= BF_EIGS_HISTORY) return;
+  double worst = 0;
+  for (size_t j = 0; j < nev; ++j)
+    if (res[j] > worst) worst = res[j];
+  eigsHistoryResidual[eigsHistoryCount] = worst / lamMax;
+  eigsHistoryDegree[eigsHistoryCount++] = degree;
+}
 
 /* ------------------------------------------------------------------------
  * the iteration
@@ -182,6 +204,12 @@ typedef struct EigsRun {
   uint64_t opColumns;
   void *stream;
   double t0;
+  /* the locked block (section 27): m == 0 and project == NULL in bfhipChebCovEigsDevice */
+  double const *dQ;
+  uint64_t ldq, m;
+  double lockMin;               /* the smallest locked eigenvalue */
+  double *dC, *dPartC;          /* coefficients of one panel [<= 256 x ld] and their per-chunk partials */
+  BfEigsProjectFn project;
 } EigsRun;
 
 static void phaseBegin(EigsRun *r) {
@@ -217,10 +245,17 @@ static int eigsGramToHost(EigsRun *r, double const *X, double const *Y) {
   return 0;
 }
 
-/* X <- X R^-1 twice (Cholesky QR applied twice); a failed pivot: that pass once more with G + s I, then two plain passes */
+/* With locked vectors Q first X <- X - Q (Q^T X), twice ("twice is enough"), the coefficients staying on the device.  Then
+ * X <- X R^-1 twice (Cholesky QR applied twice); a failed pivot: that pass once more with G + s I, then two plain passes */
 static int eigsOrthonormalise(EigsRun *r) {
   int rc, plain = 2, shifted = 0;
   size_t const p = r->p, ld = r->ld;
+  if (r->m) {
+    phaseBegin(r);
+    for (int pass = 0; pass < 2; ++pass)
+      if ((rc = r->project(r->dQ, r->ldq, r->m, r->B[r->ix], r->n, r->ld, r->dPartC, r->dC, r->stream))) return rc;
+    phaseEnd(r, PH_PROJECT);
+  }
   while (plain > 0) {
     if ((rc = eigsGramToHost(r, r->B[r->ix], r->B[r->ix]))) return rc;
     double const th = bfNowSeconds();
@@ -294,25 +329,28 @@ static int eigsRayleighRitz(EigsRun *r) {
  *   Y_1 = (sigma_1 / e) (S - c) X,   Y_{i+1} = (2 sigma_{i+1} / e) (S - c) Y_i - sigma_i sigma_{i+1} Y_{i-1},  sigma_{i+1} = 1 / (tau - sigma_i).
  * The degree is the largest m <= degree for which max_j |rho_m(theta_j)| / min_j |rho_m(theta_j)| < 2^23 over the block's Ritz
  * values, rho_m by the same recurrence in scalars: the filtered block's condition number then stays where Cholesky QR applied
- * twice still gives an orthonormal block (cond^2 2^-53 < 1 needs cond < 2^26; the factor 8 is margin). */
+ * twice still gives an orthonormal block (cond^2 2^-53 < 1 needs cond < 2^26; the factor 8 is margin).  With locked pairs
+ * their smallest eigenvalue is one more point: the filter amplifies the locked directions most, and what rounding leaves of
+ * them in the block (2^-53) must stay below 2^23 2^-53 of the least amplified Ritz direction before it is projected out. */
 static uint32_t eigsDegreeCap(EigsRun const *r, uint32_t degree, double e, double cc, double sigma1) {
-  size_t const p = r->p;
-  double *y0 = r->work, *y1 = r->work + p;            /* 2 p doubles */
+  size_t const p = r->p, q = r->m ? p + 1 : p;
+  double *y0 = r->work, *y1 = r->work + q;            /* 2 (p + 1) doubles */
+  if (r->m) r->theta[p] = r->lockMin;                 /* theta has ld + 1 entries; the slot is past every Ritz value */
   double const tau = 2 / sigma1;
   double sigma = sigma1;
   uint32_t best = 1;
-  for (size_t j = 0; j < p; ++j) { y0[j] = 1; y1[j] = sigma1 / e * (r->theta[j] - cc); }
+  for (size_t j = 0; j < q; ++j) { y0[j] = 1; y1[j] = sigma1 / e * (r->theta[j] - cc); }
   for (uint32_t m = 1; m <= degree; ++m) {
     if (m > 1) {
       double const sn = 1 / (tau - sigma);
-      for (size_t j = 0; j < p; ++j) {
+      for (size_t j = 0; j < q; ++j) {
         double const y = 2 * sn / e * (r->theta[j] - cc) * y1[j] - sigma * sn * y0[j];
         y0[j] = y1[j]; y1[j] = y;
       }
       sigma = sn;
     }
     double lo = INFINITY, hi = 0;
-    for (size_t j = 0; j < p; ++j) {
+    for (size_t j = 0; j < q; ++j) {
       double const v = fabs(y1[j]);
       if (v < lo) lo = v;
       if (v > hi) hi = v;
@@ -348,8 +386,17 @@ static int eigsFilter(EigsRun *r, uint32_t degree, double lamMax, uint32_t *used
 
 int bfhipChebCovEigsDevice(BfhipChebCov *c, BfhipEigsOptions const *opt, size_t nev, double *lam, double *residual, double *dU, size_t ldu,
                            BfhipEigsInfo *info, void *stream) {
+  return bfEigsSolve(c, opt, NULL, NULL, nev, lam, residual, dU, ldu, info, stream);
+}
+
+/* Both entries.  `full` is the object's n (rows of every block); n below is n - m, the dimension of the space that is left, which
+ * takes n's place in every limit.  With m == 0 nothing here differs from section 25: the same launches in the same order. */
+int bfEigsSolve(BfhipChebCov *c, BfhipEigsOptions const *opt, BfhipEigsLocked const *locked, BfEigsDeflation const *defl, size_t nev, double *lam,
+                double *residual, double *dU, size_t ldu, BfhipEigsInfo *info, void *stream) {
   if (!c || !lam || !dU) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "NULL argument");
-  uint64_t const n = c->n;
+  uint64_t const full = c->n;
+  uint64_t const m = locked && locked->structSize == sizeof *locked ? locked->count : 0;
+  uint64_t const n = m < full ? full - m : 0;
   if (nev == 0 || nev > 255 || nev > n) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "nev out of range (1 .. min(n, 255))");
   if (ldu < nev) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "ldu is less than nev");
   if (opt && opt->structSize != sizeof *opt) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "structSize is not sizeof(BfhipEigsOptions)");
@@ -372,53 +419,76 @@ int bfhipChebCovEigsDevice(BfhipChebCov *c, BfhipEigsOptions const *opt, size_t 
   double tol = opt ? opt->tol : 0;
   if (!(tol >= 0) || !isfinite(tol)) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "tol is negative or not finite");
   if (tol == 0) tol = 1e-10;
+  double lockMin = 0;
+  if (locked) {
+    if (locked->structSize != sizeof *locked) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "structSize is not sizeof(BfhipEigsLocked)");
+    if (m && (!locked->dVectors || !locked->lam)) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "locked: count > 0 with NULL dVectors or lam");
+    if (locked->ld < m) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "locked: ld is less than count");
+    if (m >= full) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "locked: count is not below n");
+    for (uint64_t k = 0; k < m; ++k) {
+      if (!isfinite(locked->lam[k]) || locked->lam[k] > c->lamMax)
+        return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "locked: eigenvalue %llu is not finite or lies above lamMax", (unsigned long long)k);
+      if (!k || locked->lam[k] < lockMin) lockMin = locked->lam[k];
+    }
+    if (m && (flags & BFHIP_EIGS_MASS_NORMALISED))
+      return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "locked: BFHIP_EIGS_MASS_NORMALISED with locked vectors (they must be U; bfhipChebCovEigsMassNormaliseDevice scales at the end)");
+    if (m && !defl) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "locked: no projection");
+  }
 
-  EigsRun r = { .c = c, .n = n, .p = (uint32_t)(nev + guard), .nev = (uint32_t)nev, .ix = 0, .iy = 1, .iz = 2, .stream = stream };
+  EigsRun r = { .c = c, .n = full, .p = (uint32_t)(nev + guard), .nev = (uint32_t)nev, .ix = 0, .iy = 1, .iz = 2, .stream = stream,
+                .dQ = m ? locked->dVectors : NULL, .ldq = m ? locked->ld : 0, .m = m, .lockMin = lockMin, .project = m ? defl->project : NULL };
   r.ld = (r.p + 15) / 16 * 16;
   size_t const p = r.p, ld = r.ld;
-  uint64_t const chunkRows = bfdevEigsChunkRows(n, r.ld), chunks = (n + chunkRows - 1) / chunkRows;
-  uint64_t const blockElems = n * ld, partElems = chunks * ld * ld, smallElems = 2 * ld * ld + 2 * ld;
-  uint64_t const bytes = (3 * blockElems + partElems + smallElems) * 8;
+  uint64_t const chunkRows = bfdevEigsChunkRows(full, r.ld), chunks = (full + chunkRows - 1) / chunkRows;
+  uint64_t const blockElems = full * ld, partElems = chunks * ld * ld, smallElems = 2 * ld * ld + 2 * ld;
+  /* one panel's coefficients and their per-chunk partials: a function of (n, ld, m) alone */
+  uint64_t const m16 = m < 256 ? (m + 15) / 16 * 16 : 256;
+  uint64_t const crossRows = m ? defl->chunkRows(full, r.ld) : 1, crossChunks = m ? (full + crossRows - 1) / crossRows : 0;
+  uint64_t const coefElems = m16 * ld, crossElems = crossChunks * m16 * ld;
+  uint64_t const bytes = (3 * blockElems + partElems + smallElems + coefElems + crossElems) * 8;
   void *dAll = NULL;
   double *host = NULL;
   uint32_t iterations = 0, converged = 0, maxDegree = 0;
   int rc, stored = 0;
   BfDevScope ds = {0};
-  if (eigsProfileOn) memset(eigsPhases, 0, sizeof eigsPhases);
+  if (eigsProfileOn) { memset(eigsPhases, 0, sizeof eigsPhases); eigsHistoryCount = 0; }
   if ((rc = bfDevEnter(&ds, c->device))) return rc;
-  host = malloc((2 * ld * ld + 4 * ld) * sizeof *host);
+  host = malloc((2 * ld * ld + 4 * ld + 3) * sizeof *host);
   if (!host) { rc = bfhipFail(BFABI_ERROR_MEMORY_ERROR, "out of host memory"); goto out; }
-  r.G = host; r.W = host + ld * ld; r.theta = r.W + ld * ld; r.res = r.theta + ld; r.work = r.res + ld;
+  r.G = host; r.W = host + ld * ld; r.theta = r.W + ld * ld; r.res = r.theta + ld + 1; r.work = r.res + ld;          /* theta: ld + 1, work: 2 ld + 2 */
   if ((rc = bfdevMalloc(&dAll, bytes))) goto out;
   for (int k = 0; k < 3; ++k) r.B[k] = (double *)dAll + (uint64_t)k * blockElems;
   r.dPart = (double *)dAll + 3 * blockElems;
   r.dG = r.dPart + partElems; r.dW = r.dG + ld * ld; r.dTheta = r.dW + ld * ld; r.dSumSq = r.dTheta + ld;
+  r.dC = r.dSumSq + ld; r.dPartC = r.dC + coefElems;
 
   /* ---- the start block: X[i][j] = N(seed, i p + j); the padding columns of all three blocks are zero from here on ---- */
   uint64_t const seed = opt ? opt->seed : 0;
   if (p == ld) {
-    if ((rc = bfdevFillNormal(r.B[0], n * p, 0, BFHIP_F64, seed, stream)) || (rc = bfdevMemsetAsync(r.B[1], 0, 2 * blockElems * 8, stream))) goto out;
+    if ((rc = bfdevFillNormal(r.B[0], full * p, 0, BFHIP_F64, seed, stream)) || (rc = bfdevMemsetAsync(r.B[1], 0, 2 * blockElems * 8, stream))) goto out;
   } else {
-    if ((rc = bfdevMemsetAsync(r.B[0], 0, blockElems * 8, stream)) || (rc = bfdevFillNormal(r.B[1], n * p, 0, BFHIP_F64, seed, stream)) ||
-        (rc = bfdevMemcpy2DAsync(r.B[0], ld * 8, r.B[1], p * 8, p * 8, n, stream)) || (rc = bfdevMemsetAsync(r.B[1], 0, 2 * blockElems * 8, stream))) goto out;
+    if ((rc = bfdevMemsetAsync(r.B[0], 0, blockElems * 8, stream)) || (rc = bfdevFillNormal(r.B[1], full * p, 0, BFHIP_F64, seed, stream)) ||
+        (rc = bfdevMemcpy2DAsync(r.B[0], ld * 8, r.B[1], p * 8, p * 8, full, stream)) || (rc = bfdevMemsetAsync(r.B[1], 0, 2 * blockElems * 8, stream))) goto out;
   }
 
   if ((rc = eigsRayleighRitz(&r))) goto out;
+  eigsRecord(r.res, nev, c->lamMax, 0);
   for (;;) {
     converged = 0;
     while (converged < nev && r.res[converged] <= tol * c->lamMax) ++converged;
     if (converged == nev || iterations == maxIter) break;
+    uint32_t used = 0;
     if (p < n) {
-      uint32_t used = 0;
       if ((rc = eigsFilter(&r, degree, c->lamMax, &used))) goto out;
       if (used > maxDegree) maxDegree = used;
     }
     ++iterations;
     if ((rc = eigsRayleighRitz(&r))) goto out;
+    eigsRecord(r.res, nev, c->lamMax, used);
   }
 
   /* ---- the outputs, converged or not ---- */
-  if ((rc = bfdevEigsStore(r.B[r.ix], n, r.ld, r.nev, flags & BFHIP_EIGS_MASS_NORMALISED ? (double const *)c->dD : NULL, dU, ldu, stream)) ||
+  if ((rc = bfdevEigsStore(r.B[r.ix], full, r.ld, r.nev, flags & BFHIP_EIGS_MASS_NORMALISED ? (double const *)c->dD : NULL, dU, ldu, stream)) ||
       (rc = bfdevSync(stream))) goto out;
   stored = 1;
   if (converged < nev)

@@ -551,9 +551,32 @@ int bfdevEigsGram(double const *X, double const *Y, uint64_t n, uint32_t ld, dou
 int bfdevEigsRotate(double const *X, double const *W, double *out, uint64_t n, uint32_t ld, void *stream);
 int bfdevEigsResidual(double const *X, double const *Y, double const *theta, uint64_t n, uint32_t ld, double *part, double *sumSq, void *stream);
 int bfdevEigsStore(double const *X, uint64_t n, uint32_t ld, uint32_t nev, double const *d, double *dst, uint64_t ldu, void *stream);
+/* deflation against locked eigenvectors.  dQ [n x >= m0 + mq, row-major, leading dimension ldq] lies in the
+ * caller's layout: no alignment beyond 8 bytes of dQ, ldq or m0; a panel is the mq <= 256 columns from m0.  mq16 = mq rounded up to 16.
+ *   crossGram: C [mq16 x ld] = Q[:, m0 .. m0 + mq)^T X, rows from mq on exact +0; partials per chunk of bfdevEigsCrossChunkRows rows in
+ *              `part` (chunks x mq16 x ld), summed in chunk order
+ *   deflate:   X <- X - Q[:, m0 .. m0 + mq) C in place (C as crossGram leaves it)
+ *   project:   one pass over all m locked columns, panel by panel: crossGram, then deflate; part: chunks x min(m16, 256) x ld, C: min(m16, 256) x ld */
+uint64_t bfdevEigsCrossChunkRows(uint64_t n, uint32_t ld);
+int bfdevEigsCrossGram(double const *dQ, uint64_t ldq, uint64_t m0, uint32_t mq, double const *X, uint64_t n, uint32_t ld, double *part, double *C,
+                       void *stream);
+int bfdevEigsDeflate(double const *dQ, uint64_t ldq, uint64_t m0, uint32_t mq, double const *C, double *X, uint64_t n, uint32_t ld, void *stream);
+int bfdevEigsProject(double const *dQ, uint64_t ldq, uint64_t m, double *X, uint64_t n, uint32_t ld, double *part, double *C, void *stream);
 /* host, bfhip_eigs.c: the eigenpairs of a symmetric p x p matrix (row-major, lda), ascending, Q's columns the vectors; outside the
  * public header so that tests/native/eigs_symeig_check.c can call it alone.  work: 2 p doubles.  Returns 0, or 1 when QL did not converge */
 int bfEigsSymEig(size_t p, double *A, size_t lda, double *theta, double *work);
+/* host, bfhip_eigs.c: the iteration behind bfhipChebCovEigsDevice (locked NULL, defl NULL) and bfhipChebCovEigsBandDevice
+ * (bfhip_eigs_band.c, which passes { bfdevEigsProject, bfdevEigsCrossChunkRows }: bfhip_eigs.c itself names no launch newer than
+ * section 25's, so that tests/native/eigs_symeig_check.c still links it against its fixed list of stand-ins).  project runs one
+ * projection pass; chunkRows sizes the partials it needs. */
+typedef int (*BfEigsProjectFn)(double const *dQ, uint64_t ldq, uint64_t m, double *X, uint64_t n, uint32_t ld, double *part, double *C, void *stream);
+typedef struct BfEigsDeflation { BfEigsProjectFn project; uint64_t (*chunkRows)(uint64_t n, uint32_t ld); } BfEigsDeflation;
+/* the last profiled call of this thread (bfEigsProfile; tools/lbo_bands_rate.py): seconds spent projecting, and per Rayleigh-Ritz
+ * step (at most 128 are kept) the largest residual of the wanted pairs over lamMax and the degree of the filter before it */
+double bfEigsLastProjectSeconds(void);
+uint32_t bfEigsLastHistory(double *residual, uint32_t *degree, uint32_t cap);
+int bfEigsSolve(BfhipChebCov *c, BfhipEigsOptions const *opt, BfhipEigsLocked const *locked, BfEigsDeflation const *defl, size_t nev, double *lam,
+                double *residual, double *dU, size_t ldu, BfhipEigsInfo *info, void *stream);
 /* phase seconds of the last bfhipChebCovEigsDevice of this thread when bfEigsProfile(1) was called before (tools/lbo_eigs_rate.py):
  * filter, S X, Gram, rotate, residual, host dense, summed over the call; the phases are then separated by stream synchronisations */
 void bfEigsProfile(int on);

@@ -883,7 +883,8 @@ int bfhipChebCovCondLogLikGradDevice(BfhipCovCond *c, const double *dY, const do
  * columns -- what the reference takes from ARPACK and UMFPACK (bfGetShiftedEigs, src/linalg.c) for the lowest band, with
  * no factorisation.  lam[j] = theta_j ascending; dU [n x nev, row-major, leading dimension ldu] = the orthonormal
  * eigenvectors U of S (U^T U = I), or with BFHIP_EIGS_MASS_NORMALISED Phi = D U (Phi^T M Phi = I), the eigenfunctions of
- * the pencil.  Lumped mass only: the reference's consistent-mass pencil has other numbers.  Lowest pairs only, p <= 256.
+ * the pencil.  Lumped mass only: the reference's consistent-mass pencil has other numbers.  Lowest pairs only, p <= 256 per
+ * call; bfhipChebCovEigsBandDevice below continues where a call stopped.
  *
  * Per outer iteration: a degree-m Chebyshev filter that damps [largest Ritz value, lamMax] (m <= degree, lowered so that
  * the filtered block's condition number stays below 2^23), Cholesky QR twice, Rayleigh-Ritz, residuals
@@ -928,6 +929,38 @@ typedef struct BfhipEigsInfo {
 int bfhipChebCovEigsDevice(BfhipChebCov *c, const BfhipEigsOptions *opt /* NULL = defaults */, size_t nev,
                            double *lam /* host, nev, ascending */, double *residual /* host, nev, or NULL */,
                            double *dU /* device, n x nev row-major */, size_t ldu, BfhipEigsInfo *info /* or NULL */, void *stream);
+
+/* The next band: the nev pairs of S that follow m locked ones (the m lowest, found by earlier calls), ascending, with the
+ * conventions of bfhipChebCovEigsDevice -- so any number of pairs, a band of nev <= 255 at a time.  The algorithm is the same
+ * with the block kept orthogonal to the locked vectors Q: before every orthonormalisation (of the start block and of each
+ * filtered block) X <- X - Q (Q^T X) is applied twice, on the device, Q in panels of at most 256 columns one after the other;
+ * the filter's degree is lowered further so that the locked directions, which it amplifies most, stay below 2^23 times the
+ * block's least amplified Ritz direction (min(locked.lam) is one more point of the cap).  Limits: nev <= min(n - m, 255),
+ * p = nev + guard <= min(n - m, 256); with p == n - m the first Rayleigh-Ritz step is exact and no filter runs;
+ * BFHIP_EIGS_NO_GUARD is legal only for nev == n - m; the default guard is clipped to n - m - nev.
+ *
+ * Intended use: one wide array dAll [n x total]; call k passes locked = {m, dAll, total, lamAll}, dU = dAll + m, ldu = total.
+ * The call writes columns m .. m + nev - 1 and nothing beside them, and only reads the locked columns.  The locked block must
+ * be U (orthonormal), so BFHIP_EIGS_MASS_NORMALISED is refused with count > 0: keep U across the bands and call
+ * bfhipChebCovEigsMassNormaliseDevice once at the end.  With locked NULL or count 0 the call is bfhipChebCovEigsDevice.
+ *
+ * Errors before the device is touched: those of bfhipChebCovEigsDevice in its order, with n - m in place of n; then
+ * INVALID_ARGUMENTS for a wrong locked->structSize; count > 0 with NULL dVectors or lam; ld < count; count >= n; a locked
+ * eigenvalue that is not finite or lies above lamMax; BFHIP_EIGS_MASS_NORMALISED together with count > 0. */
+typedef struct BfhipEigsLocked {
+  uint32_t structSize;     /* in: sizeof(BfhipEigsLocked) */
+  uint32_t reserved;
+  uint64_t count;          /* m >= 0 locked pairs: the m lowest of S */
+  const double *dVectors;  /* device, n x count row-major, orthonormal eigenvectors U of S (not mass-normalised) */
+  uint64_t ld;             /* >= count; no alignment beyond 8 bytes is required of dVectors or ld */
+  const double *lam;       /* host, count eigenvalues of the locked pairs */
+} BfhipEigsLocked;
+
+int bfhipChebCovEigsBandDevice(BfhipChebCov *c, const BfhipEigsOptions *opt, const BfhipEigsLocked *locked /* NULL or count 0: none */,
+                               size_t nev, double *lam, double *residual, double *dU, size_t ldu, BfhipEigsInfo *info, void *stream);
+/* dU[i][j] <- d[i] dU[i][j], j < count, in place (U -> Phi = D U): one multiplication per element.  INVALID_ARGUMENTS for a
+ * NULL c or dU (with count > 0) and for ldu < count. */
+int bfhipChebCovEigsMassNormaliseDevice(BfhipChebCov *c, double *dU, size_t ldu, size_t count, void *stream);
 
 /* ---- plan inspection (no device needed) ---------------------------------- */
 /* The flattened per-stage layout, as the kernels see it.  Valid only for an
