@@ -1,2 +1,2 @@
-from .cheb import ChebCovariance, cheb_eval, cheb_fit, matern_density, matern_density_grad, trimesh_lbo_fem  # noqa: F401
+from .cheb import ChebCovariance, cheb_eval, cheb_fit, matern_density, matern_density_grad, trimesh_lbo_fem, trimesh_lbo_fem_mass  # noqa: F401
 from .operator import ChebCovCondition, CovCondition  # noqa: F401

@@ -161,11 +161,12 @@ class BfhipChebCovInfo(C.Structure):
 
 EIGS_MASS_NORMALISED = 1   # BFHIP_EIGS_MASS_NORMALISED
 EIGS_NO_GUARD = 2          # BFHIP_EIGS_NO_GUARD
+EIGS_CONSISTENT_MASS = 4   # BFHIP_EIGS_CONSISTENT_MASS
 
 
 class BfhipEigsOptions(C.Structure):
     _fields_ = [("structSize", C.c_uint32), ("guard", C.c_uint32), ("degree", C.c_uint32), ("maxIter", C.c_uint32), ("tol", C.c_double),
-                ("seed", C.c_uint64), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+                ("seed", C.c_uint64), ("flags", C.c_uint32), ("massSteps", C.c_uint32)]
 
 
 class BfhipEigsInfo(C.Structure):
@@ -603,6 +604,10 @@ def load():
     lib.bfhipChebCovEigsBandDevice.restype = C.c_int
     lib.bfhipChebCovEigsMassNormaliseDevice.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp]
     lib.bfhipChebCovEigsMassNormaliseDevice.restype = C.c_int
+    lib.bfhipTrimeshLboFemMass.argtypes = [C.c_uint64, vp, C.c_uint64, vp, vp, vp, vp]
+    lib.bfhipTrimeshLboFemMass.restype = C.c_int
+    lib.bfhipChebCovSetConsistentMass.argtypes = [vp, vp, C.c_double, C.c_double]
+    lib.bfhipChebCovSetConsistentMass.restype = C.c_int
     lib.bfhipSetProfileSampling.argtypes = [vp, C.c_uint32]
     lib.bfhipSetProfileSampling.restype = C.c_int
     lib.bfhipPlanGetInfo.argtypes = [vp, C.POINTER(BfhipPlanInfo)]

@@ -68,6 +68,23 @@ def trimesh_lbo_fem(verts, faces):
     return rowptr, colind, data, mass
 
 
+def trimesh_lbo_fem_mass(verts, faces, rowptr, colind):
+    """The P1 consistent mass M of the mesh on the pattern trimesh_lbo_fem returned (bfhipTrimeshLboFemMass): host [nnz]."""
+    lib = _capi.load()
+    verts = np.ascontiguousarray(verts, dtype=np.float64)
+    faces = np.ascontiguousarray(faces, dtype=np.uint64)
+    rowptr = np.ascontiguousarray(rowptr, dtype=np.uint64)
+    colind = np.ascontiguousarray(colind, dtype=np.uint64)
+    if verts.ndim != 2 or verts.shape[1] != 3 or faces.ndim != 2 or faces.shape[1] != 3:
+        raise ValueError("verts is [numVerts, 3], faces is [numFaces, 3]")
+    if rowptr.shape != (verts.shape[0] + 1,) or colind.ndim != 1 or int(rowptr[-1]) != colind.size:
+        raise ValueError("rowptr [numVerts + 1], colind [nnz] with rowptr[-1] == nnz")
+    mdata = np.zeros(colind.size, dtype=np.float64)
+    check(lib.bfhipTrimeshLboFemMass(verts.shape[0], verts.ctypes.data, faces.shape[0], faces.ctypes.data, rowptr.ctypes.data, colind.ctypes.data,
+                                     mdata.ctypes.data))
+    return mdata
+
+
 class ChebCovariance:
     """S = D L D on the device and a Chebyshev polynomial p of it (include/bfhip.h, "matrix-free Chebyshev covariance")."""
 
@@ -91,12 +108,32 @@ class ChebCovariance:
         h = C.c_void_p()
         check(lib.bfhipChebCovCreate(int(device), n, rowptr.ctypes.data, colind.ctypes.data, data.ctypes.data,
                                      mass.ctypes.data if mass is not None else None, 0.0 if lam_max is None else float(lam_max), C.byref(h)))
-        return cls(h, n, device)
+        obj = cls(h, n, device)
+        obj._nnz = int(colind.size)
+        return obj
 
     @classmethod
-    def from_trimesh(cls, verts, faces, lam_max=None, device=0):
+    def from_trimesh(cls, verts, faces, lam_max=None, device=0, consistent_mass=False):
+        """consistent_mass: also set the P1 consistent mass of the mesh (set_consistent_mass with the P1 bounds)."""
         rowptr, colind, data, mass = trimesh_lbo_fem(verts, faces)
-        return cls.from_csr(rowptr, colind, data, mass, lam_max=lam_max, device=device)
+        obj = cls.from_csr(rowptr, colind, data, mass, lam_max=lam_max, device=device)
+        if consistent_mass:
+            obj.set_consistent_mass(trimesh_lbo_fem_mass(verts, faces, rowptr, colind))
+        return obj
+
+    def set_consistent_mass(self, mdata, lo=None, hi=None):
+        """The consistent mass M for eigs(..., consistent_mass=True): its nnz values on the object's pattern, host
+        (bfhipChebCovSetConsistentMass).  [lo, hi] must enclose the spectrum of D M D; None, None asks for the P1 bounds
+        [1/4, 1], accepted when the rows of M sum to the lumped mass."""
+        mdata = np.ascontiguousarray(mdata, dtype=np.float64)
+        nnz = getattr(self, "_nnz", None)
+        if nnz is None:
+            nnz = self.info()["nnz"]
+        if mdata.shape != (nnz,):
+            raise ValueError("mdata is [nnz] on the object's pattern")
+        if (lo is None) != (hi is None):
+            raise ValueError("give both bounds or neither")
+        check(self._lib.bfhipChebCovSetConsistentMass(self._h, mdata.ctypes.data, 0.0 if lo is None else float(lo), 0.0 if hi is None else float(hi)))
 
     def close(self):
         if self._h:
@@ -204,13 +241,16 @@ class ChebCovariance:
         check(self._lib.bfhipChebCovMomentsDevice(self._h, int(seed), int(first), int(num), int(batch), ptr(sum), ptr(sumsq), self._stream()))
         return sum, sumsq
 
-    def eigs(self, nev, guard=None, degree=None, tol=None, max_iter=None, seed=0, mass_normalised=False, ldu=None, raise_on_limit=True):
+    def eigs(self, nev, guard=None, degree=None, tol=None, max_iter=None, seed=0, mass_normalised=False, ldu=None, raise_on_limit=True,
+             consistent_mass=False, mass_steps=None):
         """The nev lowest eigenpairs of the lumped-mass pencil L phi = lambda M phi (bfhipChebCovEigsDevice): Chebyshev-filtered
         subspace iteration on the device, synchronous.  Returns (lam: numpy [nev] ascending, U: float64 [n, nev] on the GPU,
         info: dict with the residuals under "residual" and the return code under "code").  U has orthonormal columns
         (eigenvectors of S = D L D); with mass_normalised it is Phi = D U, Phi^T M Phi = I.  guard: extra block columns
         (None: the default, 0: none, legal only when nev == n).  ldu > nev returns U as the leading columns of a zero-filled
-        [n, ldu] tensor.  raise_on_limit=False returns the best pairs found instead of raising when max_iter was reached."""
+        [n, ldu] tensor.  raise_on_limit=False returns the best pairs found instead of raising when max_iter was reached.
+        consistent_mass: the pencil of set_consistent_mass, L phi = lambda M phi with the consistent M; U then satisfies
+        U^T B U = I, B = D M D, and Phi^T M Phi = I as before; mass_steps: steps of every mass solve (None: the default)."""
         import torch
         nev = int(nev)
         opt = _capi.BfhipEigsOptions()
@@ -221,6 +261,8 @@ class ChebCovariance:
         opt.tol = 0.0 if tol is None else float(tol)
         opt.seed = int(seed)
         opt.flags = (_capi.EIGS_MASS_NORMALISED if mass_normalised else 0) | (_capi.EIGS_NO_GUARD if guard is not None and int(guard) == 0 else 0)
+        opt.flags |= _capi.EIGS_CONSISTENT_MASS if consistent_mass else 0
+        opt.massSteps = 0 if mass_steps is None else int(mass_steps)
         info = _capi.BfhipEigsInfo()
         info.structSize = C.sizeof(info)
         ldu = max(nev, 1) if ldu is None else int(ldu)
@@ -234,12 +276,14 @@ class ChebCovariance:
         out["residual"], out["code"] = res[:nev], rc
         return lam[:nev], full[:, :nev], out
 
-    def eigs_band(self, nev, locked=None, guard=None, degree=None, tol=None, max_iter=None, seed=0, out=None, raise_on_limit=True):
+    def eigs_band(self, nev, locked=None, guard=None, degree=None, tol=None, max_iter=None, seed=0, out=None, raise_on_limit=True,
+                  consistent_mass=False, mass_steps=None):
         """The nev eigenpairs of S that follow the locked ones (bfhipChebCovEigsBandDevice), with what eigs returns.  locked:
         None, (U_all, lam_all, m) -- a float64 [n, total] tensor on this GPU whose first m columns are the locked vectors, and at
         least m eigenvalues -- or (U, lam) with U an [n, m] tensor or view (unit column stride; any row stride).  The locked vectors
         must be orthonormal eigenvectors of S, not mass-normalised.  out: an [n, nev] view to write into (unit column stride),
-        e.g. U_all[:, m:m + nev]; None allocates."""
+        e.g. U_all[:, m:m + nev]; None allocates.  consistent_mass, mass_steps: as in eigs; the locked vectors are then
+        B-orthonormal eigenvectors of the consistent pencil."""
         import torch
         nev = int(nev)
         opt = _capi.BfhipEigsOptions()
@@ -250,6 +294,8 @@ class ChebCovariance:
         opt.tol = 0.0 if tol is None else float(tol)
         opt.seed = int(seed)
         opt.flags = _capi.EIGS_NO_GUARD if guard is not None and int(guard) == 0 else 0
+        opt.flags |= _capi.EIGS_CONSISTENT_MASS if consistent_mass else 0
+        opt.massSteps = 0 if mass_steps is None else int(mass_steps)
         info = _capi.BfhipEigsInfo()
         info.structSize = C.sizeof(info)
         dev = torch.device("cuda", self._dev)
@@ -284,7 +330,8 @@ class ChebCovariance:
         d["residual"], d["code"] = res[:nev], rc
         return lam[:nev], out[:, :nev], d
 
-    def eigs_bands(self, total, band=64, guard=None, degree=None, tol=None, max_iter=None, seed=0, mass_normalised=False):
+    def eigs_bands(self, total, band=64, guard=None, degree=None, tol=None, max_iter=None, seed=0, mass_normalised=False, consistent_mass=False,
+                   mass_steps=None):
         """The `total` lowest eigenpairs in successive bands of `band` (the last one ragged), each deflated against all the
         earlier ones: (lam [total] ascending, U [n, total] on the GPU, the list of per-band info dicts).  A guard that no longer
         fits the space left is clipped.  mass_normalised scales the rows by d once at the end (Phi = D U)."""
@@ -298,7 +345,8 @@ class ChebCovariance:
             nev = min(band, total - m)
             left = self.n - m - nev
             g = 0 if left == 0 else None if guard is None else min(int(guard), left, 256 - nev)
-            lam_b, _, info = self.eigs_band(nev, (U, lam, m), guard=g, degree=degree, tol=tol, max_iter=max_iter, seed=seed, out=U[:, m:m + nev])
+            lam_b, _, info = self.eigs_band(nev, (U, lam, m), guard=g, degree=degree, tol=tol, max_iter=max_iter, seed=seed, out=U[:, m:m + nev],
+                                          consistent_mass=consistent_mass, mass_steps=mass_steps)
             lam[m:m + nev] = lam_b
             infos.append(info)
             m += nev

@@ -169,9 +169,10 @@ void bfhipChebCovFree(BfhipChebCov **pc) {
     BfDevScope ds;
     bfDevEnter(&ds, c->device);      /* a release cannot fail: errors are ignored on purpose */
     bfdevSync(NULL);
-    bfdevFree(c->dRowptr); bfdevFree(c->dColind); bfdevFree(c->dVal); bfdevFree(c->dD); bfdevFree(c->dWork);
+    bfdevFree(c->dRowptr); bfdevFree(c->dColind); bfdevFree(c->dVal); bfdevFree(c->dD); bfdevFree(c->dWork); bfdevFree(c->dMass);
     bfDevLeave(&ds);
   }
+  free(c->hRowptr); free(c->hColind); free(c->hD);
   free(c->coef);
   free(c);
   *pc = NULL;
@@ -199,7 +200,9 @@ int bfhipChebCovCreate(int device, uint64_t n, uint64_t const *rowptr, uint64_t 
   BfhipChebCov *c = calloc(1, sizeof *c);
   double *d = malloc(n * sizeof *d), *val = malloc((nnz ? nnz : 1) * sizeof *val);
   uint32_t *col32 = malloc((nnz ? nnz : 1) * sizeof *col32);
-  if (!c || !d || !val || !col32) { rc = bfhipFail(BFABI_ERROR_MEMORY_ERROR, "out of host memory"); goto fail; }
+  uint64_t *rows = malloc((n + 1) * sizeof *rows);
+  if (!c || !d || !val || !col32 || !rows) { rc = bfhipFail(BFABI_ERROR_MEMORY_ERROR, "out of host memory"); goto fail; }
+  memcpy(rows, rowptr, (n + 1) * sizeof *rows);
   for (uint64_t i = 0; i < n; ++i) d[i] = massLumped ? 1 / sqrt(massLumped[i]) : 1.0;
   double gersh = 0;
   for (uint64_t i = 0; i < n; ++i) {
@@ -223,9 +226,12 @@ int bfhipChebCovCreate(int device, uint64_t n, uint64_t const *rowptr, uint64_t 
   if ((rc = bfdevMemcpyH2D(c->dRowptr, rowptr, (n + 1) * 8)) || (nnz && (rc = bfdevMemcpyH2D(c->dColind, col32, nnz * 4))) ||
       (nnz && (rc = bfdevMemcpyH2D(c->dVal, val, nnz * 8))) || (rc = bfdevMemcpyH2D(c->dD, d, n * 8))) goto fail;
   c->deviceBytes = (n + 1) * 8 + nnz * 4 + nnz * 8 + n * 8;
+  /* the pattern and d stay on the host for bfhipChebCovSetConsistentMass, whose checks and fold run before the device is touched */
+  c->hRowptr = rows; c->hColind = col32; c->hD = d;
+  rows = NULL; col32 = NULL; d = NULL;
   *out = c; c = NULL;
 fail:
-  free(d); free(val); free(col32);
+  free(d); free(val); free(col32); free(rows);
   if (c) bfhipChebCovFree(&c);             /* touches the device only for what was allocated there */
   bfDevLeave(&ds);
   return rc;

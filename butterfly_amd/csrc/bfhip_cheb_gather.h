@@ -1,6 +1,7 @@
-// bfhip_cheb_gather.h -- the row gather shared by bfChebStepKernel (bfhip_cheb.hip) and bfEigsStepKernel (bfhip_eigs.hip):
+// bfhip_cheb_gather.h -- the row gather shared by bfChebStepKernel (bfhip_cheb.hip), bfEigsStepKernel (bfhip_eigs.hip) and
+// bfEigsMassStepKernel (bfhip_eigs_mass.hip, with the mass values in the place of S's):
 // sum_j S[i][j] * b1[col_j, c] for one row i and one column c of a row-major block, the lane layout and the gather groups
-// described at bfChebStepKernel.  Included by those two files only, after <hip/hip_runtime.h>.
+// described at bfChebStepKernel.  Included by those three files only, after <hip/hip_runtime.h>.
 #ifndef BFHIP_CHEB_GATHER_H
 #define BFHIP_CHEB_GATHER_H
 

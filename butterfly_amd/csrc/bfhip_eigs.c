@@ -6,7 +6,9 @@
  * double -- the loop needs the Ritz values and the residuals on the host in every iteration anyway.  The kernels are
  * bfhip_eigs.hip's.  bfEigsSolve is also the iteration of bfhipChebCovEigsBandDevice (bfhip_eigs_band.c):
  * with locked vectors the block is projected against them before every orthonormalisation and their lowest eigenvalue joins
- * the degree cap; with none it is section 25's call, launch for launch. */
+ * the degree cap; with none it is section 25's call, launch for launch.  With BFHIP_EIGS_CONSISTENT_MASS the
+ * same loop solves S u = theta B u: B^-1 S in the filter by a fixed number of Chebyshev semi-iterations, the B inner product in
+ * Rayleigh-Ritz; the launches of bfhip_eigs_mass.hip are reached through the object's table (bfhip_eigs_mass.c), none is named here. */
 #include <math.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -210,6 +212,10 @@ typedef struct EigsRun {
   double lockMin;               /* the smallest locked eigenvalue */
   double *dC, *dPartC;          /* coefficients of one panel [<= 256 x ld] and their per-chunk partials */
   BfEigsProjectFn project;
+  /* the consistent-mass pencil (section 28): ops == NULL in the lumped call, which then runs section 25's launches and no other */
+  BfEigsMassOps const *ops;
+  double *T, *Z2;               /* T = S Y_i of a filter step and B X of Rayleigh-Ritz; the mass solve's second block */
+  uint32_t massSteps;
 } EigsRun;
 
 static void phaseBegin(EigsRun *r) {
@@ -224,6 +230,22 @@ static int eigsStep(EigsRun *r, double const *b1, double const *b2, double *out,
   BfEigsStep s = { c->dRowptr, c->dColind, c->dVal, r->n, r->p, r->ld, b1, b2, out, alpha, beta, gamma };
   r->opColumns += r->p;
   return bfdevEigsStep(&s, r->stream);
+}
+
+/* out = B X: one mass step without its other terms */
+static int eigsMassMul(EigsRun *r, double const *X, double *out) {
+  BfhipChebCov const *c = r->c;
+  BfEigsMassStep s = { c->dRowptr, c->dColind, c->dMass, r->n, r->p, r->ld, X, NULL, NULL, out, 1.0, 0.0, 0.0, 0.0 };
+  r->opColumns += r->p;
+  return r->ops->step(&s, r->stream);
+}
+
+/* Z ~ B^-1 T into the free block; every step but the first applies B */
+static int eigsMassSolve(EigsRun *r) {
+  BfhipChebCov const *c = r->c;
+  BfEigsMassSolve s = { c->dRowptr, c->dColind, c->dMass, r->n, r->p, r->ld, r->T, r->B[r->iz], r->Z2, c->massLo, c->massHi, r->massSteps, 0 };
+  r->opColumns += (uint64_t)r->p * (r->massSteps - 1);
+  return r->ops->solve(&s, r->stream);
 }
 
 static int eigsRotateX(EigsRun *r, double const *W) {
@@ -253,11 +275,20 @@ static int eigsOrthonormalise(EigsRun *r) {
   if (r->m) {
     phaseBegin(r);
     for (int pass = 0; pass < 2; ++pass)
-      if ((rc = r->project(r->dQ, r->ldq, r->m, r->B[r->ix], r->n, r->ld, r->dPartC, r->dC, r->stream))) return rc;
+      if (r->ops) {
+        if ((rc = eigsMassMul(r, r->B[r->ix], r->T)) ||
+            (rc = r->ops->project(r->dQ, r->ldq, r->m, r->T, r->B[r->ix], r->n, r->ld, r->dPartC, r->dC, r->stream))) return rc;
+      } else if ((rc = r->project(r->dQ, r->ldq, r->m, r->B[r->ix], r->n, r->ld, r->dPartC, r->dC, r->stream))) return rc;
     phaseEnd(r, PH_PROJECT);
   }
   while (plain > 0) {
-    if ((rc = eigsGramToHost(r, r->B[r->ix], r->B[r->ix]))) return rc;
+    /* the Gram matrix of the inner product in force: X^T X, or X^T (B X) */
+    if (r->ops) {
+      phaseBegin(r);
+      if ((rc = eigsMassMul(r, r->B[r->ix], r->T))) return rc;
+      phaseEnd(r, PH_SX);
+    }
+    if ((rc = eigsGramToHost(r, r->B[r->ix], r->ops ? r->T : r->B[r->ix]))) return rc;
     double const th = bfNowSeconds();
     memcpy(r->W, r->G, ld * ld * sizeof(double));          /* the Gram matrix survives a failed factorisation in W */
     int bad = eigsCholesky(p, r->G, ld);
@@ -290,7 +321,12 @@ static int eigsRayleighRitz(EigsRun *r) {
   size_t const p = r->p, ld = r->ld;
   if ((rc = eigsOrthonormalise(r))) return rc;
   phaseBegin(r);
-  if ((rc = eigsStep(r, r->B[r->ix], NULL, r->B[r->iy], 1.0, 0.0, 0.0))) return rc;
+  if (r->ops) {
+    /* Y = S X and T = B X from one gather of X's rows; T is rotated with X and Y below */
+    BfhipChebCov const *c = r->c;
+    r->opColumns += 2 * (uint64_t)r->p;
+    if ((rc = r->ops->dual(c->dRowptr, c->dColind, c->dVal, c->dMass, r->n, r->p, r->ld, r->B[r->ix], r->B[r->iy], r->T, r->stream))) return rc;
+  } else if ((rc = eigsStep(r, r->B[r->ix], NULL, r->B[r->iy], 1.0, 0.0, 0.0))) return rc;
   phaseEnd(r, PH_SX);
   if ((rc = eigsGramToHost(r, r->B[r->ix], r->B[r->iy]))) return rc;
   double const th = bfNowSeconds();
@@ -310,11 +346,17 @@ static int eigsRayleighRitz(EigsRun *r) {
   if ((rc = eigsRotateX(r, r->W))) return rc;             /* ix = old free, iz = oldX */
   phaseBegin(r);
   if ((rc = bfdevEigsRotate(r->B[oldY], r->dW, r->B[oldX], r->n, r->ld, r->stream))) return rc;
+  if (r->ops) {
+    /* B X likewise, into the mass solve's second block, which is free between filters */
+    if ((rc = bfdevEigsRotate(r->T, r->dW, r->Z2, r->n, r->ld, r->stream))) return rc;
+    double *t = r->T; r->T = r->Z2; r->Z2 = t;
+  }
   phaseEnd(r, PH_ROTATE);
   r->iy = oldX; r->iz = oldY;
   phaseBegin(r);
+  /* with a mass the residual is Y - (B X) diag(theta): the kernel takes B X in the place of X */
   if ((rc = bfdevMemcpyH2DAsync(r->dTheta, r->theta, ld * 8, r->stream)) ||
-      (rc = bfdevEigsResidual(r->B[r->ix], r->B[r->iy], r->dTheta, r->n, r->ld, r->dPart, r->dSumSq, r->stream)) ||
+      (rc = bfdevEigsResidual(r->ops ? r->T : r->B[r->ix], r->B[r->iy], r->dTheta, r->n, r->ld, r->dPart, r->dSumSq, r->stream)) ||
       (rc = bfdevMemcpyD2HAsync(r->res, r->dSumSq, ld * 8, r->stream)) || (rc = bfdevSync(r->stream))) return rc;
   phaseEnd(r, PH_RESIDUAL);
   for (size_t j = 0; j < p; ++j) {
@@ -370,13 +412,26 @@ static int eigsFilter(EigsRun *r, uint32_t degree, double lamMax, uint32_t *used
   phaseBegin(r);
   /* Y_1 into the Y block; from there on the result is written over Y_{i-1} */
   double *prev = r->B[r->ix], *cur = r->B[r->iy];
-  if ((rc = eigsStep(r, prev, NULL, cur, sigma1 / e, -sigma1 * cc / e, 0.0))) return rc;
   double sigma = sigma1;
-  for (uint32_t i = 1; i < m; ++i) {
-    double const sn = 1 / (tau - sigma);
-    if ((rc = eigsStep(r, cur, prev, prev, 2 * sn / e, -2 * sn * cc / e, -sigma * sn))) return rc;
-    double *t = prev; prev = cur; cur = t;
-    sigma = sn;
+  if (r->ops) {
+    /* the same recurrence with A = B^-1 S: T = S Y_i, Z ~ B^-1 T in the free block, then the combination */
+    if ((rc = eigsStep(r, prev, NULL, r->T, 1.0, 0.0, 0.0)) || (rc = eigsMassSolve(r)) ||
+        (rc = r->ops->combine(r->B[r->iz], prev, NULL, cur, r->n, r->p, r->ld, sigma1 / e, -sigma1 * cc / e, 0.0, r->stream))) return rc;
+    for (uint32_t i = 1; i < m; ++i) {
+      double const sn = 1 / (tau - sigma);
+      if ((rc = eigsStep(r, cur, NULL, r->T, 1.0, 0.0, 0.0)) || (rc = eigsMassSolve(r)) ||
+          (rc = r->ops->combine(r->B[r->iz], cur, prev, prev, r->n, r->p, r->ld, 2 * sn / e, -2 * sn * cc / e, -sigma * sn, r->stream))) return rc;
+      double *t = prev; prev = cur; cur = t;
+      sigma = sn;
+    }
+  } else {
+    if ((rc = eigsStep(r, prev, NULL, cur, sigma1 / e, -sigma1 * cc / e, 0.0))) return rc;
+    for (uint32_t i = 1; i < m; ++i) {
+      double const sn = 1 / (tau - sigma);
+      if ((rc = eigsStep(r, cur, prev, prev, 2 * sn / e, -2 * sn * cc / e, -sigma * sn))) return rc;
+      double *t = prev; prev = cur; cur = t;
+      sigma = sn;
+    }
   }
   phaseEnd(r, PH_FILTER);
   if (cur != r->B[r->ix]) { uint32_t const t = r->ix; r->ix = r->iy; r->iy = t; }
@@ -419,6 +474,10 @@ int bfEigsSolve(BfhipChebCov *c, BfhipEigsOptions const *opt, BfhipEigsLocked co
   double tol = opt ? opt->tol : 0;
   if (!(tol >= 0) || !isfinite(tol)) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "tol is negative or not finite");
   if (tol == 0) tol = 1e-10;
+  /* with a mass set the flag moves the spectrum's upper bound -- the filter's upper end and the scale of the tolerance -- to
+   * lamMax / lo (without one the flag is refused below, after every older refusal) */
+  int const consistent = (flags & BFHIP_EIGS_CONSISTENT_MASS) != 0;
+  double const lamTop = consistent && c->dMass ? c->lamMax / c->massLo : c->lamMax;
   double lockMin = 0;
   if (locked) {
     if (locked->structSize != sizeof *locked) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "structSize is not sizeof(BfhipEigsLocked)");
@@ -426,7 +485,7 @@ int bfEigsSolve(BfhipChebCov *c, BfhipEigsOptions const *opt, BfhipEigsLocked co
     if (locked->ld < m) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "locked: ld is less than count");
     if (m >= full) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "locked: count is not below n");
     for (uint64_t k = 0; k < m; ++k) {
-      if (!isfinite(locked->lam[k]) || locked->lam[k] > c->lamMax)
+      if (!isfinite(locked->lam[k]) || locked->lam[k] > lamTop)
         return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "locked: eigenvalue %llu is not finite or lies above lamMax", (unsigned long long)k);
       if (!k || locked->lam[k] < lockMin) lockMin = locked->lam[k];
     }
@@ -434,9 +493,23 @@ int bfEigsSolve(BfhipChebCov *c, BfhipEigsOptions const *opt, BfhipEigsLocked co
       return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "locked: BFHIP_EIGS_MASS_NORMALISED with locked vectors (they must be U; bfhipChebCovEigsMassNormaliseDevice scales at the end)");
     if (m && !defl) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "locked: no projection");
   }
+  uint32_t massSteps = 0;
+  if (consistent) {
+    if (!c->dMass || !c->massOps)
+      return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "BFHIP_EIGS_CONSISTENT_MASS on an object with no consistent mass: call bfhipChebCovSetConsistentMass first");
+    if (opt->massSteps > 64) return bfhipFail(BFABI_ERROR_INVALID_ARGUMENTS, "massSteps is more than 64");
+    massSteps = opt->massSteps;
+    if (!massSteps) {
+      /* the smallest k with 2 rho^k <= tol: 22 at 1e-10 on P1 masses (rho = 1/3) */
+      double const sk = sqrt(c->massHi / c->massLo), rho = (sk - 1) / (sk + 1);
+      double bound = 2 * rho;
+      for (massSteps = 1; massSteps < 64 && bound > tol; ++massSteps) bound *= rho;
+    }
+  }
 
   EigsRun r = { .c = c, .n = full, .p = (uint32_t)(nev + guard), .nev = (uint32_t)nev, .ix = 0, .iy = 1, .iz = 2, .stream = stream,
-                .dQ = m ? locked->dVectors : NULL, .ldq = m ? locked->ld : 0, .m = m, .lockMin = lockMin, .project = m ? defl->project : NULL };
+                .dQ = m ? locked->dVectors : NULL, .ldq = m ? locked->ld : 0, .m = m, .lockMin = lockMin, .project = m ? defl->project : NULL,
+                .ops = consistent ? c->massOps : NULL, .massSteps = massSteps };
   r.ld = (r.p + 15) / 16 * 16;
   size_t const p = r.p, ld = r.ld;
   uint64_t const chunkRows = bfdevEigsChunkRows(full, r.ld), chunks = (full + chunkRows - 1) / chunkRows;
@@ -445,7 +518,8 @@ int bfEigsSolve(BfhipChebCov *c, BfhipEigsOptions const *opt, BfhipEigsLocked co
   uint64_t const m16 = m < 256 ? (m + 15) / 16 * 16 : 256;
   uint64_t const crossRows = m ? defl->chunkRows(full, r.ld) : 1, crossChunks = m ? (full + crossRows - 1) / crossRows : 0;
   uint64_t const coefElems = m16 * ld, crossElems = crossChunks * m16 * ld;
-  uint64_t const bytes = (3 * blockElems + partElems + smallElems + coefElems + crossElems) * 8;
+  uint64_t const blocks = consistent ? 5 : 3;          /* section 28: T and the mass solve's second block */
+  uint64_t const bytes = (blocks * blockElems + partElems + smallElems + coefElems + crossElems) * 8;
   void *dAll = NULL;
   double *host = NULL;
   uint32_t iterations = 0, converged = 0, maxDegree = 0;
@@ -458,33 +532,35 @@ int bfEigsSolve(BfhipChebCov *c, BfhipEigsOptions const *opt, BfhipEigsLocked co
   r.G = host; r.W = host + ld * ld; r.theta = r.W + ld * ld; r.res = r.theta + ld + 1; r.work = r.res + ld;          /* theta: ld + 1, work: 2 ld + 2 */
   if ((rc = bfdevMalloc(&dAll, bytes))) goto out;
   for (int k = 0; k < 3; ++k) r.B[k] = (double *)dAll + (uint64_t)k * blockElems;
-  r.dPart = (double *)dAll + 3 * blockElems;
+  if (consistent) { r.T = (double *)dAll + 3 * blockElems; r.Z2 = (double *)dAll + 4 * blockElems; }
+  r.dPart = (double *)dAll + blocks * blockElems;
   r.dG = r.dPart + partElems; r.dW = r.dG + ld * ld; r.dTheta = r.dW + ld * ld; r.dSumSq = r.dTheta + ld;
   r.dC = r.dSumSq + ld; r.dPartC = r.dC + coefElems;
 
   /* ---- the start block: X[i][j] = N(seed, i p + j); the padding columns of all three blocks are zero from here on ---- */
   uint64_t const seed = opt ? opt->seed : 0;
   if (p == ld) {
-    if ((rc = bfdevFillNormal(r.B[0], full * p, 0, BFHIP_F64, seed, stream)) || (rc = bfdevMemsetAsync(r.B[1], 0, 2 * blockElems * 8, stream))) goto out;
+    if ((rc = bfdevFillNormal(r.B[0], full * p, 0, BFHIP_F64, seed, stream)) || (rc = bfdevMemsetAsync(r.B[1], 0, (blocks - 1) * blockElems * 8, stream))) goto out;
   } else {
     if ((rc = bfdevMemsetAsync(r.B[0], 0, blockElems * 8, stream)) || (rc = bfdevFillNormal(r.B[1], full * p, 0, BFHIP_F64, seed, stream)) ||
-        (rc = bfdevMemcpy2DAsync(r.B[0], ld * 8, r.B[1], p * 8, p * 8, full, stream)) || (rc = bfdevMemsetAsync(r.B[1], 0, 2 * blockElems * 8, stream))) goto out;
+        (rc = bfdevMemcpy2DAsync(r.B[0], ld * 8, r.B[1], p * 8, p * 8, full, stream)) ||
+        (rc = bfdevMemsetAsync(r.B[1], 0, (blocks - 1) * blockElems * 8, stream))) goto out;
   }
 
   if ((rc = eigsRayleighRitz(&r))) goto out;
-  eigsRecord(r.res, nev, c->lamMax, 0);
+  eigsRecord(r.res, nev, lamTop, 0);
   for (;;) {
     converged = 0;
-    while (converged < nev && r.res[converged] <= tol * c->lamMax) ++converged;
+    while (converged < nev && r.res[converged] <= tol * lamTop) ++converged;
     if (converged == nev || iterations == maxIter) break;
     uint32_t used = 0;
     if (p < n) {
-      if ((rc = eigsFilter(&r, degree, c->lamMax, &used))) goto out;
+      if ((rc = eigsFilter(&r, degree, lamTop, &used))) goto out;
       if (used > maxDegree) maxDegree = used;
     }
     ++iterations;
     if ((rc = eigsRayleighRitz(&r))) goto out;
-    eigsRecord(r.res, nev, c->lamMax, used);
+    eigsRecord(r.res, nev, lamTop, used);
   }
 
   /* ---- the outputs, converged or not ---- */
@@ -507,7 +583,7 @@ out:
       memset(info, 0, sizeof *info);
       info->structSize = ss; info->iterations = iterations; info->converged = converged; info->blockColumns = r.p;
       info->maxDegreeUsed = maxDegree; info->operatorColumns = r.opColumns; info->workspaceBytes = bytes;
-      info->maxResidual = worst / c->lamMax; info->lamMax = c->lamMax;
+      info->maxResidual = worst / lamTop; info->lamMax = lamTop;
     }
   }
   if (dAll) { bfdevSync(stream); bfdevFree(dAll); }

@@ -526,6 +526,15 @@ struct BfhipChebCov {
   uint64_t generation;          /* bumped by every SetCoefficients: a conditioning object made before it is stale */
   void *dWork;
   uint64_t workBytes;
+  /* the consistent mass of the eigensolver (bfhipChebCovSetConsistentMass, bfhip_eigs_mass.c): host copies of
+   * the pattern and of d, which the fold and its checks read before the device is touched; B = D M D on S's pattern (NULL: none
+   * set), an interval that encloses its spectrum, and the launches of bfhip_eigs_mass.hip */
+  uint64_t *hRowptr;
+  uint32_t *hColind;
+  double *hD;
+  void *dMass;
+  double massLo, massHi;
+  struct BfEigsMassOps const *massOps;
 };
 
 /* filtered subspace iteration on S (bfhip_eigs.hip; driven by bfhip_eigs.c).  Blocks are row-major n x ld doubles, ld = p
@@ -562,6 +571,60 @@ int bfdevEigsCrossGram(double const *dQ, uint64_t ldq, uint64_t m0, uint32_t mq,
                        void *stream);
 int bfdevEigsDeflate(double const *dQ, uint64_t ldq, uint64_t m0, uint32_t mq, double const *C, double *X, uint64_t n, uint32_t ld, void *stream);
 int bfdevEigsProject(double const *dQ, uint64_t ldq, uint64_t m, double *X, uint64_t n, uint32_t ld, double *part, double *C, void *stream);
+/* the consistent-mass pencil S u = theta B u (bfhip_eigs_mass.hip).  B lies on S's pattern (rowptr, colind) with
+ * values of its own.
+ *   massStep: out = alpha (B b1) + beta b1 + gamma b2 + delta w on the first p columns.  b1 == NULL drops its two terms (no gather),
+ *             b2 == NULL and w == NULL theirs; out may be b2 and nothing else the launch reads
+ *   massSolve: z ~ B^-1 t by `steps` >= 1 steps of the three-term Chebyshev semi-iteration on [lo, hi] from z = 0, one massStep each
+ *             (the first has no product: z_1 = 2 / (hi + lo) t); `work` is a second block; the result is in z, work holds z_{steps-1}
+ *   combine:  out = a z + b y1 + g y2 on the first p columns, y2 == NULL drops its term, out may be y2
+ *   projectMass: X <- X - Q (Q^T BX) over all m locked columns with BX given: per panel of <= 256 crossGram(Q, BX), deflate(Q, C, X)
+ *   dualProduct: outS = S b1 and outB = B b1 from one gather of b1's rows, each bit-equal to its single launch (Rayleigh-Ritz needs both
+ *             of the same X; 0.64 of the two launches' time at n = 2^20, p = 64) */
+typedef struct BfEigsMassStep {
+  uint64_t const *rowptr;
+  uint32_t const *colind;
+  double const *val;
+  uint64_t n;
+  uint32_t p, ld;
+  double const *b1, *b2, *w;
+  double *out;
+  double alpha, beta, gamma, delta;
+} BfEigsMassStep;
+typedef struct BfEigsMassSolve {
+  uint64_t const *rowptr;
+  uint32_t const *colind;
+  double const *val;
+  uint64_t n;
+  uint32_t p, ld;
+  double const *t;
+  double *z, *work;
+  double lo, hi;
+  uint32_t steps, reserved;
+} BfEigsMassSolve;
+int bfdevEigsMassStep(BfEigsMassStep const *s, void *stream);
+int bfdevEigsMassSolve(BfEigsMassSolve const *s, void *stream);
+int bfdevEigsCombine(double const *z, double const *y1, double const *y2, double *out, uint64_t n, uint32_t p, uint32_t ld, double a, double b,
+                     double g, void *stream);
+int bfdevEigsDualProduct(uint64_t const *rowptr, uint32_t const *colind, double const *valS, double const *valB, uint64_t n, uint32_t p, uint32_t ld,
+                         double const *b1, double *outS, double *outB, void *stream);
+int bfdevEigsProjectMass(double const *dQ, uint64_t ldq, uint64_t m, double const *BX, double *X, uint64_t n, uint32_t ld, double *part, double *C,
+                         void *stream);
+/* what bfhip_eigs.c calls through the object (bfhipChebCovSetConsistentMass stores the table: bfhip_eigs.c names none of these launches) */
+typedef struct BfEigsMassOps {
+  int (*step)(BfEigsMassStep const *s, void *stream);
+  int (*solve)(BfEigsMassSolve const *s, void *stream);
+  int (*combine)(double const *z, double const *y1, double const *y2, double *out, uint64_t n, uint32_t p, uint32_t ld, double a, double b, double g,
+                 void *stream);
+  int (*project)(double const *dQ, uint64_t ldq, uint64_t m, double const *BX, double *X, uint64_t n, uint32_t ld, double *part, double *C,
+                 void *stream);
+  int (*dual)(uint64_t const *rowptr, uint32_t const *colind, double const *valS, double const *valB, uint64_t n, uint32_t p, uint32_t ld,
+              double const *b1, double *outS, double *outB, void *stream);
+} BfEigsMassOps;
+/* host, bfhip_eigs_mass.c: the checks of bfhipChebCovSetConsistentMass that need no device and the fold B[k] = (d[i] M[k]) d[col[k]];
+ * outside the public header so that tests/native/fem_mass_check.c can call it alone.  lo <= 0 && hi <= 0: the P1 bounds, after
+ * the row sums and the diagonal were checked; *lo and *hi return the interval in force */
+int bfEigsMassFold(uint64_t n, uint64_t const *rowptr, uint32_t const *colind, double const *d, double const *Mdata, double *lo, double *hi, double *B);
 /* host, bfhip_eigs.c: the eigenpairs of a symmetric p x p matrix (row-major, lda), ascending, Q's columns the vectors; outside the
  * public header so that tests/native/eigs_symeig_check.c can call it alone.  work: 2 p doubles.  Returns 0, or 1 when QL did not converge */
 int bfEigsSymEig(size_t p, double *A, size_t lda, double *theta, double *work);

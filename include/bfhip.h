@@ -804,6 +804,11 @@ double bfhipChebEval(size_t order, double a, double b, const double *coef, doubl
 int bfhipTrimeshLboFemCount(uint64_t numVerts, uint64_t numFaces, const uint64_t *faces, uint64_t *nnz);
 int bfhipTrimeshLboFem(uint64_t numVerts, const double *verts, uint64_t numFaces, const uint64_t *faces, uint64_t *rowptr,
                        uint64_t *colind, double *Ldata, double *massLumped);
+/* The P1 consistent mass on the pattern bfhipTrimeshLboFem produced (rowptr, colind: inputs), host only: per triangle of area A
+ * M[i][i] += A / 6 and M[i][j] += A / 12 (the M of bfTrimeshGetLboFemDiscretization), so every row sums to massLumped[i].  Mdata
+ * [nnz].  Arguments are checked as bfhipTrimeshLboFem checks them, with the same codes. */
+int bfhipTrimeshLboFemMass(uint64_t numVerts, const double *verts, uint64_t numFaces, const uint64_t *faces, const uint64_t *rowptr,
+                           const uint64_t *colind, double *Mdata);
 
 /* The products, on blocks of 1 <= q <= 65535 columns; device pointers on the object's GPU; dW, dV, dX, dZ are n x q
  * doubles.  In-place use (output == input) is refused: the input is read at every step.
@@ -883,7 +888,8 @@ int bfhipChebCovCondLogLikGradDevice(BfhipCovCond *c, const double *dY, const do
  * columns -- what the reference takes from ARPACK and UMFPACK (bfGetShiftedEigs, src/linalg.c) for the lowest band, with
  * no factorisation.  lam[j] = theta_j ascending; dU [n x nev, row-major, leading dimension ldu] = the orthonormal
  * eigenvectors U of S (U^T U = I), or with BFHIP_EIGS_MASS_NORMALISED Phi = D U (Phi^T M Phi = I), the eigenfunctions of
- * the pencil.  Lumped mass only: the reference's consistent-mass pencil has other numbers.  Lowest pairs only, p <= 256 per
+ * the pencil.  The lumped mass unless BFHIP_EIGS_CONSISTENT_MASS asks for the reference's consistent-mass pencil, which has other
+ * numbers (bfhipChebCovSetConsistentMass, further down).  Lowest pairs only, p <= 256 per
  * call; bfhipChebCovEigsBandDevice below continues where a call stopped.
  *
  * Per outer iteration: a degree-m Chebyshev filter that damps [largest Ritz value, lamMax] (m <= degree, lowered so that
@@ -902,6 +908,7 @@ int bfhipChebCovCondLogLikGradDevice(BfhipCovCond *c, const double *dY, const do
  * RUNTIME_ERROR; the caller's buffers are not written in that case. */
 #define BFHIP_EIGS_MASS_NORMALISED 1u
 #define BFHIP_EIGS_NO_GUARD 2u             /* flags: ask for guard == 0 explicitly (the field's 0 means "default") */
+#define BFHIP_EIGS_CONSISTENT_MASS 4u      /* flags: the pencil S u = theta B u of bfhipChebCovSetConsistentMass (below) */
 typedef struct BfhipEigsOptions {
   uint32_t structSize;   /* in: sizeof(BfhipEigsOptions) */
   uint32_t guard;        /* extra block columns; 0 = default max(8, nev / 4), clipped so that nev + guard <= min(n, 256) */
@@ -909,8 +916,8 @@ typedef struct BfhipEigsOptions {
   uint32_t maxIter;      /* 0 = default 100 */
   double tol;            /* a pair is converged when ||S u - theta u||_2 <= tol * lamMax; 0 = default 1e-10 */
   uint64_t seed;         /* start block X[i][j] = N(seed, i * p + j), the normal stream of bfhipFillNormalDevice */
-  uint32_t flags;        /* BFHIP_EIGS_MASS_NORMALISED | BFHIP_EIGS_NO_GUARD */
-  uint32_t reserved;
+  uint32_t flags;        /* BFHIP_EIGS_MASS_NORMALISED | BFHIP_EIGS_NO_GUARD | BFHIP_EIGS_CONSISTENT_MASS */
+  uint32_t massSteps;    /* BFHIP_EIGS_CONSISTENT_MASS: steps k of every mass solve; 0 = the smallest k with 2 rho^k <= tol; <= 64 */
 } BfhipEigsOptions;
 
 typedef struct BfhipEigsInfo {
@@ -961,6 +968,30 @@ int bfhipChebCovEigsBandDevice(BfhipChebCov *c, const BfhipEigsOptions *opt, con
 /* dU[i][j] <- d[i] dU[i][j], j < count, in place (U -> Phi = D U): one multiplication per element.  INVALID_ARGUMENTS for a
  * NULL c or dU (with count > 0) and for ldu < count. */
 int bfhipChebCovEigsMassNormaliseDevice(BfhipChebCov *c, double *dU, size_t ldu, size_t count, void *stream);
+
+/* The consistent-mass pencil L phi = lambda M phi (the reference's: bfTrimeshGetLboFemDiscretization, bfGetShiftedEigs,
+ * bfGetEigenband), M on the object's CSR pattern.  bfhipChebCovSetConsistentMass folds
+ * B[i][j] = (d[i] M[i][j]) d[j], d = massLumped^-1/2 as the object holds it, on the host and uploads one more value array next to
+ * S's.  [lo, hi] must enclose the spectrum of B.  lo <= 0 && hi <= 0 asks for the P1 bounds [1/4, 1], which hold for the mass of
+ * bfhipTrimeshLboFemMass on any triangle mesh (element by element M_e has the eigenvalues A/12 {4, 1, 1} and the lumped element
+ * matrix is A/3 I); they are accepted only when every row sum of Mdata equals massLumped[i] within rounding and every diagonal
+ * entry is positive.  Otherwise 0 < lo < hi, both finite.  INVALID_ARGUMENTS, before the device is touched: a NULL argument, an
+ * entry of Mdata or a bound that is not finite, lo >= hi or lo <= 0 with bounds given, and the two P1 conditions.  A second call
+ * replaces the array after draining the device.  Neither the coefficients nor the generation counter nor any other entry is
+ * affected; bfhipChebCovFree releases the array.
+ *
+ * With BFHIP_EIGS_CONSISTENT_MASS both eigensolver entries solve S u = theta B u: the operator is A = B^-1 S, self-adjoint in the
+ * B inner product, with the upper bound lamMaxG = lamMax / lo (BfhipEigsInfo.lamMax reports it).  A filter step is T = S Y_i,
+ * Z ~ B^-1 T by massSteps steps of the Chebyshev semi-iteration on [lo, hi] (error <= 2 rho^k, rho = (sqrt(hi / lo) - 1) /
+ * (sqrt(hi / lo) + 1): 1/3 for P1), then the three-term combination; Rayleigh-Ritz runs in the B inner product (G = X^T (B X),
+ * H = X^T (S X)); the residual is r_j = ||S u_j - theta_j B u_j||_2 with u_j^T B u_j = 1, converged at <= tol * lamMaxG.  Outputs: U
+ * with U^T B U = I, or with BFHIP_EIGS_MASS_NORMALISED Phi = D U, Phi^T M Phi = I, the reference's normalisation.  Locked vectors
+ * are B-orthonormal eigenvectors of the pencil (U, not Phi); the projection is X <- X - Q (Q^T B X), twice; a locked eigenvalue
+ * above lamMaxG is refused.  operatorColumns counts the columns of B applied too.  The call allocates five blocks of n x p16
+ * doubles.  massSteps limits the accuracy: the filter's invariant subspace differs from the pencil's by about rho^k, so a k
+ * much below the default stagnates above tol.  Refused after every refusal of the lumped call, in this order: the flag on an
+ * object with no consistent mass set; massSteps > 64.  Without the flag nothing changes, with a mass set or not. */
+int bfhipChebCovSetConsistentMass(BfhipChebCov *c, const double *Mdata /* host, nnz values on the object's pattern */, double lo, double hi);
 
 /* ---- plan inspection (no device needed) ---------------------------------- */
 /* The flattened per-stage layout, as the kernels see it.  Valid only for an
