@@ -183,6 +183,18 @@ class BfhipEigsLocked(C.Structure):
                 ("lam", C.c_void_p)]
 
 
+class BfhipTruncSvdOptions(C.Structure):
+    _fields_ = [("structSize", C.c_uint32), ("maxSweeps", C.c_uint32), ("tol", C.c_double), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class BfhipTruncSvdInfo(C.Structure):
+    _fields_ = [("structSize", C.c_uint32), ("sweeps", C.c_uint32), ("k", C.c_uint64), ("numSingular", C.c_uint64), ("transposed", C.c_uint32),
+                ("reserved", C.c_uint32), ("offNorm", C.c_double), ("seconds", C.c_double), ("workspaceBytes", C.c_uint64)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n not in ("structSize", "reserved")}
+
+
 CHEB_DENSITY_FN = C.CFUNCTYPE(C.c_double, C.c_double, C.c_void_p)      # double (*f)(double, void *)
 
 
@@ -604,6 +616,9 @@ def load():
     lib.bfhipChebCovEigsBandDevice.restype = C.c_int
     lib.bfhipChebCovEigsMassNormaliseDevice.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp]
     lib.bfhipChebCovEigsMassNormaliseDevice.restype = C.c_int
+    lib.bfhipTruncSvdDevice.argtypes = [C.c_int, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(BfhipTruncSvdOptions), vp, vp, C.c_size_t, C.c_size_t,
+                                        vp, C.c_size_t, C.c_size_t, C.POINTER(BfhipTruncSvdInfo), vp]
+    lib.bfhipTruncSvdDevice.restype = C.c_int
     lib.bfhipTrimeshLboFemMass.argtypes = [C.c_uint64, vp, C.c_uint64, vp, vp, vp, vp]
     lib.bfhipTrimeshLboFemMass.restype = C.c_int
     lib.bfhipChebCovSetConsistentMass.argtypes = [vp, vp, C.c_double, C.c_double]

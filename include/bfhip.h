@@ -993,6 +993,53 @@ int bfhipChebCovEigsMassNormaliseDevice(BfhipChebCov *c, double *dU, size_t ldu,
  * object with no consistent mass set; massSteps > 64.  Without the flag nothing changes, with a mass set or not. */
 int bfhipChebCovSetConsistentMass(BfhipChebCov *c, const double *Mdata /* host, nnz values on the object's pattern */, double lo, double hi);
 
+/* ---- truncated SVD of a real f64 matrix on the device ---------------------- */
+/* What the streamer's one numerical step needs (the reference's bfGetTruncatedSvd, src/linalg.c:1002-1082, cut by
+ * bfTruncSpecGetNumTerms, src/linalg.c:26-35): A [m x n, row-major, leading dimension lda, device, left unchanged] ~ U_k W,
+ * W = S_k V_k^T.  dSigma receives all min(m, n) singular values, descending; k is the number of leading s_j with
+ * s_j >= tol * s_0; dU [m x ldu] gets its first k columns (orthonormal), dW [k x n in ldw] its first k rows; nothing else of
+ * either is written.  dU / dW may be NULL (a values-only call); capU / capW say how many columns / rows fit: with k above one
+ * of them the call returns OUT_OF_RANGE with dSigma and info->k set and U, W untouched, so a caller can size from a first call.
+ * An all-zero A returns k = 0 (the reference's rule, 0 >= tol * 0, would keep every term of it).
+ *
+ * One-sided block Jacobi on the taller orientation (B = A or A^T, M x N with M >= N, columns in tiles of 16 padded with zero
+ * columns to an even number of tiles): sweeps of N_tiles - 1 round-robin steps; per step every disjoint tile pair's 32 x 32
+ * Gram matrix on the FP64 matrix cores, its eigenvectors Q by cyclic Jacobi in LDS (larger eigenvalue first), the panel times Q
+ * on the matrix cores in place.  An entry g_ij is converged at |g_ij| <= max(32, sqrt(M)) eps sqrt(g_ii g_jj), or when one of
+ * its columns is below (32 + N) eps times the largest column norm of B as loaded; the call stops after a sweep that rotated nothing.  No V is
+ * accumulated: the columns of B end as s_j u_j.  Tall: U = B_k / s, W = U^T A; wide: W = B_k^T, U = A B_k / s^2.
+ * SYNCHRONOUS (one drain of `stream` per sweep); allocates its own workspace (the M x N block, the partial Gram matrices, and
+ * for U / W a block of M x k and the partials of one contraction) and frees it before it returns.  Every sum has one fixed
+ * order that depends on (m, n) alone: two calls give the same bits.
+ *
+ * Errors, in this order and before the device is touched: INVALID_ARGUMENTS for a NULL dA, opt or dSigma; a wrong structSize;
+ * tol <= 0 or tol >= 1 (or NaN); flags or reserved not 0; min(m, n) == 0; min(m, n) > 16384; max(m, n) > 2^32; lda < n;
+ * ldu < capU (with dU); ldw < n (with dW).  Not converged within maxSweeps: RUNTIME_ERROR with dSigma (the column norms as they
+ * stand) and info filled in, U and W not written. */
+typedef struct BfhipTruncSvdOptions {
+  uint32_t structSize;   /* in: sizeof(BfhipTruncSvdOptions) */
+  uint32_t maxSweeps;    /* 0 = default 30 */
+  double tol;            /* relative truncation tolerance, 0 < tol < 1 */
+  uint32_t flags;        /* 0 */
+  uint32_t reserved;     /* 0 */
+} BfhipTruncSvdOptions;
+
+typedef struct BfhipTruncSvdInfo {
+  uint32_t structSize;   /* in: sizeof(BfhipTruncSvdInfo) */
+  uint32_t sweeps;       /* sweeps run, the last one (which rotated nothing) included */
+  uint64_t k;            /* terms kept by the count rule */
+  uint64_t numSingular;  /* min(m, n) */
+  uint32_t transposed;   /* 1: the call worked on A^T (m < n) */
+  uint32_t reserved;
+  double offNorm;        /* the largest |g_ij| / sqrt(g_ii g_jj) the last sweep saw, noise columns left out */
+  double seconds;        /* wall clock of the call */
+  uint64_t workspaceBytes;
+} BfhipTruncSvdInfo;
+
+int bfhipTruncSvdDevice(int device /* < 0: the current one */, const double *dA, size_t m, size_t n, size_t lda, const BfhipTruncSvdOptions *opt,
+                        double *dSigma, double *dU /* or NULL */, size_t ldu, size_t capU, double *dW /* or NULL */, size_t ldw, size_t capW,
+                        BfhipTruncSvdInfo *info /* or NULL */, void *stream);
+
 /* ---- plan inspection (no device needed) ---------------------------------- */
 /* The flattened per-stage layout, as the kernels see it.  Valid only for an
  * operator compiled with BFHIP_FLAG_PLAN_ONLY (the host mirrors are dropped
