@@ -195,6 +195,19 @@ class BfhipTruncSvdInfo(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_ if n not in ("structSize", "reserved")}
 
 
+class BfhipTruncSvdProblem(C.Structure):
+    _fields_ = [("dA", C.c_void_p), ("m", C.c_uint64), ("n", C.c_uint64), ("lda", C.c_uint64), ("dSigma", C.c_void_p),
+                ("dU", C.c_void_p), ("ldu", C.c_uint64), ("capU", C.c_uint64), ("dW", C.c_void_p), ("ldw", C.c_uint64), ("capW", C.c_uint64)]
+
+
+class BfhipTruncSvdBatchInfo(C.Structure):
+    _fields_ = [("structSize", C.c_uint32), ("groups", C.c_uint32), ("maxSweeps", C.c_uint32), ("failed", C.c_uint32), ("launches", C.c_uint64),
+                ("synchronisations", C.c_uint64), ("workspaceBytes", C.c_uint64), ("seconds", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "structSize"}
+
+
 CHEB_DENSITY_FN = C.CFUNCTYPE(C.c_double, C.c_double, C.c_void_p)      # double (*f)(double, void *)
 
 
@@ -619,6 +632,9 @@ def load():
     lib.bfhipTruncSvdDevice.argtypes = [C.c_int, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(BfhipTruncSvdOptions), vp, vp, C.c_size_t, C.c_size_t,
                                         vp, C.c_size_t, C.c_size_t, C.POINTER(BfhipTruncSvdInfo), vp]
     lib.bfhipTruncSvdDevice.restype = C.c_int
+    lib.bfhipTruncSvdBatchDevice.argtypes = [C.c_int, C.POINTER(BfhipTruncSvdProblem), C.c_size_t, C.POINTER(BfhipTruncSvdOptions), C.c_uint64,
+                                             C.POINTER(BfhipTruncSvdInfo), C.POINTER(C.c_int32), C.POINTER(BfhipTruncSvdBatchInfo), vp]
+    lib.bfhipTruncSvdBatchDevice.restype = C.c_int
     lib.bfhipTrimeshLboFemMass.argtypes = [C.c_uint64, vp, C.c_uint64, vp, vp, vp, vp]
     lib.bfhipTrimeshLboFemMass.restype = C.c_int
     lib.bfhipChebCovSetConsistentMass.argtypes = [vp, vp, C.c_double, C.c_double]

@@ -354,10 +354,11 @@ class ChebCovariance:
             check(self._lib.bfhipChebCovEigsMassNormaliseDevice(self._h, C.c_void_p(U.data_ptr()), total, total, self._stream()))
         return lam, U, infos
 
-    def eigs_butterfly(self, points, total, band=64, tol=1e-3, eigs_tol=None, consistent_mass=False, return_info=False, **kw):
+    def eigs_butterfly(self, points, total, band=64, tol=1e-3, eigs_tol=None, consistent_mass=False, return_info=False, batched=False, **kw):
         """The `total` lowest eigenpairs as the operator the rest of the library applies: eigs_bands(total, band,
         mass_normalised=True), then streamer_build.stream_butterfly with freqs = sqrt(max(lam, 0)) over [0, 1.0001 freqs[-1]]
-        (kw: freq_depth, wmin, wmax, min_rows, min_cols, factorizer, dtype, check_columns and the compile options).  points
+        (kw: freq_depth, wmin, wmax, min_rows, min_cols, factorizer, dtype, check_columns and the compile options; batched=True
+        is stream_butterfly's: one batched device call per frontier of the row tree, the same operator bit for bit).  points
         [n, 3]: the mesh vertices, in the order of the object's rows.  Returns (HipOperator, row_perm, lam): the operator
         ~ Phi in tree order to the relative tolerance `tol`, row_perm an int64 tensor on the GPU and lam (numpy) -- the
         arguments cov_sample_block_device and cov_condition take, with gamma_lam a density of lam.  return_info=True appends
@@ -368,7 +369,7 @@ class ChebCovariance:
         lam, phi, infos = self.eigs_bands(total, band=band, tol=eigs_tol, mass_normalised=True, consistent_mass=consistent_mass)
         freqs = np.sqrt(np.maximum(lam, 0.0))
         wmax = kw.pop("wmax", float(freqs[-1]) * 1.0001)
-        op, perm, info = stream_butterfly(points, phi, freqs, wmax, tol=tol, device=self._dev, **kw)
+        op, perm, info = stream_butterfly(points, phi, freqs, wmax, tol=tol, device=self._dev, batched=batched, **kw)
         info["phi"], info["eigs"] = phi, infos
         perm = torch.from_numpy(perm).to(torch.device("cuda", self._dev))
         return (op, perm, lam, info) if return_info else (op, perm, lam)

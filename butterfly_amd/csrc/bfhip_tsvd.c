@@ -15,10 +15,8 @@
 #include "../../include/bfhip_abi.h"
 #include "bfhip_tsvd.h"
 
-typedef struct TsvdCol { double norm; uint32_t index; } TsvdCol;
-
 /* descending by norm, ties by the lower index: a total order, so the result does not depend on qsort's algorithm */
-static int tsvdColCmp(void const *a, void const *b) {
+int tsvdColCmp(void const *a, void const *b) {
   TsvdCol const *x = a, *y = b;
   if (x->norm != y->norm) return x->norm > y->norm ? -1 : 1;
   return x->index < y->index ? -1 : x->index > y->index;

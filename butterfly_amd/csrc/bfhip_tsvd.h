@@ -74,6 +74,16 @@ static inline uint64_t bfTsvdContractChunkRows(uint64_t M, uint32_t ld) {
 /* the sweep's counters, device: [0] pairs rotated in the sweep, [1] the bits of the largest relative off-diagonal entry seen */
 typedef struct BfTsvdSweepState { unsigned long long rotated, offBits; } BfTsvdSweepState;
 
+/* ---- the host side's own pieces (bfhip_tsvd.c), shared with the batched driver (bfhip_tsvd_batch.c) -------------------------
+ *   tsvdColCmp:            qsort comparator of the column norms: descending, ties by the lower index
+ *   bfTsvdCount:           the count rule: leading sigma_j >= tol * sigma_0; 0 for an all-zero matrix
+ *   bfTsvdCheckArguments:  the entry's refusals, in the header's order; 0 or the recorded failure (declared by its users: its types are bfhip.h's)
+ *   bfTsvdWorkspaceElems:  doubles of the sweep workspace (block, partials, Q, sums of squares) and the offsets in it */
+typedef struct TsvdCol { double norm; uint32_t index; } TsvdCol;
+int tsvdColCmp(void const *a, void const *b);
+uint64_t bfTsvdCount(double const *sigma, uint64_t count, double tol);
+uint64_t bfTsvdWorkspaceElems(uint64_t M, uint32_t ld, uint64_t *offPart, uint64_t *offQ, uint64_t *offSumSq);
+
 /* ---- launches (bfhip_tsvd.hip); every block is row-major ------------------------------------------------------------------
  *   load:      B [M x ld] = A (m x n in lda) or A^T, padding columns zero
  *   step:      one round-robin step of one sweep over all nt / 2 pairs: partial Gram matrices per chunk, the pair solves (Q

@@ -1040,6 +1040,52 @@ int bfhipTruncSvdDevice(int device /* < 0: the current one */, const double *dA,
                         double *dSigma, double *dU /* or NULL */, size_t ldu, size_t capU, double *dW /* or NULL */, size_t ldw, size_t capW,
                         BfhipTruncSvdInfo *info /* or NULL */, void *stream);
 
+/* ---- many truncated SVDs in one call ---------------------------------------- */
+/* The independent SVDs of one frontier of the streamer (all row nodes of one depth of a feed, or of a merge) in one call: every
+ * kernel launch covers all problems, and the host waits once per sweep of the batch instead of once per sweep of every problem.
+ * Each problem gets exactly what bfhipTruncSvdDevice gives it -- orientation, padding, thresholds, its own noise level, its own
+ * number of sweeps, the sort, the count rule, U and W -- and BIT FOR BIT so: the kernels run the single call's device code on
+ * the problem's own parameters, and no sum's order depends on the other problems, on their number, on their order or on the
+ * grouping below.  A problem that has converged is skipped on the device from then on.
+ *
+ * problems: host array of `count` (<= 2^20) problems, device pointers inside, each with the meaning of the single call's
+ * arguments; the problems must not overlap in what they write.  infos[i] (or NULL) is filled as the single call fills it, apart
+ * from seconds and workspaceBytes, which are 0: they belong to the batch.  status[i] (or NULL) is the code the single call would
+ * return for problem i: 0; INVALID_ARGUMENTS for a non-finite column (nothing of the problem written, infos[i] untouched);
+ * RUNTIME_ERROR when maxSweeps sweeps did not converge (dSigma holds the column norms, U and W untouched); OUT_OF_RANGE for
+ * k > capU or k > capW (dSigma and infos[i].k set, U and W untouched).  A failed problem does not stop the others.  The call
+ * returns the status of the lowest-index failed problem, its message (prefixed "problem i: ") in bfhipLastErrorMessage, or 0.
+ *
+ * Refused before a device is touched, nothing run, in this order: INVALID_ARGUMENTS for a NULL opt or (with count > 0) NULL
+ * problems; a wrong structSize of opt or batch; count > 2^20; then, problem by problem, every refusal of bfhipTruncSvdDevice in
+ * its order (infos[i].structSize included), the message being the single call's prefixed "problem i: ".  count == 0 returns 0.
+ *
+ * Workspace: the problems are processed in consecutive groups whose summed device workspace (per problem: what the single call
+ * allocates for the sweeps, plus its recovery stage at k = min(m, n) when dU or dW is given) fits workspaceLimitBytes; 0 means
+ * 1 GiB.  A problem above the limit is a group of its own.  One allocation per group for the sweeps and one for the recovery.
+ * SYNCHRONOUS.  batch->synchronisations is, exactly, the sum over the groups of (the largest sweep count in the group + 3): one
+ * wait for the sums of squares of the blocks as loaded, one per sweep, one for the final column norms, one at the end; with one
+ * group that is batch->maxSweeps + 3.  batch->launches counts kernel launches: per group 3 for the load and its sums, per sweep
+ * 3 (max tiles of a still active problem - 1) + 1, then 2 + 1 and at most 6 for the recovery. */
+typedef struct BfhipTruncSvdProblem {
+  const double *dA; uint64_t m, n, lda;
+  double *dSigma;                          /* min(m, n) */
+  double *dU; uint64_t ldu, capU;          /* dU may be NULL */
+  double *dW; uint64_t ldw, capW;          /* dW may be NULL */
+} BfhipTruncSvdProblem;
+
+typedef struct BfhipTruncSvdBatchInfo {
+  uint32_t structSize, groups;             /* in: sizeof(BfhipTruncSvdBatchInfo); groups: consecutive sub-batches the workspace limit forced */
+  uint32_t maxSweeps, failed;              /* largest sweep count of a problem; problems whose status != 0 */
+  uint64_t launches, synchronisations;     /* kernel launches and stream synchronisations of the whole call */
+  uint64_t workspaceBytes;                 /* peak over the groups */
+  double seconds;                          /* wall clock of the call */
+} BfhipTruncSvdBatchInfo;
+
+int bfhipTruncSvdBatchDevice(int device /* < 0: the current one */, const BfhipTruncSvdProblem *problems, size_t count, const BfhipTruncSvdOptions *opt,
+                             uint64_t workspaceLimitBytes /* 0: 1 GiB */, BfhipTruncSvdInfo *infos /* [count] or NULL */,
+                             int32_t *status /* [count] or NULL */, BfhipTruncSvdBatchInfo *batch /* or NULL */, void *stream);
+
 /* ---- plan inspection (no device needed) ---------------------------------- */
 /* The flattened per-stage layout, as the kernels see it.  Valid only for an
  * operator compiled with BFHIP_FLAG_PLAN_ONLY (the host mirrors are dropped

@@ -13,7 +13,12 @@ Times: the device call on a matrix already on the GPU (host clock around the syn
 calls, all listed); gesdd on the host copy, BLAS threads as numpy finds them (one call above 1e7 elements, else as many as the
 device).  A shape whose sweeps would move more than --budget-tb terabytes (24 M ld (tiles - 1) x 10 sweeps: Gram read, rotate read
 and write) is listed as skipped with that estimate, not run.  The launch count of a call is 3 per step (Gram, solve, rotate),
-(tiles - 1) steps per sweep, plus the load, the norms and at most six launches for U and W."""
+(tiles - 1) steps per sweep, plus the load, the norms and at most six launches for U and W.
+
+--batched builds with one bfhipTruncSvdBatchDevice call per frontier of the row tree and adds the
+per-batch record (count, launches, synchronisations, seconds) to the build's figures.  --batch-family C times one batched call
+on C stand-ins of the 20-60-row family of the n32768 records (numpy blocks in, numpy factors out: what the streamer pays) against
+the loop of C single calls on the same blocks; the median of --repeat after a warm-up, every run listed."""
 import argparse
 import json
 import os
@@ -82,7 +87,42 @@ def time_shape(m, n, k, repeat, budget_tb, tol=1e-3):
     return row
 
 
-def whole_build(n, lmax, tol=1e-3, max_sweeps=None, freq_depth=None):
+def family_blocks(count):
+    """numpy stand-ins of the first `count` recorded SVDs with 20 to 60 rows (tests/golden/streamer_svd_records_n32768.npz)."""
+    recs = np.load(os.path.join(ROOT, "tests", "golden", "streamer_svd_records_n32768.npz"))["records"]
+    small = recs[(recs[:, 0] >= 20) & (recs[:, 0] <= 60)][:count]
+    return [stand_in(int(r[0]), int(r[1]), int(r[4]), 2000 + i).cpu().numpy() for i, r in enumerate(small)]
+
+
+def time_family(count, repeat, tol=1e-3):
+    import torch
+    from butterfly_amd.streamer_build import truncated_svd_batch_device, truncated_svd_device
+    blocks = family_blocks(count)
+    row = dict(count=len(blocks), shapes=[list(b.shape) for b in blocks[:3]], rows=[int(min(b.shape[0] for b in blocks)), int(max(b.shape[0] for b in blocks))],
+               cols=[int(min(b.shape[1] for b in blocks)), int(max(b.shape[1] for b in blocks))])
+    res = truncated_svd_batch_device(blocks, tol)                            # warm-up of both paths
+    ref = [truncated_svd_device(b, tol) for b in blocks]
+    row["identical"] = all(r[0] == q[0] and r[1].tobytes() == q[1].tobytes() and r[2].tobytes() == q[2].tobytes() and r[3].tobytes() == q[3].tobytes()
+                           for r, q in zip(res, ref))
+    batch, loop, inner = [], [], []
+    for _ in range(repeat):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        res = truncated_svd_batch_device(blocks, tol)
+        batch.append(time.perf_counter() - t0)
+        inner.append(res[0][4]["batch"]["seconds"])
+        t0 = time.perf_counter()
+        ref = [truncated_svd_device(b, tol) for b in blocks]
+        loop.append(time.perf_counter() - t0)
+    b = res[0][4]["batch"]
+    sweeps = [int(r[4]["sweeps"]) for r in ref]
+    row.update(batch_seconds=batch, loop_seconds=loop, batch_call_seconds=inner, batch_median=float(np.median(batch)), loop_median=float(np.median(loop)),
+               loop_over_batch=float(np.median(loop) / np.median(batch)), launches=int(b["launches"]), synchronisations=int(b["synchronisations"]),
+               loop_synchronisations_at_least=int(sum(s + 3 for s in sweeps)), sweeps=[min(sweeps), max(sweeps)], workspace_bytes=int(b["workspaceBytes"]))
+    return row
+
+
+def whole_build(n, lmax, tol=1e-3, max_sweeps=None, freq_depth=None, batched=False):
     from butterfly_amd import streamer_build as sb
     from oracle import streamer_values as sv              # the sphere's eigenfunctions: test infrastructure used as an input generator
     t0 = time.perf_counter()
@@ -96,13 +136,28 @@ def whole_build(n, lmax, tol=1e-3, max_sweeps=None, freq_depth=None):
                 print(json.dumps(dict(svds=len(self.record), svd_seconds=round(self.seconds, 2), elapsed=round(time.perf_counter() - t0, 1))), flush=True)
             return out
 
+        def svd_many(self, requests):
+            out = super().svd_many(requests)
+            print(json.dumps(dict(svds=len(self.record), batch=len(requests), svd_seconds=round(self.seconds, 2), elapsed=round(time.perf_counter() - t0, 1))),
+                  flush=True)
+            return out
+
     print(json.dumps(dict(input_seconds=round(t_input, 1))), flush=True)
-    op, perm, info = sb.stream_butterfly(pts, phi, freqs, wmax, freq_depth=freq_depth, tol=tol, check_columns=4, factorizer=Progress(tol, 0, [], max_sweeps))
+    op, perm, info = sb.stream_butterfly(pts, phi, freqs, wmax, freq_depth=freq_depth, tol=tol, check_columns=4, factorizer=Progress(tol, 0, [], max_sweeps),
+                                         batched=batched)
     rec = np.asarray([(m, nn, k, s) for m, nn, k, s, _ in info["svd_records"]])
     out = dict(n=n, columns=int(info["columns"]), freq_depth=info["freq_depth"], svds=info["svds"], merges=info["merges"], feeds=info["feeds"],
                seconds=info["seconds"], svd_seconds=info["svd_seconds"], host_seconds=info["host_seconds"], compile_seconds=info["compile_seconds"],
                input_seconds=t_input, leaf_bytes=info["leaf_bytes"], acceptance=info["acceptance"], max_sweeps=int(rec[:, 3].max()), sweep_cap=30 if max_sweeps is None else int(max_sweeps), svds_above_30_sweeps=int(np.sum(rec[:, 3] > 30)),
                max_rows=int(rec[:, 0].max()), max_cols=int(rec[:, 1].max()), wide=int(np.sum(rec[:, 0] < rec[:, 1])), single_run=True)
+    if batched:
+        b = info["svd_batches"]
+        out.update(batched=True, batches=len(b), largest_batch=max(c for c, *_ in b), launches=int(sum(x[1] for x in b)),
+                   synchronisations=int(sum(x[2] for x in b)), batch_records=[list(x) for x in b])
+    else:
+        # per call: 3 launches per step of a sweep, 3 + 2 for the load and the two sums, at most 5 for U and W; one wait per sweep and three more
+        tiles = (np.minimum(rec[:, 0], rec[:, 1]) + 31) // 32 * 2
+        out.update(batched=False, launches_at_most=int(np.sum(3 * (tiles - 1) * rec[:, 3] + 10)), synchronisations_at_least=int(np.sum(rec[:, 3] + 3)))
     op.close()
     return out
 
@@ -116,6 +171,8 @@ def main():
     ap.add_argument("--build-lmax", type=int, default=63)
     ap.add_argument("--build-max-sweeps", type=int, default=None, help="sweep cap of the build's SVDs (default: the library's 30)")
     ap.add_argument("--build-freq-depth", type=int, default=None, help="levels of the frequency tree (default: row-tree depth - 3)")
+    ap.add_argument("--batched", action="store_true", help="build with one batched device call per frontier of the row tree")
+    ap.add_argument("--batch-family", type=int, default=0, help="time a batch of this many 20-60-row stand-ins against the loop of single calls")
     ap.add_argument("--no-build", action="store_true")
     ap.add_argument("--no-shapes", action="store_true")
     a = ap.parse_args()
@@ -139,8 +196,12 @@ def main():
                 print(json.dumps(row), flush=True)
                 res["shapes"].append(row)
                 flush()
+    if a.batch_family:
+        res["batch_family"] = time_family(a.batch_family, a.repeat)
+        print(json.dumps(res["batch_family"]), flush=True)
+        flush()
     if not a.no_build:
-        res["build"] = whole_build(a.build_n, a.build_lmax, max_sweeps=a.build_max_sweeps, freq_depth=a.build_freq_depth)
+        res["build"] = whole_build(a.build_n, a.build_lmax, max_sweeps=a.build_max_sweeps, freq_depth=a.build_freq_depth, batched=a.batched)
         print(json.dumps(res["build"]), flush=True)
     flush()
     print(json.dumps(dict(done=True, shapes=len(res["shapes"]), build="build" in res)))
